@@ -7,13 +7,23 @@ spawns the N ranks itself (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_* set, before anything here touches the GPU runtime) and relays rank
 0's line; under `torch.distributed.run` it is one of the ranks.
 
+A plain run does what the headline needs and nothing else: it sets up the
+headline ensemble, warms up, times exactly K steps (`ms_per_step` is one of
+them) and prints the line.  Everything below that is not the headline -- the
+other workloads in `extra`, the 1-GPU scaling references, the CPU baseline,
+the per-launch spread, the diagnostic counter and the result windows -- runs
+with `--full` only.  `--dump-outputs DIR` writes what the timed path computed
+in its last step as DIR/<name>.npy (float64; a fixed sample of the rows where
+the whole state would be larger than 64 MB); the inputs are seeded, so two
+builds compare output for output.
+
 What a "step" is and which workload is the headline:
 
 * N = 1 -- BASELINE.json configs[1]: mrbp_qmc VMC, N = 64 bosons, 2^20
   independent chains; a step is one all-particle Metropolis step of every
-  chain including the local energy.  `extra.dmc` is configs[2] (DMC, N = 64,
-  2^18 walkers) and `extra.c4_dmc_sharded` the multi-GPU workload run on this
-  one GPU (the strong-scaling reference point).
+  chain including the local energy.  With `--full`, `extra.dmc` is configs[2]
+  (DMC, N = 64, 2^18 walkers) and `extra.c4_dmc_sharded` the multi-GPU
+  workload run on this one GPU (the strong-scaling reference point).
 * N > 1 -- BASELINE.json configs[3]: mrbp_qmc DMC, N = 128 bosons, ONE
   population of 2^22 walkers (global target) sharded over the ranks
   (`dist.DistributedDmc`): per time step every rank branches and propagates
@@ -25,17 +35,17 @@ What a "step" is and which workload is the headline:
   conservation and bit-identical E_ref on all ranks are asserted and
   `extra.phases` times the all-reduce, the host enqueue, the rebalances and the
   evolve kernel.  Total work is fixed as N grows: `"scaling": "strong"`.
-  `extra.vmc_weak` is the VMC workload at 2^20 chains per GPU.
+  With `--full`, `extra.vmc_weak` is the VMC workload at 2^20 chains per GPU.
 
 Both scaling curves from ONE run at each N: every line, at every --gpus,
 carries `extra.curves = {"vmc_n64_weak": <walker-steps/s>, "dmc_n128_strong":
 <walker-steps/s>}` under the same keys -- the two workloads are never mixed in
 one curve, whatever `value` is at that N -- and `extra.strong_scaling` /
-`extra.weak_scaling` = {ref_1gpu, speedup, efficiency}.  At N > 1 the 1-GPU
-reference points are measured IN THE SAME RUN on rank 0's GPU (the full
-population of configs[3] / one rank's VMC share, through the same code, while
-the other ranks wait at a barrier), so that an efficiency never stitches two
-boxes together; at N = 1 they are the run itself.
+`extra.weak_scaling` = {ref_1gpu, speedup, efficiency}.  At N > 1 (`--full`)
+the 1-GPU reference points are measured IN THE SAME RUN on rank 0's GPU (the
+full population of configs[3] / one rank's VMC share, through the same code,
+while the other ranks wait at a barrier), so that an efficiency never stitches
+two boxes together; at N = 1 they are the run itself.
 
 The ensembles are timed in the STATIONARY state of the chain, the state a
 production run spends its time in.  That state is far from a random start: E/N
@@ -49,16 +59,17 @@ now takes `--pre-equil` (30 000) steps from one particle per lattice well --
 one second of GPU time at that size -- every chain starts from one of its
 configurations and `--equil` (320) steps with the chains' own random streams
 take the copies apart (`HipBackend.equilibrated_vmc`; the CPU baseline starts
-from the same seed configurations).  The result windows (energy per particle,
-acceptance: the stationary values) are asserted in here, and the line carries
-both; with `--unrelaxed`, `extra.vmc_unrelaxed_start` is the same kernel on the
-old ensemble in the same run.  Inputs are resident in HBM when a timed region starts.  `roofline` is the HBM view the metric contract
-asks for: algorithmic bytes of SURVEY.md 8(d) over the dominant kernel's own
-duration, measured with HIP events on the stream it is launched on; the path
-is fp64-VALU bound, so `extra.valu` gives the pair-evaluation rate as well.
-`cpu_baseline` (N = 1, rank 0) times the CPU oracle -- the C restatement of
-the reference algorithm, OpenMP over chains, rebuilt here with -O3
--march=native -- on bounded samples of the same workload: on every core of the
+from the same seed configurations).  With `--full` the result windows (energy
+per particle, acceptance: the stationary values) are asserted in here, and the
+line carries both; with `--unrelaxed`, `extra.vmc_unrelaxed_start` is the same
+kernel on the old ensemble in the same run.  Inputs are resident in HBM when a
+timed region starts.  `roofline` is the HBM view the metric contract asks for:
+algorithmic bytes of SURVEY.md 8(d) over the dominant kernel's own duration,
+measured with HIP events on the stream it is launched on; the path is fp64-VALU
+bound, so `extra.valu` gives the pair-evaluation rate as well.  `cpu_baseline`
+(N = 1, rank 0, `--full`) times the CPU oracle -- the C restatement of the
+reference algorithm, OpenMP over chains, rebuilt here with -O3 -march=native --
+on bounded samples of the same workload: on every core of the
 affinity mask and on 16 threads (`runs`; `value` is the better), and on
 BASELINE configs[0] (`c1`).  `"backend"` names the engine that produced the
 line ("hip"; the CPU stand-ins of tests/ say so).
@@ -87,6 +98,7 @@ VMC_E_WINDOW = (15.30, 15.50)       # stationary: 15.395 (15.73 after 320 steps
                                     # from a uniform random start, 15.40 after 40 000)
 VMC_ACC_WINDOW = (0.43, 0.47)       # stationary: 0.450
 DMC_E_WINDOW = (15.20, 15.90)       # relaxing from the VMC value towards 15.46
+DUMP_BYTES = 64 << 20               # --dump-outputs: all arrays together
 
 
 def box_spec(n):
@@ -119,6 +131,13 @@ def parse_args(argv=None):
     ap.add_argument('--c4-walkers', type=int, default=1 << 22,
                     help='GLOBAL target population of the sharded DMC run')
     ap.add_argument('--rebalance-every', type=int, default=16)
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: the other workloads, the '
+                         'same-run scaling references, the CPU baseline, the '
+                         'per-launch spread and the result windows')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the timed path computed in its last '
+                         'step to DIR/<name>.npy')
     ap.add_argument('--no-dmc', action='store_true')
     ap.add_argument('--no-c4', action='store_true',
                     help='skip the sharded-DMC workload at --gpus 1')
@@ -425,8 +444,11 @@ def load_traffic(n, kernel, path=None, loaded=None):
 
 # ---------------------------------------------------------------- VMC leg ---
 def bench_vmc(be, args, rank, world, use_pg, n, W, fast_math=False,
-              unrelaxed=False):
-    """Timed VMC run of this rank's W chains -> dict of raw measurements."""
+              unrelaxed=False, diag=True, dump=None):
+    """Timed VMC run of this rank's W chains -> dict of raw measurements.
+    `diag`: also the diagnostic counter over the timed region, the per-launch
+    spread and the estimators (energy, acceptance) of one more block; `dump`:
+    directory for the state the last timed step left."""
     import torch
     import torch.distributed as dist
     eng = be.engine(n, fast_math)
@@ -457,7 +479,7 @@ def bench_vmc(be, args, rank, world, use_pg, n, W, fast_math=False,
     run_steps(args.warmup)
     # (device counter of walkers that leave the sorted-row pair sums: read
     # over the timed region -- which code did the timed kernel run?)
-    gp = getattr(eng, 'general_path_walkers', None)
+    gp = getattr(eng, 'general_path_walkers', None) if diag else None
     if gp is not None:
         gp(reset=True)
     barrier()
@@ -472,6 +494,11 @@ def bench_vmc(be, args, rank, world, use_pg, n, W, fast_math=False,
         tmax = torch.tensor([dt], dtype=torch.float64, device=be.device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if dump:
+        write_outputs(dump, vmc_outputs(vmc))
+    m = dict(vmc=vmc, eng=eng, dt=dt, kernel_ms=kernel_ms, launches=launches)
+    if not diag:
+        return m
     # per-launch spread: every launch bracketed by its own event pair
     eng.profile_begin(args.block * 4)
     vmc.run_block(args.block * 4, sums=False)
@@ -485,12 +512,41 @@ def bench_vmc(be, args, rank, world, use_pg, n, W, fast_math=False,
     if use_pg:
         dist.all_reduce(tot)
     tot = tot.cpu().numpy()
-    return dict(vmc=vmc, eng=eng, dt=dt, kernel_ms=kernel_ms,
-                launches=launches, general_path_walkers=gp_timed,
-                launch_ms_avg_isolated=tot_ms / max(nl, 1),
-                launch_ms_min=min_ms, launch_ms_max=max_ms,
-                energy_per_particle=float(tot[0] / tot[2] / n),
-                accept_rate=float(tot[1] / tot[2]))
+    m.update(general_path_walkers=gp_timed,
+             launch_ms_avg_isolated=tot_ms / max(nl, 1),
+             launch_ms_min=min_ms, launch_ms_max=max_ms,
+             energy_per_particle=float(tot[0] / tot[2] / n),
+             accept_rate=float(tot[1] / tot[2]))
+    return m
+
+
+def vmc_outputs(vmc):
+    """What a caller of the timed step receives: the state of every chain
+    after the last step (positions, log |psi|, local energy) -- a fixed
+    sample of the chains where all of them would be more than 48 MB --, and
+    the chain index of each row."""
+    import numpy as np
+    pos, wf, ec = vmc.get_state()
+    W, n = pos.shape
+    rows = min(W, (48 << 20) // (8 * (n + 3)))
+    idx = np.arange(W) if rows == W else np.sort(
+        np.random.RandomState(0).choice(W, rows, replace=False))
+    return {'vmc_chain': idx, 'vmc_pos': pos[idx],
+            'vmc_wf_abs_log': wf[idx], 'vmc_energy': ec[idx]}
+
+
+def write_outputs(dirname, arrays):
+    """{name: array} -> dirname/<name>.npy in float64, at most DUMP_BYTES."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64)
+              for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise SystemExit(f'bench.py: {total} bytes of outputs, more than '
+                         f'{DUMP_BYTES}')
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + '.npy'), a)
 
 
 def vmc_line(args, m, n, W, world):
@@ -503,7 +559,7 @@ def vmc_line(args, m, n, W, world):
     tj, traffic_note = load_traffic(n, 'vmc_step_kernel')
     traffic = tj.get('bytes_per_chain_step')
     valu = tj.get('valu_instr_per_chain_step')
-    return {
+    line = {
         'metric': 'walker-steps/sec',
         'value': value,
         'unit': 'walker-steps/s',
@@ -548,13 +604,16 @@ def vmc_line(args, m, n, W, world):
                 (W * valu / (launch_ms * 1e-3)) / (1024 * 2.4e9 / 4),
                 'note': 'the path is fp64-VALU bound (SURVEY.md 8d); unique '
                         'pairs N(N-1)/2 per chain-step'},
-            'launch_ms_isolated_avg': m['launch_ms_avg_isolated'],
-            'launch_ms_min': m['launch_ms_min'],
-            'launch_ms_max': m['launch_ms_max'],
-            'vmc_energy_per_particle': m['energy_per_particle'],
-            'vmc_accept_rate': m['accept_rate'],
         },
     }
+    if 'accept_rate' in m:           # (measured by the diagnostic run)
+        line['extra'].update(
+            launch_ms_isolated_avg=m['launch_ms_avg_isolated'],
+            launch_ms_min=m['launch_ms_min'],
+            launch_ms_max=m['launch_ms_max'],
+            vmc_energy_per_particle=m['energy_per_particle'],
+            vmc_accept_rate=m['accept_rate'])
+    return line
 
 
 # ---------------------------------------------------------------- DMC legs --
@@ -603,9 +662,10 @@ def bench_dmc_single(be, args, n, vmc, target):
     }
 
 
-def bench_dmc_sharded(be, args, rank, world, use_pg, solo=False):
+def bench_dmc_sharded(be, args, rank, world, use_pg, solo=False, dump=None):
     """configs[3]: ONE population of --c4-walkers (global target) sharded over
-    the ranks.  -> dict (identical on every rank).
+    the ranks.  -> dict (identical on every rank).  `dump`: directory for the
+    global series (E_t, W_t, E_ref) of the timed steps (rank 0 writes it).
 
     At world > 1 the ranks start deliberately unequal (+-`--start-skew` of
     their share) and the population is levelled by FORCED rebalances -- one in
@@ -708,7 +768,12 @@ def bench_dmc_sharded(be, args, rank, world, use_pg, solo=False):
         raise SystemExit('bench.py: the forced rebalance moved no walker; '
                          'the RCCL transfer path was not exercised')
     e_per = float(np.sum(e_glob) / np.sum(w_glob) / n)
-    check_window('sharded DMC energy per particle', e_per, DMC_E_WINDOW, args)
+    if args.full:
+        check_window('sharded DMC energy per particle', e_per, DMC_E_WINDOW,
+                     args)
+    if dump and rank == 0:
+        write_outputs(dump, {'dmc_energy': e_glob, 'dmc_weight': w_glob,
+                             'dmc_ref_energy': cat('ref_energy', 3)})
     b_dmc = 32 * n + 40 + 16
     out = {
         'workload': f'mrbp_qmc DMC, N={n} bosons, ONE population of target '
@@ -989,16 +1054,20 @@ def run_rank(args):
     ref_detail = None
     if world == 1:
         # ---- headline: VMC, configs[1] ----
-        m = bench_vmc(be, args, rank, world, use_pg, n, W)
-        check_window('VMC energy per particle', m['energy_per_particle'],
-                     VMC_E_WINDOW, args)
-        check_window('VMC acceptance', m['accept_rate'], VMC_ACC_WINDOW, args)
+        m = bench_vmc(be, args, rank, world, use_pg, n, W, diag=args.full,
+                      dump=args.dump_outputs)
         out = vmc_line(args, m, n, W, world)
         curves[key_v] = ref_v = out['value']
-        # walkers of the timed region evaluated by the general pair sum
-        # instead of the sorted-row one (of W x steps evaluations)
-        out['extra']['general_path_walkers_timed'] = m['general_path_walkers']
-        if not args.no_dmc:
+        if args.full:
+            check_window('VMC energy per particle', m['energy_per_particle'],
+                         VMC_E_WINDOW, args)
+            check_window('VMC acceptance', m['accept_rate'], VMC_ACC_WINDOW,
+                         args)
+            # walkers of the timed region evaluated by the general pair sum
+            # instead of the sorted-row one (of W x steps evaluations)
+            out['extra']['general_path_walkers_timed'] = \
+                m['general_path_walkers']
+        if args.full and not args.no_dmc:
             out['extra']['dmc'] = bench_dmc_single(be, args, n, m['vmc'],
                                                    args.dmc_walkers)
         m['vmc'].close()
@@ -1034,23 +1103,24 @@ def run_rank(args):
                         f'wavefront; NOT the headline',
             }
             mu['vmc'].close()
-        if not args.no_c4:
+        if args.full and not args.no_c4:
             s = bench_dmc_sharded(be, args, rank, world, use_pg)
             out['extra']['c4_dmc_sharded'] = dict(
                 s, note='the --gpus N > 1 headline workload on ONE GPU: the '
                         'strong-scaling reference point')
             curves[key_d] = ref_d = s['walker_steps_per_s']
-        if not args.no_cpu and rank == 0:
+        if args.full and not args.no_cpu and rank == 0:
             spec = box_spec(n)
             out['cpu_baseline'] = cpu_baseline(
                 args, spec, n, 0.25 * spec.well_width,
                 start=getattr(be, 'seed_confs', {}).get(n))
     else:
         # ---- headline: ONE sharded DMC population, configs[3] ----
-        s = bench_dmc_sharded(be, args, rank, world, use_pg)
+        s = bench_dmc_sharded(be, args, rank, world, use_pg,
+                              dump=args.dump_outputs)
         out = sharded_line(args, s, world)
         curves[key_d] = out['value']
-        if be.has_vmc and not args.no_vmc_extra:
+        if args.full and be.has_vmc and not args.no_vmc_extra:
             m = bench_vmc(be, args, rank, world, use_pg, n, W)
             lv = vmc_line(args, m, n, W, world)
             out['extra']['vmc_weak'] = {
@@ -1062,7 +1132,7 @@ def run_rank(args):
             }
             curves[key_v] = lv['value']
             m['vmc'].close()
-        if not args.no_scaling_ref:
+        if args.full and not args.no_scaling_ref:
             # The 1-GPU reference points, in this run, on this box: rank 0
             # alone runs the WHOLE population of configs[3] (and one rank's
             # VMC share) through the same code while the other ranks wait at

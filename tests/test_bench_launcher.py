@@ -29,7 +29,7 @@ def test_bench_spawns_two_ranks(oracle):
     r = run_bench(['--gpus', '2', '--steps', '6', '--warmup', '2',
                    '--c4-bosons', '8', '--c4-walkers', '48',
                    '--rebalance-every', '2', '--start-skew', '0.25',
-                   '--no-checks'],
+                   '--no-checks', '--full'],
                   {'QMC_BENCH_BACKEND': 'tests._bench_standin'})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -78,6 +78,47 @@ def test_bench_spawns_two_ranks(oracle):
     assert 'same run' in ss['ref_measured']
     assert 30 < ss['ref_detail']['mean_walkers'] < 70   # the WHOLE population
     assert ex['weak_scaling'] is None
+
+
+@pytest.mark.timeout(300)
+def test_plain_run_is_the_headline_and_dumps_its_outputs(oracle, tmp_path):
+    """Without --full the run is the headline alone (no same-run 1-GPU
+    reference), and --dump-outputs writes the global series of the timed
+    steps: float64, one row per timed step, identical from run to run."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f'out{k}'
+        r = run_bench(['--gpus', '2', '--steps', '6', '--warmup', '2',
+                       '--c4-bosons', '8', '--c4-walkers', '48',
+                       '--rebalance-every', '2', '--start-skew', '0.25',
+                       '--dump-outputs', str(d)],
+                      {'QMC_BENCH_BACKEND': 'tests._bench_standin'})
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out['n_gpus'] == 2 and out['steps'] == 6
+        assert out['metric'] == 'walker-steps/sec' and out['value'] > 0
+        assert out['ms_per_step'] > 0
+        ex = out['extra']
+        assert ex['strong_scaling'] is None and ex['weak_scaling'] is None
+        assert ex['curves']['dmc_n8_strong'] == out['value']
+        # the forced rebalances are part of the headline workload
+        assert ex['walkers_moved_warmup_all_ranks'] >= 12
+        names = sorted(os.listdir(d))
+        assert names == ['dmc_energy.npy', 'dmc_ref_energy.npy',
+                         'dmc_weight.npy']
+        arrs = {nm: np.load(d / nm) for nm in names}
+        for a in arrs.values():
+            assert a.dtype == np.float64 and a.shape == (6,)
+            assert np.all(np.isfinite(a))
+        # W_t of every step is the sum over both ranks
+        assert np.all((30 < arrs['dmc_weight.npy']) &
+                      (arrs['dmc_weight.npy'] < 70))
+        dumps.append(arrs)
+    for nm in dumps[0]:
+        assert np.array_equal(dumps[0][nm], dumps[1][nm]), nm
 
 
 def test_bench_refuses_world_size_mismatch():

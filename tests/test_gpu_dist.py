@@ -278,7 +278,8 @@ def test_bench_two_ranks_on_one_gpu_real_engine():
         [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2',
          '--steps', '12', '--warmup', '4', '--equil', '100', '--pre-equil', '500',
          '--c4-bosons', '128', '--c4-walkers', '16384', '--chains', '4096',
-         '--rebalance-every', '4', '--launch-timeout', '500', '--no-checks'],
+         '--rebalance-every', '4', '--launch-timeout', '500', '--no-checks',
+         '--full'],
         env=env, capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

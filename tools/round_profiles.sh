@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (GPU box, repo root): tools/round_profiles.sh <outdir under gpurun_out> [bench|pmc|all]
 # The measurement records of a round at the kernels in the tree (development
-# tool): the default bench line, the same command under `rocprofv3
+# tool): the full bench line (--full), the same command under `rocprofv3
 # --kernel-trace --stats` (the program itself after `--`, counters never mixed
 # with other trace domains), and the kernel-trace + counter passes of
 # tools/profile.sh for the VMC step at N = 64 and the DMC step at N = 64 / 128.
@@ -12,10 +12,10 @@ out=$R/gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
 if [ "$what" = bench ] || [ "$what" = all ]; then
-  python3 $R/bench.py --steps 20 --warmup 5 --fp32 --unrelaxed > $out/bench.json 2> $out/bench.err
+  python3 $R/bench.py --steps 20 --warmup 5 --full --fp32 --unrelaxed > $out/bench.json 2> $out/bench.err
   echo "bench rc=$?"
   (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_prof -- \
-      python3 $R/bench.py --steps 20 --warmup 5 --no-cpu > $out/bench_under_rocprof.json 2> $out/bench_prof.err)
+      python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu > $out/bench_under_rocprof.json 2> $out/bench_prof.err)
   echo "bench under rocprofv3 rc=$?"
   f=$(ls $out/bench_prof/*/*kernel_stats.csv 2>/dev/null | head -1)
   [ -n "$f" ] && cp $f $out/bench_kernel_stats.csv
