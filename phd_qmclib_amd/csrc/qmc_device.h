@@ -332,14 +332,17 @@ __device__ __forceinline__ void dmc_normal2(uint64_t seed, uint32_t slot,
 // ------------------------------------------------------------ helpers ----
 // Periodic wrap into [0, L) with the reference's floor-mod result
 // (qmc_base/utils.py:55-66) for excursions of less than one box length.
+// One period out (every move of a spread below L): two selects, no branch.
+// The division runs only when some lane of the wavefront is further out; the
+// test is a ballot, so the branch is wave-uniform (a scalar branch, no exec
+// mask).  Same arithmetic as the nested form: the results are bit-identical.
 __device__ __forceinline__ double wrap_box(double z, double L)
 {
-    if (z < 0.0) {
-        z = (z >= -L) ? z + L : z - L * floor(z / L);
-    } else if (z >= L) {
-        z = (z < 2.0 * L) ? z - L : z - L * floor(z / L);
-    }
-    return z;
+    double zw = (z < 0.0) ? z + L : (z >= L) ? z - L : z;
+    const bool far = z < -L || z >= 2.0 * L;
+    if (__builtin_expect(__ballot(far) != 0ull, 0))
+        zw = far ? z - L * floor(z / L) : zw;
+    return zw;
 }
 
 // Slot (index into the walker's row of positions) held by (lane gl, register p)
@@ -368,6 +371,15 @@ template <int G, bool PAD>
 __device__ __forceinline__ int lanes_in_use(const DevModel &m)
 {
     return PAD ? m.ge : G;
+}
+
+// Particles of a walker.  An unpadded shape holds exactly G P of them (the
+// host picks PAD = n != G P, qmcwalk.hip: pick_shape): a compile-time
+// constant there, so that `i < n` guards fold away and `w * n` is a shift.
+template <int G, int P, bool PAD>
+__device__ __forceinline__ int walker_n(const DevModel &m)
+{
+    return PAD ? m.n : G * P;
 }
 
 template <int G, int P, bool PAD>
@@ -1290,7 +1302,7 @@ __device__ __forceinline__ void eval_walker(const DevModel &m,
     constexpr bool RD = sizeof(R) == 8;      // the pair loop runs in double
     R *lS = (R *)lds, *lC = lS + ROW, *lSU = lS + 2 * ROW,
       *lCU = lS + 3 * ROW, *lZ = lS + 4 * ROW;
-    const int n = m.n;
+    const int n = walker_n<G, P, PAD>(m);
     const int ge = lanes_in_use<G, PAD>(m);   // lanes the rotation runs over
     // one-case form with a shifted second copy of the tables (pair_core1)
     // (one particle per lane; in double only where the kernels keep the lanes

@@ -16,6 +16,8 @@
     KW template __global__ void vmc_step_kernel<G, P, PAD, ZC, true, R>(      \
         const DevModel *, VmcArgs);                                           \
     KW template __global__ void vmc_step_kernel<G, P, PAD, ZC, false, R>(     \
+        const DevModel *, VmcArgs);                                           \
+    KW template __global__ void vmc_step_kernel<G, P, PAD, ZC, true, R, true>(\
         const DevModel *, VmcArgs);
 #define QMC_INST_EVO_R(KW, G, P, PAD, ZC, R)                                  \
     KW template __global__ void dmc_evolve_kernel<G, P, PAD, ZC, R>(          \

@@ -174,6 +174,7 @@ evaluate_kernel(const DevModel *__restrict__ mp, EvalArgs a)
     const bool active = w < a.nconf;
     if (GPB == 1 && !active) return;      // (no one else in the workgroup)
     const long long wr = active ? w : 0;
+    const int n = walker_n<G, P, PAD>(m);
     double z[P], z1[P], F[P], ei[P], E, wf;
 #pragma unroll
     for (int p = 0; p < P; ++p) {
@@ -181,7 +182,7 @@ evaluate_kernel(const DevModel *__restrict__ mp, EvalArgs a)
         // (any position is accepted, as by the reference's functions: pair
         // tables from the image inside the box, one-body factor from the
         // position as given -- eval_walker)
-        z1[p] = (i < m.n) ? a.pos[wr * m.n + i] : 0.0;
+        z1[p] = (i < n) ? a.pos[wr * n + i] : 0.0;
         z[p] = wrap_box(z1[p], m.L);
     }
     eval_walker<G, P, PAD, true, true, ZC, R>(m, z, z1, gl, lds, F, ei, E, wf);
@@ -189,9 +190,9 @@ evaluate_kernel(const DevModel *__restrict__ mp, EvalArgs a)
 #pragma unroll
     for (int p = 0; p < P; ++p) {
         int i = lane_particle<G, P, PAD>(m, gl, p);
-        if (i < m.n) {
-            if (a.ith) a.ith[w * m.n + i] = ei[p];
-            if (a.drift) a.drift[w * m.n + i] = F[p];
+        if (i < n) {
+            if (a.ith) a.ith[w * n + i] = ei[p];
+            if (a.drift) a.drift[w * n + i] = F[p];
         }
     }
     if (gl == 0) {
@@ -225,11 +226,12 @@ prepare_kernel(const DevModel *__restrict__ mp, PrepArgs a)
     const bool active = w < a.nconf;
     if (GPB == 1 && !active) return;      // (no one else in the workgroup)
     const long long wr = active ? w : 0;
+    const int n = walker_n<G, P, PAD>(m);
     double z[P], z1[P], F[P], ei[P], E, wf;
 #pragma unroll
     for (int p = 0; p < P; ++p) {
         int i = lane_particle<G, P, PAD>(m, gl, p);
-        z1[p] = (i < m.n) ? a.pos[wr * m.n + i] : 0.0;
+        z1[p] = (i < n) ? a.pos[wr * n + i] : 0.0;
         z[p] = wrap_box(z1[p], m.L);
     }
     eval_walker<G, P, PAD, false, false, ZC, R>(m, z, z1, gl, lds, F, ei, E,
@@ -238,12 +240,34 @@ prepare_kernel(const DevModel *__restrict__ mp, PrepArgs a)
 #pragma unroll
     for (int p = 0; p < P; ++p) {
         int i = lane_particle<G, P, PAD>(m, gl, p);
-        if (i < m.n) a.drift[w * m.n + i] = F[p];
+        if (i < n) a.drift[w * n + i] = F[p];
     }
     if (gl == 0) a.energy[w] = E;
 }
 
 // ---- VMC: one launch = one generator yield of every chain ----------------
+// The scalars of one chain in one 64-byte record (three spare words): one
+// scalar load at the top of the step kernel instead of five, one vector store
+// of 64 bytes from lanes 0-7 at its end instead of five one-lane stores.  The
+// compact [W] arrays of the C ABI (qmc_vmc_get_state, _state_dev,
+// _block_sums_dev) are refreshed from the records after every run_block
+// (vmc_unpack_kernel) and packed into them by set_state (vmc_pack_kernel).
+struct alignas(64) VmcRec {
+    double wf;            // log|psi|
+    double ecarry;        // energy carried to rejected moves
+    double sum_e, sum_e2; // running block sums
+    long long n_acc;
+    long long spare[3];
+};
+static_assert(sizeof(VmcRec) == 64, "one record = 8 eight-byte words");
+// (a record as one wave-uniform load)
+typedef unsigned int VmcRecWords __attribute__((ext_vector_type(16)));
+#define QMC_CONST __attribute__((address_space(4)))
+__device__ __forceinline__ double vmc_rec_word(const VmcRecWords &r, int k)
+{
+    return __hiloint2double((int)r[2 * k + 1], (int)r[2 * k]);
+}
+
 // (a step loop inside the kernel lets LICM hoist ~40 polynomial constants and
 // the model constants across it, tripling the register count; with the loop on
 // the host the kernel has the register footprint of `evaluate_kernel` and the
@@ -251,10 +275,7 @@ prepare_kernel(const DevModel *__restrict__ mp, PrepArgs a)
 struct VmcArgs {
     double *pos;          // [W][N] in/out, lane (position) order
     unsigned short *label;// [W][N] in/out, original index of each lane's particle
-    double *wf;           // [W]    in/out  log|psi|
-    double *ecarry;       // [W]    in/out  energy carried to rejected moves
-    double *sum_e, *sum_e2;   // [W] running block sums
-    long long *n_acc;
+    VmcRec *rec;          // [W]    in/out  per-chain scalars
     double *ser_wf, *ser_e;   // [nyield][W] or null
     unsigned char *ser_stat;
     double *ser_pos;          // [nyield][W][N] or null
@@ -274,11 +295,16 @@ struct VmcArgs {
 
 // LEAN = the production path (Philox uniform proposal, per-chain block sums
 // only); the full variant adds the test-only tape replay, the Gaussian
-// proposal and the per-step series.
-template <int G, int P, bool PAD, bool ZC, bool LEAN, typename R = double>
+// proposal and the per-step series.  STEADY (LEAN only): a yield after the
+// first of a block -- `forced` and `reset_sums` are zero, and the forced-move
+// and initial-state paths are not compiled (qmc_vmc_run_block launches it for
+// every yield y >= 1).
+template <int G, int P, bool PAD, bool ZC, bool LEAN, typename R = double,
+          bool STEADY = false>
 __global__ void __launch_bounds__(WalkBlock<G>::N QMC_LB_WAVES_VMC)
 vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
 {
+    static_assert(LEAN || !STEADY, "the steady variant is a LEAN kernel");
     const DevModel &m = *mp;
     [[maybe_unused]] constexpr int QMC_SEC_OFF = 0;
     QMC_SECTION("top");
@@ -292,23 +318,35 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
     const bool active = w < a.W;
     if (GPB == 1 && !active) return;      // (no one else in the workgroup)
     const long long wr = active ? w : 0;
-    const int n = m.n;
+    const int n = walker_n<G, P, PAD>(m);
     const unsigned int slot = a.chain0 + (unsigned int)wr;
     // The very first yield of a generator is the initial state itself,
     // flagged ACCEPTED (qmc_base/vmc.py:616-618): a forced zero move.
-    const bool forced = a.forced != 0;
+    const bool forced = !STEADY && a.forced != 0;
+    const bool reset_sums = !STEADY && a.reset_sums != 0;
 
-    // The chain's scalars are needed only after the pair sum; their loads are
+    // The chain's scalars are needed only after the pair sum; their load is
     // issued here so that the memory latency runs under it.  One chain per
-    // wavefront: the index is wave-uniform and the loads are scalar (SGPR
-    // results, no vector registers held across the pair sum).
+    // wavefront: the index is wave-uniform and the whole record is one
+    // s_load_dwordx16 (SGPR results, no vector registers held across the pair
+    // sum) -- through the constant address space: through a generic pointer
+    // the loads were merged into vector loads.  The record is written once,
+    // at the end, by this wavefront.  The sums restart on the first yield of
+    // a block.
     const long long wl = (G == 64) ? qmc_uniform(wr) : wr;
-    double wf_cur = a.wf[wl];
-    double e_cur = a.ecarry[wl];
-    double se = 0.0, se2 = 0.0;
+    double wf_cur, e_cur, se = 0.0, se2 = 0.0;
     long long na = 0;
-    if (G == 64 && !a.reset_sums) {
-        se = a.sum_e[wl]; se2 = a.sum_e2[wl]; na = a.n_acc[wl];
+    if constexpr (G == 64) {
+        const VmcRecWords r = *(const QMC_CONST VmcRecWords *)(a.rec + wl);
+        wf_cur = vmc_rec_word(r, 0);
+        e_cur = vmc_rec_word(r, 1);
+        se = vmc_rec_word(r, 2);
+        se2 = vmc_rec_word(r, 3);
+        na = __double_as_longlong(vmc_rec_word(r, 4));
+        if (reset_sums) { se = 0.0; se2 = 0.0; na = 0; }
+    } else {
+        wf_cur = a.rec[wl].wf;
+        e_cur = a.rec[wl].ecarry;
     }
 
     QMC_SECTION("load+philox+wrap");
@@ -525,15 +563,29 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
             }
         }
     }
+    if (G == 64) {
+        // the record back in one 64-byte store: word gl from lane gl
+        const double sum1 = se + e_cur;
+        const double sum2 = fma(e_cur, e_cur, se2);
+        // (n_acc: a scalar, the word of lane 4 -- spare words zero)
+        const long long na1 = qmc_uniform(na + (acc ? 1 : 0));
+        double v = __longlong_as_double((gl == 4) ? na1 : 0ll);
+        v = (gl == 0) ? wf_cur : v;
+        v = (gl == 1) ? e_cur : v;
+        v = (gl == 2) ? sum1 : v;
+        v = (gl == 3) ? sum2 : v;
+        if (gl < 8) reinterpret_cast<double *>(a.rec + wl)[gl] = v;
+    }
     if (gl == 0) {
-        if (G != 64 && !a.reset_sums) {
-            se = a.sum_e[w]; se2 = a.sum_e2[w]; na = a.n_acc[w];
+        if (G != 64) {
+            VmcRec *r = a.rec + w;
+            if (!reset_sums) { se = r->sum_e; se2 = r->sum_e2; na = r->n_acc; }
+            r->wf = wf_cur;
+            r->ecarry = e_cur;
+            r->sum_e = se + e_cur;
+            r->sum_e2 = fma(e_cur, e_cur, se2);
+            r->n_acc = na + (acc ? 1 : 0);
         }
-        a.wf[w] = wf_cur;
-        a.ecarry[w] = e_cur;
-        a.sum_e[w] = se + e_cur;
-        a.sum_e2[w] = fma(e_cur, e_cur, se2);
-        a.n_acc[w] = na + (acc ? 1 : 0);
         if (!LEAN) {
             if (a.ser_wf) a.ser_wf[a.y * a.W + w] = wf_cur;
             if (a.ser_e) a.ser_e[a.y * a.W + w] = e_cur;
@@ -597,7 +649,7 @@ dmc_evolve_kernel(const DevModel *__restrict__ mp, EvolveArgs a)
     QMC_SECTION("top");
     const bool active = s < nw;
     const long long sr = active ? s : 0;
-    const int n = m.n;
+    const int n = walker_n<G, P, PAD>(m);
     const unsigned int step = a.ctl->step;
     const double ref_energy = a.ctl->ref_energy;
     // slots that existed at the previous (even) step have a stored normal

@@ -645,6 +645,34 @@ __global__ void unpack_walkers_kernel(WalkerRecArgs a, const double *buf)
     else a.dens_aux[dst * a.nb + (j - 3 * n - 2 - a.m3)] = v;
 }
 
+// The VMC chain records (VmcRec, qmc_kernels.h) and the compact [W] arrays
+// of the C ABI: the records into the arrays after a block (every field) ...
+__global__ void __launch_bounds__(BLOCK)
+vmc_unpack_kernel(const VmcRec *rec, long long W, double *wf, double *ecarry,
+                  double *sum_e, double *sum_e2, long long *n_acc)
+{
+    const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= W) return;
+    const VmcRec r = rec[w];
+    wf[w] = r.wf;
+    ecarry[w] = r.ecarry;
+    sum_e[w] = r.sum_e;
+    sum_e2[w] = r.sum_e2;
+    n_acc[w] = r.n_acc;
+}
+
+// ... and a new state (log|psi|, carried energy) into the records; the block
+// sums are not read before the first yield of a block resets them.
+__global__ void __launch_bounds__(BLOCK)
+vmc_pack_kernel(VmcRec *rec, long long W, const double *wf,
+                const double *ecarry)
+{
+    const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= W) return;
+    rec[w].wf = wf[w];
+    rec[w].ecarry = ecarry[w];
+}
+
 // Population size after a rebalance (stream-ordered, no host round trip).
 // Slots at or beyond `spare_cap` lose their cached Box-Muller normal: an
 // imported walker must not consume the normal another walker stored there

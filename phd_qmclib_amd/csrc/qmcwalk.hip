@@ -245,6 +245,26 @@ struct LaunchPrep {
 template <int G, int P, bool PAD, bool ZC>
 struct LaunchVmc {
     static constexpr bool want_mask(int np) { return np >= 4; }
+    template <typename R, bool LEAN, bool STEADY>
+    static void launch(const qmc_engine *e, const VmcArgs &a, size_t lds)
+    {
+        allow_lds(vmc_step_kernel<G, P, PAD, ZC, LEAN, R, STEADY>, lds);
+        hipLaunchKernelGGL((vmc_step_kernel<G, P, PAD, ZC, LEAN, R, STEADY>),
+                           dim3(grid_for<G>(a.W)), dim3(WalkBlock<G>::N), lds,
+                           e->stream, e->dm_dev, a);
+    }
+    template <typename R>
+    static void launch(const qmc_engine *e, const VmcArgs &a, size_t lds,
+                       bool lean)
+    {
+        // (the steady variant: every yield of a block after its first)
+        if (lean && !a.forced && !a.reset_sums)
+            launch<R, true, true>(e, a, lds);
+        else if (lean)
+            launch<R, true, false>(e, a, lds);
+        else
+            launch<R, false, false>(e, a, lds);
+    }
     static int run(const qmc_engine *e, const VmcArgs &a)
     {
         const size_t lds = step_lds_bytes<G, P, PAD, ZC>();
@@ -253,35 +273,12 @@ struct LaunchVmc {
         ProfScope prof(e);
         if constexpr (has_fast<G, ZC>()) {
             if (e->fast) {
-                if (lean) {
-                    allow_lds(vmc_step_kernel<G, P, PAD, ZC, true, float>, lds);
-                    hipLaunchKernelGGL(
-                        (vmc_step_kernel<G, P, PAD, ZC, true, float>),
-                        dim3(grid_for<G>(a.W)), dim3(WalkBlock<G>::N), lds, e->stream,
-                        e->dm_dev, a);
-                } else {
-                    allow_lds(vmc_step_kernel<G, P, PAD, ZC, false, float>,
-                              lds);
-                    hipLaunchKernelGGL(
-                        (vmc_step_kernel<G, P, PAD, ZC, false, float>),
-                        dim3(grid_for<G>(a.W)), dim3(WalkBlock<G>::N), lds, e->stream,
-                        e->dm_dev, a);
-                }
+                launch<float>(e, a, lds, lean);
                 HIP_TRY(hipGetLastError());
                 return 0;
             }
         }
-        if (lean) {
-            allow_lds(vmc_step_kernel<G, P, PAD, ZC, true>, lds);
-            hipLaunchKernelGGL((vmc_step_kernel<G, P, PAD, ZC, true>),
-                               dim3(grid_for<G>(a.W)), dim3(WalkBlock<G>::N), lds,
-                               e->stream, e->dm_dev, a);
-        } else {
-            allow_lds(vmc_step_kernel<G, P, PAD, ZC, false>, lds);
-            hipLaunchKernelGGL((vmc_step_kernel<G, P, PAD, ZC, false>),
-                               dim3(grid_for<G>(a.W)), dim3(WalkBlock<G>::N), lds,
-                               e->stream, e->dm_dev, a);
-        }
+        launch<double>(e, a, lds, lean);
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -1110,6 +1107,10 @@ struct qmc_vmc {
     unsigned short *label = nullptr;
     double *sum_e = nullptr, *sum_e2 = nullptr;
     long long *n_acc = nullptr;
+    // the per-chain scalars the step kernel reads and writes; wf, ecarry,
+    // sum_e, sum_e2 and n_acc above are their copies for the C ABI, refreshed
+    // at the end of every run_block
+    VmcRec *rec = nullptr;
     double *tape = nullptr;
     long long tape_steps = 0, tape_used = 0;
     unsigned int step = 0;
@@ -1131,7 +1132,8 @@ extern "C" int qmc_vmc_create(qmc_engine *e, const qmc_vmc_params *p,
     const size_t W = (size_t)v->W, n = (size_t)e->dm.n;
     if (dev_alloc(&v->pos, W * n) || dev_alloc(&v->label, W * n) ||
         dev_alloc(&v->wf, W) || dev_alloc(&v->ecarry, W) || dev_alloc(&v->sum_e, W) ||
-        dev_alloc(&v->sum_e2, W) || dev_alloc(&v->n_acc, W)) {
+        dev_alloc(&v->sum_e2, W) || dev_alloc(&v->n_acc, W) ||
+        dev_alloc(&v->rec, W)) {
         delete v;
         return 1;
     }
@@ -1146,7 +1148,7 @@ extern "C" void qmc_vmc_destroy(qmc_vmc *v)
     hipFree(v->pos); hipFree(v->label); hipFree(v->wf); hipFree(v->ecarry);
     if (v->ssf_partial) hipFree(v->ssf_partial);
     if (v->ssf_out) hipFree(v->ssf_out);
-    hipFree(v->sum_e); hipFree(v->sum_e2); hipFree(v->n_acc);
+    hipFree(v->sum_e); hipFree(v->sum_e2); hipFree(v->n_acc); hipFree(v->rec);
     if (v->tape) hipFree(v->tape);
     delete v;
 }
@@ -1168,6 +1170,10 @@ extern "C" int qmc_vmc_set_state(qmc_vmc *v, const double *pos)
     int rc = qmc_evaluate_dev(e, v->W, v->pos, v->wf, nullptr, nullptr,
                               nullptr);
     if (rc) return rc;
+    hipLaunchKernelGGL(vmc_pack_kernel, dim3((unsigned)((W + BLOCK - 1) / BLOCK)),
+                       dim3(BLOCK), 0, e->stream, v->rec, v->W, v->wf,
+                       v->ecarry);
+    HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(e->stream));
     v->step = 0;
     v->yield_initial = 1;
@@ -1315,8 +1321,7 @@ extern "C" int qmc_vmc_run_block(qmc_vmc *v, int64_t nyield, double *sum_e,
         return 1;
     }
     VmcArgs a;
-    a.pos = v->pos; a.label = v->label; a.wf = v->wf; a.ecarry = v->ecarry;
-    a.sum_e = v->sum_e; a.sum_e2 = v->sum_e2; a.n_acc = v->n_acc;
+    a.pos = v->pos; a.label = v->label; a.rec = v->rec;
     a.ser_wf = dwf; a.ser_e = de; a.ser_stat = dst; a.ser_pos = dpos;
     a.tape = v->tape;
     a.tape_steps = v->tape_steps;
@@ -1335,6 +1340,12 @@ extern "C" int qmc_vmc_run_block(qmc_vmc *v, int64_t nyield, double *sum_e,
         if (!a.forced) { v->step += 1; v->tape_used += 1; }
     }
     v->yield_initial = 0;
+    // the records into the compact arrays of the C ABI (on the engine stream,
+    // ahead of the copies below and of any later reader)
+    hipLaunchKernelGGL(vmc_unpack_kernel, dim3((unsigned)((W + BLOCK - 1) / BLOCK)),
+                       dim3(BLOCK), 0, e->stream, v->rec, v->W, v->wf, v->ecarry,
+                       v->sum_e, v->sum_e2, v->n_acc);
+    HIP_TRY(hipGetLastError());
     bool need_sync = false;
     if (sum_e) { HIP_TRY(hipMemcpyAsync(sum_e, v->sum_e, W * sizeof(double),
                  hipMemcpyDeviceToHost, e->stream)); need_sync = true; }
