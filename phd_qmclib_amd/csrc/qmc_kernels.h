@@ -81,6 +81,56 @@ __device__ __forceinline__ long long qmc_uniform(long long v)
     const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
     return ((long long)hi << 32) | (unsigned int)lo;
 }
+// a value the compiler cannot see through (nothing computed from it is
+// loop-invariant)
+__device__ __forceinline__ int qmc_opaque(int v)
+{
+    asm volatile("" : "+v"(v));
+    return v;
+}
+// lane 0's / lane k's double, as a scalar
+__device__ __forceinline__ double qmc_uniform_f64(double v)
+{
+    return __longlong_as_double(qmc_uniform(__double_as_longlong(v)));
+}
+__device__ __forceinline__ double qmc_lane_f64(double v, int k)
+{
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_readlane((int)b, k);
+    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), k);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
+// The fused VMC yields (vmc_step_kernel, VmcFused): where particles 0 and 1
+// sit -- lane | slot << 6 -- so that the accept words are two readlanes.  The
+// labels move only with an accepted move; one ballot each, then.  (n = 1:
+// particle 0 gives both words, as in vmc_step_kernel.)
+template <int P>
+__device__ __forceinline__ void vmc_accept_lanes(const int (&lab)[P], int n,
+                                                 int &src0, int &src1)
+{
+    src0 = 0;
+    src1 = 0;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        const unsigned long long b0 = __ballot(lab[p] == 0);
+        const unsigned long long b1 = __ballot(lab[p] == 1);
+        if (b0) src0 = ((int)__ffsll((long long)b0) - 1) | (p << 6);
+        if (b1) src1 = ((int)__ffsll((long long)b1) - 1) | (p << 6);
+    }
+    if (n == 1) src1 = src0;
+}
+template <int P>
+__device__ __forceinline__ unsigned int vmc_read_slot(const uint32_t (&wd)[P],
+                                                      int src)
+{
+    unsigned int r = 0u;
+#pragma unroll
+    for (int p = 0; p < P; ++p)
+        if ((src >> 6) == p)
+            r = (unsigned)__builtin_amdgcn_readlane((int)wd[p], src & 63);
+    return r;
+}
 
 // Minimum waves per SIMD asked of the register allocator for the N <= 64
 // shape.  Round 2 held it to 64 registers (8 waves, one spilled double: +1.5 %
@@ -110,6 +160,9 @@ __device__ __forceinline__ long long qmc_uniform(long long v)
 #ifndef QMC_LB_VMC_P2
 #define QMC_LB_VMC_P2 4
 #endif
+// (Round 6: the fused steady kernel of the N <= 64 shape takes 67 registers --
+// 7 waves, no scratch; held to 8 waves it spills 12 bytes per lane, and the
+// two measure the same, profiles/r06_ab_variants.txt.)
 #define QMC_LB_WAVES_VMC , ((G == 64 && P == 1) ? QMC_LB_P1 \
                             : (G == 64 && P == 2 && !ZC) ? QMC_LB_VMC_P2 : 1)
 
@@ -268,10 +321,10 @@ __device__ __forceinline__ double vmc_rec_word(const VmcRecWords &r, int k)
     return __hiloint2double((int)r[2 * k + 1], (int)r[2 * k]);
 }
 
-// (a step loop inside the kernel lets LICM hoist ~40 polynomial constants and
-// the model constants across it, tripling the register count; with the loop on
-// the host the kernel has the register footprint of `evaluate_kernel` and the
-// state round trip is ~1 KB per chain-step, far below the HBM roofline.)
+// (Rounds 2-3: a step loop inside the kernel let LICM hoist ~40 polynomial
+// constants and the model constants across it, tripling the register count.
+// Round 6 loops over the steady yields of a block again -- VmcFused below --
+// at 67 registers on the sorted-row N <= 64 shape.)
 struct VmcArgs {
     double *pos;          // [W][N] in/out, lane (position) order
     unsigned short *label;// [W][N] in/out, original index of each lane's particle
@@ -284,6 +337,7 @@ struct VmcArgs {
     long long tape_idx;   // real step index into the tape for this yield
     long long W;
     long long y;          // yield index inside the block (series row)
+    unsigned int nsteps;  // yields of one launch of the fused STEADY kernel
     int forced;           // this yield is the initial state (ACCEPTED)
     int reset_sums;       // first yield of a block: sums start from zero
     int gaussian;
@@ -293,12 +347,35 @@ struct VmcArgs {
     double move_spread;
 };
 
+// Several steady yields in one launch (VmcFused): the STEADY kernel of the
+// sorted-row N <= 64 shape runs `a.nsteps` consecutive yields of a block for its
+// chain.  The walker mapping, the record, the row and its labels are loaded
+// once; the row stays in registers (a rejected move keeps it there), the
+// chain's scalars in scalar registers, and the row, its labels and the record
+// are stored once, at the end.  Every yield draws from the same Philox counters
+// and runs the same arithmetic in the same order as a launch of its own: the
+// results are bit-identical.  The loop costs registers (values derived from
+// the lane index are hoisted out of it, qmc_opaque keeps most of them in):
+// N <= 64 takes 67 -- 7 waves instead of 8, no scratch -- and the 66 <= N <= 128
+// shape 115 (4 waves, as its per-yield kernel).  Measured against the per-yield
+// launches, profiles/r06_ab_variants.txt: -9.5 % per step at N = 64, -8.8 % at
+// N = 48, -8.5 % at N = 128.
+#ifndef QMC_VMC_FUSED
+#define QMC_VMC_FUSED 1
+#endif
+template <int G, int P, bool ZC>
+struct VmcFused {
+    static constexpr bool ON =
+        QMC_VMC_FUSED && G == 64 && !ZC &&
+        ((P == 1 && QMC_SORTED64) || (P == 2 && QMC_SORTED128));
+};
+
 // LEAN = the production path (Philox uniform proposal, per-chain block sums
 // only); the full variant adds the test-only tape replay, the Gaussian
 // proposal and the per-step series.  STEADY (LEAN only): a yield after the
 // first of a block -- `forced` and `reset_sums` are zero, and the forced-move
 // and initial-state paths are not compiled (qmc_vmc_run_block launches it for
-// every yield y >= 1).
+// every yield y >= 1; on VmcFused shapes once, for all of them).
 template <int G, int P, bool PAD, bool ZC, bool LEAN, typename R = double,
           bool STEADY = false>
 __global__ void __launch_bounds__(WalkBlock<G>::N QMC_LB_WAVES_VMC)
@@ -349,6 +426,32 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
         e_cur = a.rec[wl].ecarry;
     }
 
+    // fused yields: the row and its labels in registers for the whole launch
+    constexpr bool FUSED = STEADY && VmcFused<G, P, ZC>::ON;
+    double zc[P];
+    int labc[P];
+    int src0 = 0, src1 = 0;   // lanes of particles 0 and 1 (FUSED)
+    if constexpr (FUSED) {
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            int i = lane_particle<G, P, PAD>(m, gl, p);
+            zc[p] = (i < n) ? a.pos[wr * n + i] : 0.0;
+            labc[p] = (i < n) ? (int)a.label[wr * n + i] : i;
+        }
+        vmc_accept_lanes<P>(labc, n, src0, src1);
+    }
+    bool any_acc = false;     // FUSED: some yield of the launch accepted
+    const unsigned int nst = FUSED ? a.nsteps : 1u;
+    bool acc = false;
+    // ---- one yield per trip (one trip unless FUSED; the body keeps the
+    // indentation of the per-yield kernel) ----
+    [[maybe_unused]] const int gl_top = gl;
+    for (unsigned int s = 0; s < nst; ++s) {
+    const unsigned int step = a.step + s;
+    // (FUSED: what the sort and the pair sums derive from the lane index is
+    // derived again on every trip instead of being hoisted out of the loop and
+    // held in registers across it)
+    const int gl = FUSED ? qmc_opaque(gl_top) : gl_top;
     QMC_SECTION("load+philox+wrap");
     double zn[P];
     int labn[P];              // original particle index held by each lane
@@ -358,11 +461,19 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
     unsigned int aw0 = 0u, aw1 = 0u;
     bool has0 = false, has1 = false;
     bool outside = false;     // forced yield: a particle given outside [0, L)
+    [[maybe_unused]] uint32_t wacc[P];   // FUSED: every slot's second word
 #pragma unroll
     for (int p = 0; p < P; ++p) {
+        wacc[p] = 0u;
         int i = lane_particle<G, P, PAD>(m, gl, p);
-        const double zp = (i < n) ? a.pos[wr * n + i] : 0.0;
-        labn[p] = (i < n) ? (int)a.label[wr * n + i] : i;
+        double zp;
+        if constexpr (FUSED) {
+            zp = zc[p];
+            labn[p] = labc[p];
+        } else {
+            zp = (i < n) ? a.pos[wr * n + i] : 0.0;
+            labn[p] = (i < n) ? (int)a.label[wr * n + i] : i;
+        }
         const unsigned li = (unsigned)labn[p];
         double d = 0.0;
         if (!forced && i < n) {
@@ -372,15 +483,19 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
                                : (tv - 0.5) * a.move_spread;
             } else if (!LEAN && a.gaussian) {
                 double g0, g1;
-                philox_normal2(a.seed, slot, a.step, li, STREAM_VMC_MOVE, g0,
+                philox_normal2(a.seed, slot, step, li, STREAM_VMC_MOVE, g0,
                                g1);
                 d = a.move_spread * g0;
             } else {
                 uint32_t w0, w1;
-                vmc_move_block(a.seed, slot, a.step, li, w0, w1);
+                vmc_move_block(a.seed, slot, step, li, w0, w1);
                 d = vmc_move_unit(w0) * a.move_spread;
-                if (li == 0u) { aw0 = w1; has0 = true; }
-                if (li == 1u || n == 1) { aw1 = w1; has1 = true; }
+                if constexpr (FUSED) {
+                    wacc[p] = w1;
+                } else {
+                    if (li == 0u) { aw0 = w1; has0 = true; }
+                    if (li == 1u || n == 1) { aw1 = w1; has1 = true; }
+                }
             }
         }
         // mrbp_qmc/vmc.py:215-233 (recast to the supercell).  The forced
@@ -391,6 +506,12 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
         // it until the first accepted move.
         zn[p] = wrap_box(zp + d, m.L);
         if (forced) outside = outside || zn[p] != zp;
+    }
+    if constexpr (FUSED) {
+        // the accept words straight from the lanes that hold particles 0 and
+        // 1 (known since the last accepted move: no ballots)
+        aw0 = vmc_read_slot<P>(wacc, src0);
+        aw1 = vmc_read_slot<P>(wacc, src1);
     }
     QMC_SECTION("resort");
     // (one odd-even pass every QMC_RESORT_EVERY steps keeps the lanes sorted
@@ -467,12 +588,14 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
                                                        ei, e_new, wf_new);
     }
     QMC_SECTION("metropolis+store");
-    if (!forced) {
+    if (FUSED) {
+        ua = u53(aw0, aw1);
+    } else if (!forced) {
         if (!LEAN && a.tape) {
             ua = a.tape[(wr * a.tape_steps + a.tape_idx) * (n + 1) + n];
         } else if (!LEAN && a.gaussian) {
             double u1;
-            philox_uniform2(a.seed, slot, a.step, 0u, STREAM_VMC_ACCEPT, ua,
+            philox_uniform2(a.seed, slot, step, 0u, STREAM_VMC_ACCEPT, ua,
                             u1);
         } else {
             // exactly one lane of the group holds particle 0 and one particle 1:
@@ -504,10 +627,19 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
     // Metropolis test (qmc_base/vmc.py:636)
     // log(u) <= 0: an uphill move needs no logarithm (wave-uniform when one
     // wavefront owns one chain)
-    bool acc = forced || ua <= 0.0 || wf_new > wf_cur;
-    if (!acc) acc = wf_new > 0.5 * log_pos(ua) + wf_cur;
-    // (one chain per wavefront: every lane holds the same decision)
-    if (G == 64) acc = __builtin_amdgcn_readfirstlane((int)acc) != 0;
+    if constexpr (FUSED) {
+        // lane 0's log|psi| -- the lane whose decision the per-yield kernel
+        // takes -- as a scalar: the test and its branch are scalar
+        const double w0 = qmc_uniform_f64(wf_new);
+        acc = ua <= 0.0 || w0 > wf_cur;
+        if (!acc) acc = w0 > 0.5 * log_pos(ua) + wf_cur;
+        acc = __builtin_amdgcn_readfirstlane((int)acc) != 0;
+    } else {
+        acc = forced || ua <= 0.0 || wf_new > wf_cur;
+        if (!acc) acc = wf_new > 0.5 * log_pos(ua) + wf_cur;
+        // (one chain per wavefront: every lane holds the same decision)
+        if (G == 64) acc = __builtin_amdgcn_readfirstlane((int)acc) != 0;
+    }
     if (acc) {
         if constexpr (TWO_PASS) {
             QMC_SECTION("energy_pass");
@@ -534,20 +666,55 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
             QMC_SECTION_PHASE(0);
             QMC_SECTION("store");
         }
+        if constexpr (FUSED) {
 #pragma unroll
-        for (int p = 0; p < P; ++p) {
-            int i = lane_particle<G, P, PAD>(m, gl, p);
-            if (i < n && !forced) {
-                a.pos[w * n + i] = zn[p];
-                a.label[w * n + i] = (unsigned short)labn[p];
+            for (int p = 0; p < P; ++p) {
+                zc[p] = zn[p];
+                labc[p] = labn[p];
+            }
+            vmc_accept_lanes<P>(labc, n, src0, src1);
+            any_acc = true;
+        } else {
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                int i = lane_particle<G, P, PAD>(m, gl, p);
+                if (i < n && !forced) {
+                    a.pos[w * n + i] = zn[p];
+                    a.label[w * n + i] = (unsigned short)labn[p];
+                }
             }
         }
         // (the initial yield too: log|psi| of the initial state then comes
         // from the same pair sum as every later one -- the sorted-row path on
         // its shapes -- instead of qmc_vmc_set_state's batch evaluation)
-        wf_cur = wf_new;
-        e_cur = e_new;       // energy only re-evaluated on accepted moves
-    }                        // (qmc_base/jastrow/vmc.py:253-262)
+        if (!FUSED) {
+            wf_cur = wf_new;
+            e_cur = e_new;   // energy only re-evaluated on accepted moves
+        }                    // (qmc_base/jastrow/vmc.py:253-262)
+    }
+    if constexpr (FUSED) {
+        // The per-yield kernel writes the record from lanes 0-3: log|psi| of
+        // lane 0, the carried energy of lane 1 and each sum with the energy of
+        // its own lane (wave sums need not agree to the last bit across
+        // lanes).  The same lanes here, then the scalars carry on.
+        if (acc) {
+            wf_cur = qmc_uniform_f64(wf_new);
+            const double e2 = qmc_lane_f64(e_new, 2);
+            const double e3 = qmc_lane_f64(e_new, 3);
+            e_cur = qmc_lane_f64(e_new, 1);
+            se = se + e2;
+            se2 = fma(e3, e3, se2);
+            na = na + 1;
+        } else {
+            se = se + e_cur;
+            se2 = fma(e_cur, e_cur, se2);
+        }
+        // (back into scalar registers: the compiler carries a double that a
+        // vector instruction wrote in vector registers)
+        se = qmc_uniform_f64(se);
+        se2 = qmc_uniform_f64(se2);
+        continue;
+    }
     if (!LEAN && a.ser_pos) {
 #pragma unroll
         for (int p = 0; p < P; ++p) {
@@ -591,6 +758,27 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
             if (a.ser_e) a.ser_e[a.y * a.W + w] = e_cur;
             if (a.ser_stat) a.ser_stat[a.y * a.W + w] = acc ? 1 : 0;
         }
+    }
+    }                        // (the yield loop: one trip unless FUSED)
+    if constexpr (FUSED) {
+        QMC_SECTION("fused_store");
+        if (any_acc) {
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                int i = lane_particle<G, P, PAD>(m, gl, p);
+                if (i < n) {
+                    a.pos[w * n + i] = zc[p];
+                    a.label[w * n + i] = (unsigned short)labc[p];
+                }
+            }
+        }
+        // (every value is a scalar now: the sums are complete)
+        double v = __longlong_as_double((gl == 4) ? qmc_uniform(na) : 0ll);
+        v = (gl == 0) ? wf_cur : v;
+        v = (gl == 1) ? e_cur : v;
+        v = (gl == 2) ? se : v;
+        v = (gl == 3) ? se2 : v;
+        if (gl < 8) reinterpret_cast<double *>(a.rec + wl)[gl] = v;
     }
     QMC_SECTION("end");
 }

@@ -255,30 +255,34 @@ struct LaunchVmc {
     }
     template <typename R>
     static void launch(const qmc_engine *e, const VmcArgs &a, size_t lds,
-                       bool lean)
+                       bool lean, bool steady)
     {
         // (the steady variant: every yield of a block after its first)
-        if (lean && !a.forced && !a.reset_sums)
+        if (steady)
             launch<R, true, true>(e, a, lds);
         else if (lean)
             launch<R, true, false>(e, a, lds);
         else
             launch<R, false, false>(e, a, lds);
     }
-    static int run(const qmc_engine *e, const VmcArgs &a)
+    // One launch from yield a.y on; *ran = the yields it ran: 1, or on a
+    // VmcFused shape all a.nsteps steady yields left in the block.
+    static int run(const qmc_engine *e, const VmcArgs &a, long long *ran)
     {
         const size_t lds = step_lds_bytes<G, P, PAD, ZC>();
         const bool lean = !a.tape && !a.gaussian && !a.ser_wf && !a.ser_e &&
                           !a.ser_stat && !a.ser_pos;
+        const bool steady = lean && !a.forced && !a.reset_sums;
+        *ran = (steady && VmcFused<G, P, ZC>::ON) ? (long long)a.nsteps : 1;
         ProfScope prof(e);
         if constexpr (has_fast<G, ZC>()) {
             if (e->fast) {
-                launch<float>(e, a, lds, lean);
+                launch<float>(e, a, lds, lean, steady);
                 HIP_TRY(hipGetLastError());
                 return 0;
             }
         }
-        launch<double>(e, a, lds, lean);
+        launch<double>(e, a, lds, lean, steady);
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -1329,15 +1333,18 @@ extern "C" int qmc_vmc_run_block(qmc_vmc *v, int64_t nyield, double *sum_e,
     a.gaussian = v->p.gaussian;
     a.chain0 = v->p.chain0;
     a.seed = v->p.rng_seed; a.move_spread = v->p.move_spread;
-    for (long long y = 0; y < nyield; ++y) {
+    for (long long y = 0; y < nyield;) {
         a.y = y;
         a.forced = (y == 0 && v->yield_initial) ? 1 : 0;
         a.reset_sums = (y == 0) ? 1 : 0;
         a.step = v->step;
         a.tape_idx = v->tape_used;
-        int rc = dispatch_shape<LaunchVmc>(e, a);
+        a.nsteps = (unsigned int)(nyield - y);
+        long long ran = 1;
+        int rc = dispatch_shape<LaunchVmc>(e, a, &ran);
         if (rc) return rc;
-        if (!a.forced) { v->step += 1; v->tape_used += 1; }
+        if (!a.forced) { v->step += ran; v->tape_used += ran; }
+        y += ran;
     }
     v->yield_initial = 0;
     // the records into the compact arrays of the C ABI (on the engine stream,

@@ -1,6 +1,6 @@
 """Quick A/B timing of the VMC and DMC step kernels (development tool).
 usage: ab_bench.py [--bosons N] [--walkers W] [--steps K] [--equil E]
-Prints ms per launch (HIP events around every launch) for the library /
+Prints VMC ms per step (HIP events around every launch) for the library /
 environment it runs under (QMCWALK_LIB, QMCWALK_SHAPE, QMCWALK_OB_TABLE)."""
 import argparse
 import os
@@ -52,8 +52,10 @@ nl, tot, mn, mx = eng.profile_end()
 res = v.run_block(16)
 e = res['sum_energy'].sum() / (16 * a.walkers * n)
 acc = res['num_accepted'].sum() / (16 * a.walkers)
-print(f'{a.tag:24s} VMC N={n} W={a.walkers}: {tot / nl:.4f} ms/launch '
-      f'(min {mn:.4f} max {mx:.4f}) = {a.walkers / (tot / nl) / 1e3:.4g} steps/s'
+# (per step: a launch of the fused steady kernel runs several steps)
+print(f'{a.tag:24s} VMC N={n} W={a.walkers}: {tot / a.steps:.4f} ms/step '
+      f'({nl} launches, min {mn:.4f} max {mx:.4f} ms) = '
+      f'{a.walkers / (tot / a.steps) / 1e3:.4g} steps/s'
       f'  E/N={e:.5f} acc={acc:.4f}', flush=True)
 if a.no_dmc:
     sys.exit(0)

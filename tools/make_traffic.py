@@ -1,9 +1,13 @@
 """profiles/traffic.json from the PMC summaries of tools/profile.sh
-(development tool).  usage: make_traffic.py key,summary.txt,kernel-substring,unit[,scale] ...
+(development tool).
+usage: make_traffic.py key,summary.txt,kernel-substring,unit[,scale[,steps]] ...
 Per unit (chain-step / walker-step): HBM bytes = (2 x FETCH_SIZE + WRITE_SIZE)
 x 1024 / SQ_WAVES x waves-per-unit -- FETCH_SIZE counts half of a coalesced
 read on gfx950 (MI355X_MICROARCH.md, HBM section) -- and VALU / SALU
 instructions per unit = SQ_INSTS_* / SQ_WAVES (one wavefront per walker).
+`steps`: steps one wavefront of the kernel runs (default 1).  The fused steady
+VMC kernel runs every yield of a block after the first in one launch: with
+tools/prof_workload.py --steps K, K - 1 of them.
 
 Every entry records WHICH kernels were measured: `kernel_source_sha` is the
 `qmc_source_hash()` of the library the counter passes ran (tools/profile.sh
@@ -43,7 +47,7 @@ def main(argv):
         head = ''
     res = {'source': 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE / SQ_INSTS_* in '
                      'separate passes (tools/profile.sh), profiles/'
-                     'r04_*_pmc_summary.txt',
+                     'r06_*_pmc_summary.txt',
            'correction': 'read bytes = 2 x FETCH_SIZE x 1024 (gfx950 half-count '
                          'of coalesced reads), write bytes = WRITE_SIZE x 1024',
            'head': head}
@@ -53,10 +57,12 @@ def main(argv):
         # waves launched per unit of work (DMC launches max_num_walkers waves,
         # the ones beyond the population exit at once)
         scale = float(parts[4]) if len(parts) > 4 else 1.0
+        steps = float(parts[5]) if len(parts) > 5 else 1.0
         kernels, sha = parse(path)
         for name, c in kernels.items():
             if kern in name and 'SQ_WAVES' in c:
-                w = c['SQ_WAVES'] / scale
+                # (units of work: waves x steps per wave / waves per unit)
+                w = c['SQ_WAVES'] * steps / scale
                 ent = res.setdefault(key, {})
                 short = 'vmc_step_kernel' if 'vmc' in kern else 'dmc_evolve_kernel'
                 ent[f'{short}_bytes_per_{unit}'] = \
