@@ -359,12 +359,9 @@ __device__ __forceinline__ double wrap_box(double z, double L)
 // over those: N = 100 on the (64, 2) shape runs 25 rotation steps over 50 lanes
 // instead of 32 over 64 (round 1 paid the full shape: 4.7e11 pair evaluations/s
 // at N = 100 against 8.0e11 at N = 128).
-#ifndef QMC_INTERLEAVE
-#define QMC_INTERLEAVE 1
-#endif
 template <int G, int P>
 struct SlotMap {
-    static constexpr bool CONSECUTIVE = QMC_INTERLEAVE && (G == 64) && (P >= 2);
+    static constexpr bool CONSECUTIVE = (G == 64) && (P >= 2);
 };
 
 template <int G, bool PAD>
@@ -418,71 +415,26 @@ __device__ __forceinline__ double group_sum(double v)
     return v;
 }
 
-// The same over a whole wavefront on the matrix cores: a v_mfma_f64_16x16x4
-// contracts over k = lane >> 4, so A = the lanes' values against B = ones
-// leaves r_i = the sum of the four lanes with lane & 15 = i in row i; a lane
-// holds rows (lane >> 4) + 4 reg, adds its four and feeds the partial back as
-// A: every element of the second product is the total.  Two sums share the
-// second product (rows 0-7 carry one, rows 8-15 the other).  Against the
-// butterfly (12 ds_bpermute + 6 adds per sum, the LDS pipe being the kernel's
-// second-busiest resource) this is 3 vector adds and no LDS traffic.
-#ifndef QMC_MFMA_SUM
-#define QMC_MFMA_SUM 1
-#endif
-typedef double qmc_v4d __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double wave_partial_mfma(double v)
-{
-    const qmc_v4d zero = {0.0, 0.0, 0.0, 0.0};
-    const qmc_v4d d = __builtin_amdgcn_mfma_f64_16x16x4f64(v, 1.0, zero, 0, 0, 0);
-    return (d[0] + d[1]) + (d[2] + d[3]);
-}
-
-// One sum over the wavefront through the 4x4x4 form (four independent 4x4
-// blocks; 16 cycles an instruction against 64 for 16x16x4, profiles/
-// r02_ubench3_mfma_overlap.txt).  Lane layout, probed on the chip
+// The same over a whole wavefront on the matrix cores: against the butterfly
+// (12 ds_bpermute + 6 adds per sum, the LDS pipe being the kernel's
+// second-busiest resource) two matrix products, two DPP rotations and no LDS
+// traffic.  The 4x4x4 form (four independent 4x4 blocks; 16 cycles an
+// instruction against 64 for 16x16x4, profiles/r02_ubench3_mfma_overlap.txt):
+// round 2's two v_mfma_f64_16x16x4 per sum were measured against it
+// (profiles/r03_ab_variants.txt) and removed.  Lane layout, probed on the chip
 // (tools/mfma4_layout.hip): block b = (lane / 4) % 4; A[i][k] sits in lane
 // i + 4 b + 16 k and D[i][j] in lane j + 4 b + 16 i.  Against B = ones the first
 // product leaves, in row i of the wavefront, the sum over the four rows of
 // the lanes i + 4 b; fed back as A the second leaves the total of the block's
 // 16 lanes {i + 4 b + 16 k} in all of them; two rotations inside the rows of
 // 16 (by 4 and by 8 lanes: DPP, no LDS) add the four blocks.
-#ifndef QMC_MFMA4_SUM
-#define QMC_MFMA4_SUM 1
-#endif
-template <int N> __device__ __forceinline__ double row_ror_f64(double v);
-__device__ __forceinline__ double wave_sum_mfma4(double v)
+__device__ __forceinline__ double wave_sum_mfma(double v)
 {
     const double r = __builtin_amdgcn_mfma_f64_4x4x4f64(v, 1.0, 0.0, 0, 0, 0);
     double t = __builtin_amdgcn_mfma_f64_4x4x4f64(r, 1.0, 0.0, 0, 0, 0);
     t += row_ror_f64<4>(t);
     t += row_ror_f64<8>(t);
     return t;
-}
-
-__device__ __forceinline__ double wave_sum_mfma(double v)
-{
-    if (QMC_MFMA4_SUM) return wave_sum_mfma4(v);
-    const qmc_v4d zero = {0.0, 0.0, 0.0, 0.0};
-    const qmc_v4d t = __builtin_amdgcn_mfma_f64_16x16x4f64(
-        wave_partial_mfma(v), 1.0, zero, 0, 0, 0);
-    return t[0];
-}
-
-__device__ __forceinline__ void wave_sum2_mfma(double a, double b, double &sa,
-                                               double &sb)
-{
-    if (QMC_MFMA4_SUM) {
-        sa = wave_sum_mfma4(a);
-        sb = wave_sum_mfma4(b);
-        return;
-    }
-    const qmc_v4d zero = {0.0, 0.0, 0.0, 0.0};
-    const double pa = wave_partial_mfma(a), pb = wave_partial_mfma(b);
-    const qmc_v4d t = __builtin_amdgcn_mfma_f64_16x16x4f64(
-        (threadIdx.x & 8) ? pb : pa, 1.0, zero, 0, 0, 0);
-    sa = t[0];          // rows 0-3
-    sb = t[2];          // rows 8-11
 }
 
 // Lane order = position order.  Bosons are identical, so which lane holds which
@@ -566,9 +518,6 @@ __device__ __forceinline__ void resort_linear(double &z, int &lab, int gl,
 // (Adding the partner's share into an LDS row with ds_add_f64 instead -- no
 // travelling sum at all, 3 vector instructions fewer per step -- measured the
 // same time with two table-shaped rows and 3.5 % more with one masked row.)
-#ifndef QMC_T_DPP
-#define QMC_T_DPP 1
-#endif
 // every lane takes the value of the lane below it in its group, the first lane
 // that of the last (groups of 64: wave_ror:1; of 16: row_ror:1)
 template <int G>
@@ -1225,36 +1174,16 @@ __device__ __forceinline__ void pair_core1(const PairConstsT<R> &m, R as,
 // costs occupancy through LDS (P = 8: 128 KB per block, one wave per SIMD), so
 // the table is stored once and the rotated index is masked (one v_and per
 // partner table, i.e. per 2-8 pairs).
-#ifndef QMC_LINEAR_ORDER
-#define QMC_LINEAR_ORDER 1
-#endif
-#ifndef QMC_LEAD_SHORT
-#define QMC_LEAD_SHORT 1
-#endif
-#ifndef QMC_ROLLED_LOOP
-#define QMC_ROLLED_LOOP 1
-#endif
-#ifndef QMC_TWOCASE
-#define QMC_TWOCASE 1
-#endif
-
-// Tile-sweep knobs of the N = 512 shape (BASELINE.json configs[4]: "LDS
-// tile-size sweep"; tools/tile_sweep.sh builds the variants): own particles per
-// rotation pass (the register tile: 64 * QMC_PA8 particles) and copies of the
-// LDS tables.  Defaults = the fastest measured (profiles/r02_n512_tile_sweep.txt).
-#ifndef QMC_PA8
-#define QMC_PA8 8
-#endif
-#ifndef QMC_DUP8
-#define QMC_DUP8 1
-#endif
-
-#ifndef QMC_SORTED64
-#define QMC_SORTED64 1
-#endif
+//
+// The N = 512 shape (BASELINE.json configs[4]: "LDS tile-size sweep"): own
+// particles per rotation pass (the register tile: 64 * PA8 particles) and
+// copies of the LDS tables, the fastest measured (profiles/
+// r02_n512_tile_sweep.txt).
+static constexpr int PA8 = 8;
+static constexpr int DUP8 = 1;
 template <int G, int P, bool ZCLASS>
 struct GroupLds {
-    static constexpr int DUP = (P >= 8) ? QMC_DUP8 : ((P >= 2) ? 1 : 2);
+    static constexpr int DUP = (P >= 8) ? DUP8 : ((P >= 2) ? 1 : 2);
     static constexpr int ROW = DUP * G * P;
     // (the stepping kernels allocate the larger of this layout and the
     // sorted-row one, qmc_kernels.h: StepLds)
@@ -1297,7 +1226,7 @@ __device__ __forceinline__ void eval_walker(const DevModel &m,
     // Own particles are processed PA at a time: with P = 8 the tables of all
     // eight (96 VGPRs) would leave one wave per SIMD, so the rotation runs in
     // two passes of four own particles (tables re-read from LDS).
-    constexpr int PA = (P > 4) ? QMC_PA8 : P;
+    constexpr int PA = (P > 4) ? PA8 : P;
     constexpr int NPASS = P / PA;
     constexpr bool RD = sizeof(R) == 8;      // the pair loop runs in double
     R *lS = (R *)lds, *lC = lS + ROW, *lSU = lS + 2 * ROW,
@@ -1308,10 +1237,10 @@ __device__ __forceinline__ void eval_walker(const DevModel &m,
     // (one particle per lane; in double only where the kernels keep the lanes
     // in ascending position, i.e. one walker per wavefront: LINEAR_ORDER)
     constexpr bool ROTCOPY = (P == 1) && (DUP == 2) && !ZCLASS &&
-                             (!RD || (G == 64 && QMC_LINEAR_ORDER));
+                             (!RD || G == 64);
     // two particles per lane in ascending rows: two-case form (pair_core2)
-    constexpr bool TWOCASE = QMC_TWOCASE && (P == 2) && (G == 64) && !ZCLASS &&
-                             QMC_LINEAR_ORDER && SlotMap<G, P>::CONSECUTIVE;
+    constexpr bool TWOCASE = (P == 2) && (G == 64) && !ZCLASS &&
+                             SlotMap<G, P>::CONSECUTIVE;
     // four-case short-range form while the own tables fit (see pair_core4)
     constexpr bool FOURCASE = (P <= 2) && !ROTCOPY && !TWOCASE;
     PTabT<R> t[PA];
@@ -1538,7 +1467,7 @@ __device__ __forceinline__ void eval_walker(const DevModel &m,
         }
 
         // ---- k = 1 .. G/2: rotate over partner lanes ----
-        constexpr bool ROT_DPP = QMC_T_DPP && (G == 64 || G == 16) && !PAD;
+        constexpr bool ROT_DPP = (G == 64 || G == 16) && !PAD;
         const int lane = threadIdx.x & 63;
         // the lane below in the ring of the ge lanes in use
         const int src = lane - gl + (PAD ? (gl == 0 ? ge - 1 : gl - 1)
@@ -1639,11 +1568,6 @@ __device__ __forceinline__ void eval_walker(const DevModel &m,
                 QMC_FOLD(prodL, expL);                                        \
             }                                                                 \
         }
-#if QMC_ROLLED_LOOP
-#define QMC_ROLL_PRAGMA _Pragma("clang loop unroll(disable)")
-#else
-#define QMC_ROLL_PRAGMA
-#endif
 #define QMC_PASS(H)                                                           \
         if ((H) < NPASS) {                                                    \
             if (NPASS > 1) {                                                  \
@@ -1657,7 +1581,7 @@ __device__ __forceinline__ void eval_walker(const DevModel &m,
             /* (kept rolled: unrolled, the scheduler hoists the LDS reads of \
                every copy and the kernel loses half its occupancy: -8 %) */  \
             QMC_SECTION("rotation_loop_body");                                \
-            QMC_ROLL_PRAGMA                                                   \
+            _Pragma("clang loop unroll(disable)")                             \
             for (int k = ((H) == 0 ? k_first : 1); k < ge / 2; ++k)           \
                 QMC_KSTEP(H, k, false)                                        \
             QMC_SECTION("rotation_last_step");                                \
@@ -1691,8 +1615,7 @@ __device__ __forceinline__ void eval_walker(const DevModel &m,
         // against 24.  The first step where some lane says no is redone by the
         // general loop, which takes over from there.
         int k_first = 1;
-        constexpr bool LEAD_SHORT = QMC_LEAD_SHORT && ROTCOPY && (G == 64) &&
-                                    !PAD && (P == 1);
+        constexpr bool LEAD_SHORT = ROTCOPY && (G == 64) && !PAD && (P == 1);
         if constexpr (LEAD_SHORT) {
             if (pc.sp_ok) {
                 R Q1 = 0, P1 = 1;          // tallies of these steps
@@ -1812,7 +1735,7 @@ __device__ __forceinline__ void eval_walker(const DevModel &m,
     // cores, the energy's together with log|psi|'s further down)
     // (one particle per lane only: with more, the accumulator registers of the
     // matrix instruction cost the N = 128 DMC step a wave of occupancy, -5 %)
-    constexpr bool MSUM = QMC_MFMA_SUM && (G == 64) && (P == 1);
+    constexpr bool MSUM = (G == 64) && (P == 1);
     if (!EN) {
     } else if (!MSUM) E = group_sum<G>(e_lane);
     else if (!WF) E = wave_sum_mfma(e_lane);
@@ -1848,7 +1771,8 @@ __device__ __forceinline__ void eval_walker(const DevModel &m,
               xoff_sum;
         if (!WAVE_COUNT) lw += (double)nshort * m.log_am;
         if (MSUM && EN) {
-            wave_sum2_mfma(e_lane, lw, E, logwf);
+            E = wave_sum_mfma(e_lane);
+            logwf = wave_sum_mfma(lw);
             E += e_consts;
         } else if (MSUM) {
             logwf = wave_sum_mfma(lw);

@@ -8,10 +8,6 @@
 #include "qmc_sorted64.h"
 #include "qmc_sorted128.h"
 
-#ifndef QMC_SORTED128
-#define QMC_SORTED128 1
-#endif
-
 static constexpr int BLOCK = 256;          // 4 wavefronts per workgroup
 
 // Workgroup size of the walker kernels.  One walker per wavefront (G = 64):
@@ -22,12 +18,10 @@ static constexpr int BLOCK = 256;          // 4 wavefronts per workgroup
 // move and the two-pass step gains nothing (measured: 10 % fewer busy vector
 // cycles, 5 % MORE time); with one, a slot is free again as soon as its chain is
 // done.  The kernels synchronise inside a wavefront only, so the size is free.
-#ifndef QMC_BLOCK64
-#define QMC_BLOCK64 64
-#endif
+static constexpr int BLOCK64 = 64;
 template <int G>
 struct WalkBlock {
-    static constexpr int N = (G == 64) ? QMC_BLOCK64 : BLOCK;
+    static constexpr int N = (G == 64) ? BLOCK64 : BLOCK;
 };
 
 // Which walker a workgroup of the one-wavefront-per-workgroup kernels owns.
@@ -40,13 +34,12 @@ struct WalkBlock {
 // per VMC chain-step against the algorithmic 1056).  Here the 16 walkers of a
 // line go to ONE XCD: within every run of 128 workgroups, XCD x takes walkers
 // 16 x .. 16 x + 15.  (The launch grid is rounded up to a multiple of 128.)
-#ifndef QMC_XCD_MAP
-#define QMC_XCD_MAP 1
-#endif
+// The identity mapping was measured against it, 2 % slower on the VMC step
+// (profiles/r05_ab_variants.txt), and removed.
 template <int GPB>
 __device__ __forceinline__ long long walker_of_block(unsigned b, int grp)
 {
-    if (QMC_XCD_MAP && GPB == 1)
+    if (GPB == 1)
         return ((long long)(b >> 7) << 7) + ((b & 7u) << 4) + ((b & 127u) >> 3);
     return (long long)b * GPB + grp;
 }
@@ -60,13 +53,10 @@ template <int G, int P, bool PAD, bool ZC, bool DMC = false>
 struct StepLds {
     static constexpr int NROWS =
         DMC ? SortedCot<false, true, false>::ROWS : 5;
-    // (+ one row of partner sums, qmc_sorted64.h: QMC_T_LDS)
     static constexpr int SORTED =
-        (QMC_SORTED128 && G == 64 && P == 2 && !ZC)
-            ? NROWS * SortedRows<128>::ROW
-            : (QMC_SORTED64 && G == 64 && P == 1 && !ZC)
-                  ? (NROWS + (QMC_T_LDS ? 1 : 0)) * SortedRows<64>::ROW
-                  : 0;
+        (G == 64 && P == 2 && !ZC)   ? NROWS * SortedRows<128>::ROW
+        : (G == 64 && P == 1 && !ZC) ? NROWS * SortedRows<64>::ROW
+                                     : 0;
     // a walker that fails the per-walker checks of the sorted-row path runs
     // eval_walker on the same LDS region: room for the larger of the two
     // layouts (N <= 64: 485 doubles sorted, 512 general -- ADVICE r3)
@@ -140,44 +130,36 @@ __device__ __forceinline__ unsigned int vmc_read_slot(const uint32_t (&wd)[P],
 // r03_ab_variants.txt): the build without scratch ships.
 // (The N <= 128 shape held to 80 registers for 6 waves spills 56-140 bytes per
 // lane and loses 10-15 %.)
-#ifndef QMC_LB_P1
-#define QMC_LB_P1 7
-#endif
+static constexpr int LB_P1 = 7;
 // (the sorted-row N = 128 shape: 7.5 KB of LDS per walker leaves room for five
 // wavefronts per SIMD, which takes <= 96 registers)
-#ifndef QMC_LB_DMC_P2
-#define QMC_LB_DMC_P2 5
-#endif
-#define QMC_LB_WAVES , ((G == 64 && P == 1) ? QMC_LB_P1 : 1)
-#define QMC_LB_WAVES_DMC , ((G == 64 && P == 1) ? QMC_LB_P1 \
-                            : (G == 64 && P == 2 && !ZC) ? QMC_LB_DMC_P2 : 1)
+static constexpr int LB_DMC_P2 = 5;
 // (The VMC step of the exact N <= 128 shape held to 96 registers for a fifth
 // wave was 2.4 % faster with the four-case form; with the two-case form it needs
 // 108 registers unconstrained (4 waves) and the constraint costs 2.5 %: off.)
 // (Round 4: the production instantiation needs 94 on its own -- five waves --
 // but the series / tape instantiation was allotted 129, three waves: held to
 // four.)
-#ifndef QMC_LB_VMC_P2
-#define QMC_LB_VMC_P2 4
-#endif
+static constexpr int LB_VMC_P2 = 4;
 // (Round 6: the fused steady kernel of the N <= 64 shape takes 67 registers --
 // 7 waves, no scratch; held to 8 waves it spills 12 bytes per lane, and the
 // two measure the same, profiles/r06_ab_variants.txt.)
-#define QMC_LB_WAVES_VMC , ((G == 64 && P == 1) ? QMC_LB_P1 \
-                            : (G == 64 && P == 2 && !ZC) ? QMC_LB_VMC_P2 : 1)
+// The minimum waves per SIMD of a kernel on shape (G, P, ZC); `p2` is the
+// kernel's figure for the sorted-row N <= 128 shape (1: none).
+constexpr int lb_waves(int G, int P, bool ZC, int p2)
+{
+    return (G == 64 && P == 1) ? LB_P1 : (G == 64 && P == 2 && !ZC) ? p2 : 1;
+}
 
 // The VMC step in two passes (one wavefront per walker: the accept decision
 // is wave-uniform): log|psi| of the proposal first -- no quotient, no drift --
 // then, for accepted moves only, energy and drift from the pair tables still in
 // LDS.  The reference computes the energy of accepted moves only as well
 // (qmc_base/jastrow/vmc.py:253-262); a rejected proposal (53 % at the benchmark's
-// move spread) pays for log|psi| alone.
-#ifndef QMC_VMC_TWO_PASS
-#define QMC_VMC_TWO_PASS 1
-#endif
+// move spread) pays for log|psi| alone (vmc_step_kernel: TWO_PASS).
 
 // The second normal of a Box-Muller pair is kept for the next time step of the
-// slot (1) or computed again there (0: same stream, no `spare` array -- 8 N
+// slot (`spare`) or computed again there (same stream, no `spare` array -- 8 N
 // bytes less to write on even and to read on odd steps, a Philox block, a
 // logarithm, a square root and a sincos per particle more on odd ones;
 // VERDICT r3 item 5 asked for the A/B: profiles/r04_ab_variants.txt, 10).
@@ -189,18 +171,13 @@ __device__ __forceinline__ unsigned int vmc_read_slot(const uint32_t (&wd)[P],
 // ms).  The kernel is nowhere near the HBM roofline, so one particle per lane
 // keeps the cache; two or more per lane do without it -- 1 KiB less traffic
 // per walker-step at N = 128 and no 4.3 GB array at 2^22 walkers.
-#ifndef QMC_DMC_SPARE
-#define QMC_DMC_SPARE 1
-#endif
 template <int P>
 struct DmcSpare {
-    static constexpr bool ON = QMC_DMC_SPARE && P == 1;
+    static constexpr bool ON = P == 1;
 };
 
 // odd-even transposition passes (resort_step) run every this many steps
-#ifndef QMC_RESORT_EVERY
-#define QMC_RESORT_EVERY 4
-#endif
+static constexpr int RESORT_EVERY = 4;
 
 // --------------------------------------------------------------- kernels ---
 struct EvalArgs {
@@ -211,7 +188,7 @@ struct EvalArgs {
 };
 
 template <int G, int P, bool PAD, bool ZC, typename R = double>
-__global__ void __launch_bounds__(WalkBlock<G>::N QMC_LB_WAVES)
+__global__ void __launch_bounds__(WalkBlock<G>::N, lb_waves(G, P, ZC, 1))
 evaluate_kernel(const DevModel *__restrict__ mp, EvalArgs a)
 {
     // model constants live in device memory: scalar loads on demand keep the
@@ -263,7 +240,7 @@ struct PrepArgs {
 };
 
 template <int G, int P, bool PAD, bool ZC, typename R = double>
-__global__ void __launch_bounds__(WalkBlock<G>::N QMC_LB_WAVES)
+__global__ void __launch_bounds__(WalkBlock<G>::N, lb_waves(G, P, ZC, 1))
 prepare_kernel(const DevModel *__restrict__ mp, PrepArgs a)
 {
     // model constants live in device memory: scalar loads on demand keep the
@@ -360,14 +337,9 @@ struct VmcArgs {
 // shape 115 (4 waves, as its per-yield kernel).  Measured against the per-yield
 // launches, profiles/r06_ab_variants.txt: -9.5 % per step at N = 64, -8.8 % at
 // N = 48, -8.5 % at N = 128.
-#ifndef QMC_VMC_FUSED
-#define QMC_VMC_FUSED 1
-#endif
 template <int G, int P, bool ZC>
 struct VmcFused {
-    static constexpr bool ON =
-        QMC_VMC_FUSED && G == 64 && !ZC &&
-        ((P == 1 && QMC_SORTED64) || (P == 2 && QMC_SORTED128));
+    static constexpr bool ON = G == 64 && !ZC && (P == 1 || P == 2);
 };
 
 // LEAN = the production path (Philox uniform proposal, per-chain block sums
@@ -378,7 +350,7 @@ struct VmcFused {
 // every yield y >= 1; on VmcFused shapes once, for all of them).
 template <int G, int P, bool PAD, bool ZC, bool LEAN, typename R = double,
           bool STEADY = false>
-__global__ void __launch_bounds__(WalkBlock<G>::N QMC_LB_WAVES_VMC)
+__global__ void __launch_bounds__(WalkBlock<G>::N, lb_waves(G, P, ZC, LB_VMC_P2))
 vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
 {
     static_assert(LEAN || !STEADY, "the steady variant is a LEAN kernel");
@@ -514,13 +486,13 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
         aw1 = vmc_read_slot<P>(wacc, src1);
     }
     QMC_SECTION("resort");
-    // (one odd-even pass every QMC_RESORT_EVERY steps keeps the lanes sorted
+    // (one odd-even pass every RESORT_EVERY steps keeps the lanes sorted
     // well enough: a particle moves a few per cent of the spacing per step)
     // exactly ascending lanes: the fast pair sum of qmc_sorted64.h
     // (33 <= N <= 63 as well: the ring then has N members)
-    constexpr bool S64 = QMC_SORTED64 && G == 64 && P == 1 && !ZC;
+    constexpr bool S64 = G == 64 && P == 1 && !ZC;
     // (66 <= N <= 126, N even, as well: N / 2 lanes with two particles each)
-    constexpr bool S128 = QMC_SORTED128 && G == 64 && P == 2 && !ZC;
+    constexpr bool S128 = G == 64 && P == 2 && !ZC;
     bool fast = false;
     // (an initial configuration with a particle outside the box: the row in
     // memory is ordered by the positions as given, not by their images, and
@@ -543,34 +515,34 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
         // (diagnostic, cold path only: walkers that leave the sorted-row path)
         if (!fast && !m.is_ideal && gl == 0 && active)
             atomicAdd(m.diag, 1ull);
-    } else if constexpr (G == 64 && P == 1 && QMC_LINEAR_ORDER) {
+    } else if constexpr (G == 64 && P == 1) {
         // ascending order, wrap point anchored at the lane seam (qmc_device.h)
         // (one particle per lane: lanes 0 .. n-1 hold them)
         if (!forced) {
             anchor_seam(zn[0], labn[0], n);
-            if ((a.step % QMC_RESORT_EVERY) == 0)
+            if ((a.step % RESORT_EVERY) == 0)
                 resort_linear<G>(zn[0], labn[0], gl,
-                                 a.step / QMC_RESORT_EVERY, n);
+                                 a.step / RESORT_EVERY, n);
         }
-    } else if constexpr (SlotMap<G, P>::CONSECUTIVE && QMC_LINEAR_ORDER) {
+    } else if constexpr (SlotMap<G, P>::CONSECUTIVE) {
         if (!forced) {
             anchor_seam_rows<P>(zn, labn, n);
-            if ((a.step % QMC_RESORT_EVERY) == 0)
-                resort_linear_rows<P>(zn, labn, gl, a.step / QMC_RESORT_EVERY, n);
+            if ((a.step % RESORT_EVERY) == 0)
+                resort_linear_rows<P>(zn, labn, gl, a.step / RESORT_EVERY, n);
         }
-    } else if (!forced && (a.step % QMC_RESORT_EVERY) == 0)
-        resort_step<G, P>(zn, labn, gl, a.step / QMC_RESORT_EVERY, n, m.L,
+    } else if (!forced && (a.step % RESORT_EVERY) == 0)
+        resort_step<G, P>(zn, labn, gl, a.step / RESORT_EVERY, n, m.L,
                           m.half_L, lanes_in_use<G, PAD>(m));
-    constexpr bool TWO_PASS = QMC_VMC_TWO_PASS && (G == 64);
+    constexpr bool TWO_PASS = G == 64;   // (the 16/32-lane shapes: one pass)
     double F[P], ei[P], e_new = 0.0, wf_new;
     if (S64 && fast) {
         if constexpr (S64)
-            eval_sorted64<R, true, !TWO_PASS, false, PAD>(
+            eval_sorted64<R, true, false, false, PAD>(
                 m, zn[0], gl, lds, F[0], e_new, wf_new);
     } else if (S128 && fast) {
         if constexpr (S128)
-            eval_sorted128<R, true, !TWO_PASS, false, PAD>(m, zn, gl, lds, F,
-                                                           e_new, wf_new);
+            eval_sorted128<R, true, false, false, PAD>(m, zn, gl, lds, F,
+                                                       e_new, wf_new);
     } else {
         // (the general path; z1: see eval_walker -- the stored positions on
         // a first yield given outside the box, nothing was reordered then)
@@ -816,7 +788,7 @@ struct EvolveArgs {
 // Drift-diffusion + local energy of every child walker
 // (qmc_base/jastrow/dmc.py:758-825, 892-942).
 template <int G, int P, bool PAD, bool ZC, typename R = double>
-__global__ void __launch_bounds__(WalkBlock<G>::N QMC_LB_WAVES_DMC)
+__global__ void __launch_bounds__(WalkBlock<G>::N, lb_waves(G, P, ZC, LB_DMC_P2))
 dmc_evolve_kernel(const DevModel *__restrict__ mp, EvolveArgs a)
 {
     // model constants live in device memory: scalar loads on demand keep the
@@ -890,8 +862,8 @@ dmc_evolve_kernel(const DevModel *__restrict__ mp, EvolveArgs a)
         z[p] = zz;
     }
     QMC_SECTION("resort");
-    constexpr bool S64 = QMC_SORTED64 && G == 64 && P == 1 && !ZC;
-    constexpr bool S128 = QMC_SORTED128 && G == 64 && P == 2 && !ZC;
+    constexpr bool S64 = G == 64 && P == 1 && !ZC;
+    constexpr bool S128 = G == 64 && P == 2 && !ZC;
     bool fast = false;
     if constexpr (S64) {
         fast = !m.is_ideal && sort_lanes64(z[0], lab[0], gl, PAD ? n : 64) &&
@@ -907,16 +879,16 @@ dmc_evolve_kernel(const DevModel *__restrict__ mp, EvolveArgs a)
         // (diagnostic, cold path only: walkers that leave the sorted-row path)
         if (!fast && !m.is_ideal && gl == 0 && active)
             atomicAdd(m.diag, 1ull);
-    } else if constexpr (G == 64 && P == 1 && QMC_LINEAR_ORDER) {
+    } else if constexpr (G == 64 && P == 1) {
         anchor_seam(z[0], lab[0], n);
-        if ((step % QMC_RESORT_EVERY) == 0)
-            resort_linear<G>(z[0], lab[0], gl, step / QMC_RESORT_EVERY, n);
-    } else if constexpr (SlotMap<G, P>::CONSECUTIVE && QMC_LINEAR_ORDER) {
+        if ((step % RESORT_EVERY) == 0)
+            resort_linear<G>(z[0], lab[0], gl, step / RESORT_EVERY, n);
+    } else if constexpr (SlotMap<G, P>::CONSECUTIVE) {
         anchor_seam_rows<P>(z, lab, n);
-        if ((step % QMC_RESORT_EVERY) == 0)
-            resort_linear_rows<P>(z, lab, gl, step / QMC_RESORT_EVERY, n);
-    } else if ((step % QMC_RESORT_EVERY) == 0)
-        resort_step<G, P>(z, lab, gl, step / QMC_RESORT_EVERY, n, m.L,
+        if ((step % RESORT_EVERY) == 0)
+            resort_linear_rows<P>(z, lab, gl, step / RESORT_EVERY, n);
+    } else if ((step % RESORT_EVERY) == 0)
+        resort_step<G, P>(z, lab, gl, step / RESORT_EVERY, n, m.L,
                           m.half_L, lanes_in_use<G, PAD>(m));
     // positions and labels leave now: not live across the pair sum
 #pragma unroll

@@ -178,38 +178,10 @@ __device__ __forceinline__ double exp_bounded(double x)
 // (qmc_log_table_info, tests/test_cabi.py).  (Round 3 moved the mantissa to
 // [sqrt(1/2), sqrt(2)) to keep the RELATIVE error near 1 as well: four
 // instructions per logarithm for a property nobody uses.)
-#ifndef QMC_LOG_TABLE
-#define QMC_LOG_TABLE 1
-#endif
 static __device__ const double QMC_LOG_TAB[2 * QMC_LOG_ROWS] = { QMC_LOG_TAB_VALUES };
-
-__device__ __forceinline__ double log_series(double x)
-{
-    const double LN2_HI = 6.93147180369123816490e-01;
-    const double LN2_LO = 1.90821492927058770002e-10;
-    int e;
-    double m = frexp(x, &e);                 // m in [0.5, 1)
-    if (m < 0.70710678118654752440) { m *= 2.0; e -= 1; }
-    double s = fast_div(m - 1.0, m + 1.0);
-    double z = s * s;
-    double p = sconst(1.0 / 21.0);
-    p = fma(p, z, sconst(1.0 / 19.0));
-    p = fma(p, z, sconst(1.0 / 17.0));
-    p = fma(p, z, sconst(1.0 / 15.0));
-    p = fma(p, z, sconst(1.0 / 13.0));
-    p = fma(p, z, sconst(1.0 / 11.0));
-    p = fma(p, z, sconst(1.0 / 9.0));
-    p = fma(p, z, sconst(1.0 / 7.0));
-    p = fma(p, z, sconst(1.0 / 5.0));
-    p = fma(p, z, sconst(1.0 / 3.0));
-    double lm = fma(s * z, 2.0 * p, 2.0 * s);
-    double de = (double)e;
-    return fma(de, LN2_HI, fma(de, LN2_LO, lm));
-}
 
 __device__ __forceinline__ double log_pos(double x)
 {
-    if (!QMC_LOG_TABLE) return log_series(x);
     const double LN2_HI = 6.93147180369123816490e-01;
     const double LN2_LO = 1.90821492927058770002e-10;
     const double m = __builtin_amdgcn_frexp_mant(x);       // [1/2, 1)

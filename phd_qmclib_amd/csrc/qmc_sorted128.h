@@ -25,9 +25,6 @@
 // the two table entries of a lane (slots 2 l, 2 l + 1) in one LDS access:
 // ds_read_b128 in double (the rows keep the pairs 16-byte aligned,
 // SortedRows<128>), ds_read_b64 in float
-#ifndef QMC_S128_SU_PAIRS
-#define QMC_S128_SU_PAIRS 1
-#endif
 template <typename R> struct SlotPair;
 template <> struct SlotPair<double> {
     typedef double type __attribute__((ext_vector_type(2)));
@@ -239,12 +236,13 @@ __device__ __forceinline__ void eval_sorted128(const DevModel &m,
                     : (oa).ks0 * (bcu) - (oa).kc0 * (bsu);
     // a pair of a general step: class from the sine, short ones recomputed in
     // an exec-masked region
-    // (bsu, bcu: the partner's k2-table entry.  QMC_S128_SU_PAIRS: read for
-    // both partner slots with one 16-byte access per row at the top of the
-    // step -- a step of the general phase nearly always has short pairs in some
-    // lane, an LDS instruction costs the same for one lane as for 64, and a
-    // read inside the exec-masked region is a lane-stride-16 access (2-way
-    // bank conflict) whose latency nothing hides; 0: read where it is used)
+    // (bsu, bcu: the partner's k2-table entry, read for both partner slots
+    // with one 16-byte access per row at the top of the step -- a step of the
+    // general phase nearly always has short pairs in some lane, an LDS
+    // instruction costs the same for one lane as for 64, and a read inside the
+    // exec-masked region is a lane-stride-16 access (2-way bank conflict) whose
+    // latency nothing hides.  Reading them where they are used was measured,
+    // profiles/r04_ab_variants.txt 2, and removed.)
     // (COT, qmc_sorted64.h: cs = the partner's cotangent, cc = its position)
 #define QMC_S128_XY(oa, cs, cc, bsu, bcu, X, Y, sh)                           \
     const R Y##_s = COT ? (cs) - (oa).s              /* t_j - t_i */           \
@@ -353,25 +351,15 @@ __device__ __forceinline__ void eval_sorted128(const DevModel &m,
     // ---- general steps ----
     QMC_SECTION("rotation_loop_body");
     // the four pairs of a step against partner tables (s0, c0), (s1, c1)
-#if QMC_S128_SU_PAIRS
-#define QMC_S128_SU_LOAD(kk)                                                  \
-        const typename SlotPair<R>::type su_ = ld_pair(pSU - 2 * (kk)),       \
-            cu_ = TAN ? su_ : ld_pair(pCU - 2 * (kk));
-#define QMC_S128_SU(kk, b) su_[b]
-#define QMC_S128_CU(kk, b) cu_[b]
-#else
-#define QMC_S128_SU_LOAD(kk)
-#define QMC_S128_SU(kk, b) pSU[-2 * (kk) + (b)]
-#define QMC_S128_CU(kk, b) pCU[-2 * (kk) + (b)]
-#endif
 #define QMC_S128_STEP(s0_, c0_, s1_, c1_, kk, LAST)                           \
     {                                                                         \
         const bool mine = live & (!(LAST) || gl < K);                         \
-        QMC_S128_SU_LOAD(kk)                                                  \
-        QMC_S128_XY(o[0], s0_, c0_, QMC_S128_SU(kk, 0), QMC_S128_CU(kk, 0), X00, Y00, h00) \
-        QMC_S128_XY(o[1], s0_, c0_, QMC_S128_SU(kk, 0), QMC_S128_CU(kk, 0), X10, Y10, h10) \
-        QMC_S128_XY(o[0], s1_, c1_, QMC_S128_SU(kk, 1), QMC_S128_CU(kk, 1), X01, Y01, h01) \
-        QMC_S128_XY(o[1], s1_, c1_, QMC_S128_SU(kk, 1), QMC_S128_CU(kk, 1), X11, Y11, h11) \
+        const typename SlotPair<R>::type su_ = ld_pair(pSU - 2 * (kk)),       \
+            cu_ = TAN ? su_ : ld_pair(pCU - 2 * (kk));                        \
+        QMC_S128_XY(o[0], s0_, c0_, su_[0], cu_[0], X00, Y00, h00)            \
+        QMC_S128_XY(o[1], s0_, c0_, su_[0], cu_[0], X10, Y10, h10)            \
+        QMC_S128_XY(o[0], s1_, c1_, su_[1], cu_[1], X01, Y01, h01)            \
+        QMC_S128_XY(o[1], s1_, c1_, su_[1], cu_[1], X11, Y11, h11)            \
         if (WF && mine) {                                                     \
             PL *= (Y00 * Y10) * (Y01 * Y11);                                  \
             if (h00) { asm volatile(""); PS *= Y00; }                         \
@@ -476,9 +464,6 @@ __device__ __forceinline__ void eval_sorted128(const DevModel &m,
         if (half_last) QMC_S128_STEP(as[0], ac[0], as[1], ac[1], k, true)
     }
 #undef QMC_S128_STEP
-#undef QMC_S128_SU_LOAD
-#undef QMC_S128_SU
-#undef QMC_S128_CU
 #undef QMC_S128_LONG_STEP
 #undef QMC_S128_LONG_XY
 #undef QMC_S128_XY

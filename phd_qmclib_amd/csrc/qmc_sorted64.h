@@ -40,22 +40,14 @@
 
 #include "qmc_device.h"
 
-#ifndef QMC_SORTED64
-#define QMC_SORTED64 1
-#endif
-#ifndef QMC_LDS_AHEAD
-#define QMC_LDS_AHEAD 0
-#endif
-// The partner's share of a pair's drift: added into an LDS row at the partner's
-// table index with ds_add_f64 (1), or carried in a travelling register that
-// rotates one lane per step (0: a subtraction and two DPP moves per step).
-// Measured twice now (round 2 on the general path, round 3 here): the atomics
-// remove 3 vector instructions per step of the energy pass and are SLOWER --
-// VMC 1.882 against 1.829 ms, DMC 0.526 against 0.515 (profiles/
-// r03_ab_variants.txt): ds_add_f64 occupies the LDS pipe for 32 cycles.
-#ifndef QMC_T_LDS
-#define QMC_T_LDS 0
-#endif
+// The partner's share of a pair's drift is carried in a travelling register
+// that rotates one lane per step (a subtraction and two DPP moves per step).
+// Adding it into an LDS row at the partner's table index with ds_add_f64
+// instead was measured twice (round 2 on the general path, round 3 here) and
+// removed: the atomics remove 3 vector instructions per step of the energy
+// pass and are SLOWER -- VMC 1.882 against 1.829 ms, DMC 0.526 against 0.515
+// (profiles/r03_ab_variants.txt): ds_add_f64 occupies the LDS pipe for 32
+// cycles.
 // Long-range pairs of the energy-only evaluation (the DMC step: no log|psi|)
 // from ONE table per particle, t = cot(pi z / L):
 //   a_long cot(pi D' / L) = a_long (t_i t_j + 1) / (t_j - t_i),
@@ -73,16 +65,10 @@
 // two correctly rounded operations on correctly rounded cotangents).
 // The log|psi| pass needs sin(pi D' / L) itself (the factor of the product),
 // so that pass keeps the sin / cos tables.
-#ifndef QMC_COT
-#define QMC_COT 1
-#endif
 // The energy pass of the two-pass VMC step (REUSE: tables of this
 // configuration are in LDS) uses it too: every lane replaces its entries of the
 // sine row by the cotangent (one division per accepted move) and the loops take
 // the partner's position from the position row.
-#ifndef QMC_COT_REUSE
-#define QMC_COT_REUSE 1
-#endif
 // The short-range pairs of the same passes, likewise from one number per
 // particle: with A = k2 z_i - phi (own) and B = k2 z'_j (partner),
 //   f2'/f2 = -k2 tan(A - B) = -k2 (tan A - tan B) / (1 + tan A tan B):
@@ -99,9 +85,6 @@
 // per-particle tangents are clamped away from zero (sign kept) so that no
 // product overflows.  Accuracy: the reference's golden configurations through
 // this form, tests/test_gpu_sorted_pins.py, 2e-11.
-#ifndef QMC_TAN
-#define QMC_TAN 1
-#endif
 
 // Trailing rotation steps without classification (one particle per lane).  In
 // the stationary ensemble of the benchmark box 15 of the 31 steps are
@@ -111,26 +94,10 @@
 // all-long (profiles/r04_ab_variants.txt section 13).
 // One logarithm per lane in the log|psi| pass (pairs of lanes share the two
 // products; eval_sorted64).
-#ifndef QMC_LW_PAIRS
-#define QMC_LW_PAIRS 1
-#endif
-#ifndef QMC_S64_TRAIL
-#define QMC_S64_TRAIL 1
-#endif
-// The log|psi| pass with the pair class from the positions (QMC_WF_ZCLASS): a
-// long lane computes the sine and multiplies it into the product of the long
-// factors, a short lane computes the short-range factor and multiplies it into
-// the product of the short ones -- the same instructions as with the class
-// from the sine (which every lane computed first), but each on the lanes that
-// need it only: fewer fp64 operations on live lanes, one more LDS read per step.
-#ifndef QMC_WF_ZCLASS
-#define QMC_WF_ZCLASS 0
-#endif
 template <bool WF, bool EN, bool REUSE>
 struct SortedCot {
-    static constexpr bool ON = QMC_COT && EN && !WF &&
-                               (QMC_COT_REUSE || !REUSE);
-    static constexpr bool TAN = ON && QMC_TAN;
+    static constexpr bool ON = EN && !WF;
+    static constexpr bool TAN = ON;     // (the short pairs: the tangent form)
     // The DMC step (energy only, tables built here) then uses THREE rows --
     // cotangent, kappa tan(k2 z), position -- and keeps them together: 4.7 KB
     // per walker at N = 128 instead of 7.8 (the VMC step needs all five rows
@@ -260,23 +227,6 @@ __device__ __forceinline__ bool far_partner_ok_ring(const DevModel &m, double z,
     return __builtin_amdgcn_ballot_w64(live & (d >= m.L_minus_rm)) == 0ull;
 }
 
-// A table read that stays where it is written: the loops below request the
-// partner's entries ahead of their use, and the optimizer otherwise sinks a
-// plain load back to its first use (the round trip then lies in the step's
-// critical path again).
-template <typename R>
-__device__ __forceinline__ R lds_ahead(const R *p)
-{
-#if QMC_LDS_AHEAD
-    // (an explicit LDS pointer: a volatile access through a generic one is
-    // issued as a flat load)
-    typedef const volatile __attribute__((address_space(3))) R *lds_ptr;
-    return *(lds_ptr)p;
-#else
-    return *p;
-#endif
-}
-
 template <typename R>
 struct Own64 {
     R s, c;          // sin, cos(pi z / L)
@@ -386,7 +336,7 @@ __device__ __forceinline__ void sorted_particle_setup(const DevModel &m, double 
     // the k2 entry one period below: rotation by k2 L
     pub.su_lo = fma(ta.su, m.cth, -(ta.cu * m.sth_signed));
     pub.cu_lo = fma(ta.cu, m.cth, ta.su * m.sth_signed);
-    if (COT && TAN) {
+    if (COT) {
         // cot(pi z / L) = c / s, tan(k2 z - phi) = s0 / c0, tan(k2 z) = su / cu
         // and tan(k2 z - k2 L) = su_lo / cu_lo: FOUR quotients from ONE
         // reciprocal (of the product of the denominators; 15 fp64 operations
@@ -422,13 +372,6 @@ __device__ __forceinline__ void sorted_particle_setup(const DevModel &m, double 
         pub.su = m.m_k2_over_a * tB;                     // kappa tan(k2 z)
         pub.su_lo = m.m_k2_over_a * tBl;
     } else {
-        // (clamp: the product of two clamped quantities stays finite)
-        const double tiny = sizeof(R) == 4 ? 1e-18 : 1e-140;
-        if (COT) {
-            // (s >= 0 inside the box)
-            pub.s = fast_div(ta.c, fmax(ta.s, tiny));    // cot(pi z / L)
-            pub.c = z;
-        }
         o.s0 = (R)s0; o.c0 = (R)c0;
         if (EN) {
             o.ks0 = (R)(m.m_k2_over_a * s0);
@@ -487,15 +430,9 @@ __device__ __forceinline__ void eval_sorted64(const DevModel &m, double z, int g
     constexpr int G = 64, H = SortedRows<G>::H, ROW = SortedRows<G>::ROW;
     constexpr bool COT = SortedCot<WF, EN, REUSE>::ON;
     constexpr bool TAN = SortedCot<WF, EN, REUSE>::TAN;
-    constexpr bool ZW = QMC_WF_ZCLASS && WF && !EN;   // (PL = long factors only)
-    // (1: in every pass; 2: in the passes that compute the energy)
-    constexpr bool TRAIL = QMC_S64_TRAIL == 1 || (QMC_S64_TRAIL == 2 && EN);
     typedef SortedCot<WF, EN, REUSE> RowsOf;
     R *lS = (R *)lds, *lC = lS + ROW, *lSU = lS + RowsOf::ROW_SU * ROW,
       *lCU = lS + 3 * ROW, *lZ = lS + RowsOf::ROW_Z * ROW;
-    // sixth row (double whatever R is): the sums the partners collect
-    constexpr bool T_LDS = QMC_T_LDS && EN;
-    double *lA = lds + RowsOf::ROWS * ROW;
     const int nl = PAD ? m.n : G;            // lanes in use = particles
     const int K = nl / 2;                    // rotation steps
     const bool half_last = !PAD || (nl & 1) == 0;   // step K is a half step
@@ -511,15 +448,7 @@ __device__ __forceinline__ void eval_sorted64(const DevModel &m, double z, int g
     SortedPub pub_own;
     sorted_particle_setup<R, WF, EN, REUSE, G>(m, z, gl, (R *)lds, o, ob, nl,
                                                ta_own, pub_own);
-    // (where the shares of this lane's particle arrive: its own index from the
-    // lanes above it, the index one period below from the lanes that reach it
-    // around the end of the row)
-    const int a_lo = H + gl - nl;
-    if (T_LDS && live) {
-        lA[H + gl] = 0.0;
-        if (a_lo >= 1) lA[a_lo] = 0.0;
-    }
-    if (!REUSE || T_LDS || COT) {
+    if (!REUSE || COT) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -534,8 +463,6 @@ __device__ __forceinline__ void eval_sorted64(const DevModel &m, double z, int g
     // (COT: the second entry of a general step is the partner's position)
     const R *pS = lS + H + gl, *pC = (COT ? lZ : lC) + H + gl,
             *pSU = lSU + H + gl, *pCU = lCU + H + gl, *pZ = lZ + H + gl;
-    typedef __attribute__((address_space(3))) double *lds_dptr;
-    const lds_dptr pA = (lds_dptr)(lA + H + gl);
     // the lane below in the ring of the lanes in use (travelling sums)
     int ring_src = 0;
     if (PAD) ring_src = (live ? (gl == 0 ? nl - 1 : gl - 1) : gl) << 2;
@@ -573,24 +500,18 @@ __device__ __forceinline__ void eval_sorted64(const DevModel &m, double z, int g
 #define QMC_S64_ADD_Q(q, kk)                                                  \
     {                                                                         \
         Fr += (q);                                                            \
-        if (T_LDS) {                                                          \
-            if (live)                                                         \
-                (void)__builtin_amdgcn_ds_atomic_fadd_f64(pA - (kk),          \
-                                                          -(double)(q));      \
-        } else {                                                              \
-            T -= (q);                                                         \
-            T = (R)QMC_S64_ROR(T);                                            \
-        }                                                                     \
+        T -= (q);                                                             \
+        T = (R)QMC_S64_ROR(T);                                                \
     }
     // every lane in use says yes
 #define QMC_S64_ALL(cond)                                                     \
     ((__builtin_amdgcn_ballot_w64(cond) | ~live_mask) == ~0ull)
     {
         // (TAN: the cosine row of the k2-table is not read -- nor written)
-        R asu = lds_ahead(pSU - 1), acu = TAN ? (R)0 : lds_ahead(pCU - 1),
-          az = lds_ahead(pZ - 1);
-        R bsu = lds_ahead(pSU - 2), bcu = TAN ? (R)0 : lds_ahead(pCU - 2),
-          bz = lds_ahead(pZ - 2);
+        R asu = pSU[-1], acu = TAN ? (R)0 : pCU[-1],
+          az = pZ[-1];
+        R bsu = pSU[-2], bcu = TAN ? (R)0 : pCU[-2],
+          bz = pZ[-2];
         // (k odd at the top; both steps of a trip are full steps.  The row
         // ascends: when the FARTHER partner of a trip is short for every lane,
         // so is the nearer one -- one wave-wide test per trip, on az no more)
@@ -601,13 +522,13 @@ __device__ __forceinline__ void eval_sorted64(const DevModel &m, double z, int g
             // the loop carries neither the old product nor the old address)
             if (!QMC_S64_ALL(bz > o.zt)) break;
             QMC_S64_LEAD_XY(asu, acu, Xa, Ya)
-            asu = lds_ahead(pSU - (k + 2));
-            if (!TAN) acu = lds_ahead(pCU - (k + 2));
-            az = lds_ahead(pZ - (k + 2));
+            asu = pSU[-(k + 2)];
+            if (!TAN) acu = pCU[-(k + 2)];
+            az = pZ[-(k + 2)];
             QMC_S64_LEAD_XY(bsu, bcu, Xb, Yb)
-            bsu = lds_ahead(pSU - (k + 3));
-            if (!TAN) bcu = lds_ahead(pCU - (k + 3));
-            bz = lds_ahead(pZ - (k + 3));
+            bsu = pSU[-(k + 3)];
+            if (!TAN) bcu = pCU[-(k + 3)];
+            bz = pZ[-(k + 3)];
             k += 2;
             if (EN) {
                 // (one reciprocal for both quotients -- r = 1 / (Ya Yb), qa = Xa r
@@ -624,30 +545,13 @@ __device__ __forceinline__ void eval_sorted64(const DevModel &m, double z, int g
     }
 #undef QMC_S64_LEAD_XY
     // (these pairs belong to both products and both sums)
-    if (WF && !ZW) { PL = PS; eL = eS; }
+    if (WF) { PL = PS; eL = eS; }
     if (EN) { Qall = Qs; ns = (k - 1) * nl; }
 
     // ---- general steps: classified pair by pair ----
     QMC_SECTION("rotation_loop_body");
     // numerator / denominator / class of a general step
     // (COT: cs = the partner's cotangent, cc = its position)
-    // (ZW: the log|psi| pass with the class from the partner's position zj)
-#define QMC_S64_ZW(cs, cc, zj, kk, LAST)                                      \
-    {                                                                         \
-        const bool mine = live & (!(LAST) || gl < K);                         \
-        const bool sh = (zj) > o.zt;                                          \
-        if (!sh) {                                                            \
-            asm volatile("");                                                 \
-            const R Y = o.s * (cc) - o.c * (cs);                              \
-            if (mine) PL *= Y;                                                \
-        }                                                                     \
-        if (sh) {                                                             \
-            asm volatile("");                                                 \
-            const R bsu_ = pSU[-(kk)], bcu_ = pCU[-(kk)];                     \
-            const R Y = o.c0 * bcu_ + o.s0 * bsu_;                            \
-            if (mine) PS *= Y;                                                \
-        }                                                                     \
-    }
 #define QMC_S64_XY(cs, cc, kk, LAST, X, Y, sh, mine)                          \
     const R Y##_s = COT ? (cs) - o.s           /* t_j - t_i */                 \
                         : o.s * (cc) - o.c * (cs);  /* sin(pi D' / L) >= 0 */  \
@@ -686,126 +590,89 @@ __device__ __forceinline__ void eval_sorted64(const DevModel &m, double z, int g
             Qs = q_fma(q, q, Qs);                                             \
         }                                                                     \
     }
-    if constexpr (ZW) {
-        R as_ = lds_ahead(pS - k), ac_ = lds_ahead(pC - k), az_ = lds_ahead(pZ - k);
-        R bs_ = lds_ahead(pS - (k + 1)), bc_ = lds_ahead(pC - (k + 1)),
-          bz_ = lds_ahead(pZ - (k + 1));
+    R as_ = pS[-k], ac_ = pC[-k];   // step k
+    // step k + 1 (<= K + 1: inside the rows)
+    R bs_ = pS[-(k + 1)], bc_ = pC[-(k + 1)];
 #pragma clang loop unroll(disable)
-        while (k < kfull) {
-            QMC_S64_ZW(as_, ac_, az_, k, false)
-            as_ = lds_ahead(pS - (k + 2)); ac_ = lds_ahead(pC - (k + 2));
-            az_ = lds_ahead(pZ - (k + 2));
-            QMC_S64_ZW(bs_, bc_, bz_, k + 1, false)
-            bs_ = lds_ahead(pS - (k + 3)); bc_ = lds_ahead(pC - (k + 3));
-            bz_ = lds_ahead(pZ - (k + 3));
-            k += 2;
-            if (sizeof(R) == 4) {
-                q_fold(PS, eS);
-                q_fold(PL, eL);
-            }
+    while (k < kfull) {
+        QMC_S64_XY(as_, ac_, k, false, Xa, Ya, sha, minea)
+        as_ = pS[-(k + 2)]; ac_ = pC[-(k + 2)];
+        QMC_S64_XY(bs_, bc_, k + 1, false, Xb, Yb, shb, mineb)
+        // (k + 3 <= K + 2: the unused entry in front of the rows)
+        bs_ = pS[-(k + 3)]; bc_ = pC[-(k + 3)];
+        k += 2;
+        if (EN) {
+            const R qa = pair_div(Xa, Ya), qb = pair_div(Xb, Yb);
+            QMC_S64_ADD_Q(qa, k - 2)
+            QMC_S64_ADD_Q(qb, k - 1)
+            QMC_S64_TALLY(qa, sha, minea)
+            QMC_S64_TALLY(qb, shb, mineb)
         }
-        if (k <= kfull) {
-            QMC_S64_ZW(as_, ac_, az_, k, false)
-            ++k;
-            as_ = bs_; ac_ = bc_; az_ = bz_;
+        if (WF && sizeof(R) == 4) {
+            q_fold(PS, eS);
+            q_fold(PL, eL);
         }
-        QMC_SECTION("rotation_last_step");
-        if (half_last) QMC_S64_ZW(as_, ac_, az_, k, true)
-    } else {
-        R as_ = lds_ahead(pS - k), ac_ = lds_ahead(pC - k);   // step k
-        // step k + 1 (<= K + 1: inside the rows)
-        R bs_ = lds_ahead(pS - (k + 1)), bc_ = lds_ahead(pC - (k + 1));
-#pragma clang loop unroll(disable)
-        while (k < kfull) {
-            QMC_S64_XY(as_, ac_, k, false, Xa, Ya, sha, minea)
-            as_ = lds_ahead(pS - (k + 2)); ac_ = lds_ahead(pC - (k + 2));
-            QMC_S64_XY(bs_, bc_, k + 1, false, Xb, Yb, shb, mineb)
-            // (k + 3 <= K + 2: the unused entry in front of the rows)
-            bs_ = lds_ahead(pS - (k + 3)); bc_ = lds_ahead(pC - (k + 3));
-            k += 2;
-            if (EN) {
-                const R qa = pair_div(Xa, Ya), qb = pair_div(Xb, Yb);
-                QMC_S64_ADD_Q(qa, k - 2)
-                QMC_S64_ADD_Q(qb, k - 1)
-                QMC_S64_TALLY(qa, sha, minea)
-                QMC_S64_TALLY(qb, shb, mineb)
-            }
-            if (WF && sizeof(R) == 4) {
-                q_fold(PS, eS);
-                q_fold(PL, eL);
-            }
-            // the row ascends: a lane's partners only get farther, so once
-            // no lane had a short pair in a step none will in a later one
-            if (TRAIL && shb_m == 0ull) break;
-        }
-        // ---- trailing steps: every pair is long-range, no classification ----
-        if (TRAIL) {
-            QMC_SECTION("rotation");
+        // the row ascends: a lane's partners only get farther, so once
+        // no lane had a short pair in a step none will in a later one
+        if (shb_m == 0ull) break;
+    }
+    // ---- trailing steps: every pair is long-range, no classification ----
+    QMC_SECTION("rotation");
 #define QMC_S64_LONG(cs, cc)                                                  \
-            {                                                                 \
-                const R Y = COT ? (cs) - o.s : o.s * (cc) - o.c * (cs);       \
-                if (WF && live) PL *= Y;                                      \
-                if (EN) {                                                     \
-                    const R X = COT ? q_fma(o.s, (cs), (R)1)                  \
-                                    : o.c * (cc) + o.s * (cs);                \
-                    const R q = pair_div(X, Y);                               \
-                    QMC_S64_ADD_Q(q, k)                                       \
-                    if (live) Qall = q_fma(q, q, Qall);                       \
-                }                                                             \
-                ++k;                                                          \
-            }
+    {                                                                         \
+        const R Y = COT ? (cs) - o.s : o.s * (cc) - o.c * (cs);               \
+        if (WF && live) PL *= Y;                                              \
+        if (EN) {                                                             \
+            const R X = COT ? q_fma(o.s, (cs), (R)1)                          \
+                            : o.c * (cc) + o.s * (cs);                        \
+            const R q = pair_div(X, Y);                                       \
+            QMC_S64_ADD_Q(q, k)                                               \
+            if (live) Qall = q_fma(q, q, Qall);                               \
+        }                                                                     \
+        ++k;                                                                  \
+    }
 #pragma clang loop unroll(disable)
-            while (k < kfull) {
-                // (the entries of a trip are read IN the trip: requested a
-                // trip ahead they arrive in other registers than the loop
-                // carries and cost two 64-bit moves per trip -- the latency is
-                // the other wavefronts' to hide, the moves are nobody's)
-                QMC_S64_LONG(pS[-k], pC[-k])
-                QMC_S64_LONG(pS[-k], pC[-k])
-                if (WF && sizeof(R) == 4) q_fold(PL, eL);
-            }
-            as_ = pS[-k]; ac_ = pC[-k];
-            bs_ = pS[-(k + 1)]; bc_ = pC[-(k + 1)];
+    while (k < kfull) {
+        // (the entries of a trip are read IN the trip: requested a
+        // trip ahead they arrive in other registers than the loop
+        // carries and cost two 64-bit moves per trip -- the latency is
+        // the other wavefronts' to hide, the moves are nobody's)
+        QMC_S64_LONG(pS[-k], pC[-k])
+        QMC_S64_LONG(pS[-k], pC[-k])
+        if (WF && sizeof(R) == 4) q_fold(PL, eL);
+    }
+    as_ = pS[-k]; ac_ = pC[-k];
+    bs_ = pS[-(k + 1)]; bc_ = pC[-(k + 1)];
 #undef QMC_S64_LONG
+    if (k <= kfull) {
+        // an odd number of full steps was left: the last one is in the
+        // first set
+        QMC_S64_XY(as_, ac_, k, false, Xa, Ya, sha, minea)
+        if (EN) {
+            const R q = pair_div(Xa, Ya);
+            QMC_S64_ADD_Q(q, k)
+            QMC_S64_TALLY(q, sha, minea)
         }
-        if (k <= kfull) {
-            // an odd number of full steps was left: the last one is in the
-            // first set
-            QMC_S64_XY(as_, ac_, k, false, Xa, Ya, sha, minea)
-            if (EN) {
-                const R q = pair_div(Xa, Ya);
-                QMC_S64_ADD_Q(q, k)
-                QMC_S64_TALLY(q, sha, minea)
-            }
-            ++k;
-            as_ = bs_; ac_ = bc_;
-        }
-        // the final half step (an even number of lanes in use) visits every
-        // pair from both sides: each side updates its own particle, the lower
-        // half of the lanes tallies
-        QMC_SECTION("rotation_last_step");
-        if (half_last) {
-            QMC_S64_XY(as_, ac_, k, true, Xl, Yl, shl, minel)
-            if (EN) {
-                const R q = pair_div(Xl, Yl);
-                Fr += q;
-                QMC_S64_TALLY(q, shl, minel)
-            }
+        ++k;
+        as_ = bs_; ac_ = bc_;
+    }
+    // the final half step (an even number of lanes in use) visits every
+    // pair from both sides: each side updates its own particle, the lower
+    // half of the lanes tallies
+    QMC_SECTION("rotation_last_step");
+    if (half_last) {
+        QMC_S64_XY(as_, ac_, k, true, Xl, Yl, shl, minel)
+        if (EN) {
+            const R q = pair_div(Xl, Yl);
+            Fr += q;
+            QMC_S64_TALLY(q, shl, minel)
         }
     }
 #undef QMC_S64_XY
-#undef QMC_S64_ZW
 #undef QMC_S64_TALLY
 #undef QMC_S64_ADD_Q
 #undef QMC_S64_ALL
-    if (T_LDS) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        double t = lA[H + gl];
-        if (a_lo >= 1) t += lA[a_lo];
-        Fr += (R)t;
-    } else if (EN) {
+    if (EN) {
         // after kfull rotations lane l holds the sum of particle l - kfull - 1
         if (PAD) {
             int src = gl + kfull + 1;
@@ -835,12 +702,7 @@ __device__ __forceinline__ void eval_sorted64(const DevModel &m, double z, int g
     if (WF) {
         const double LN2 = 0.693147180559945309417;
         const double PS_d = (double)PS, PL_d = (double)PL;
-        if (ZW) {
-            // (PL: the long factors alone)
-            lw = fma(m.beta, log_pos(PL_d),
-                     log_pos((!m.is_free && m.ob_table) ? PS_d : prod1 * PS_d));
-        } else if (QMC_LW_PAIRS && sizeof(R) == 8 && !m.is_free &&
-                   m.ob_table) {
+        if (sizeof(R) == 8 && !m.is_free && m.ob_table) {
             // ONE logarithm per lane instead of two.  What the sum over the
             // lanes needs is beta sum log PL + (1 - beta) sum log PS, and a
             // wavefront pays for a logarithm per instruction sequence, not per
@@ -877,18 +739,17 @@ __device__ __forceinline__ void eval_sorted64(const DevModel &m, double z, int g
             lw = log_pos(prod1 * PS_d) +
                  m.beta * log_pos(fast_div(PL_d, PS_d));
         }
-        constexpr bool LWP = QMC_LW_PAIRS && sizeof(R) == 8 && !ZW;
-        const bool merged = LWP && !m.is_free && m.ob_table;
+        const bool merged = sizeof(R) == 8 && !m.is_free && m.ob_table;
         if (sizeof(R) == 4)
-            lw += LN2 * ((double)eS +
-                         m.beta * (double)(ZW ? eL : eL - eS));
+            lw += LN2 * ((double)eS + m.beta * (double)(eL - eS));
         if (!merged) {
             lw -= xoff;
             if (PAD && !live) lw = 0.0;
         }
     }
     if (WF && EN) {
-        wave_sum2_mfma(e_lane, lw, E, logwf);
+        E = wave_sum_mfma(e_lane);
+        logwf = wave_sum_mfma(lw);
         E += e_consts;
     } else if (EN) {
         E = wave_sum_mfma(e_lane) + e_consts;

@@ -181,7 +181,7 @@ static unsigned grid_for(long long nwalkers)
     const long long gpb = WalkBlock<G>::N / G;
     long long blocks = (nwalkers + gpb - 1) / gpb;
     // (one wavefront per workgroup: walker_of_block permutes runs of 128)
-    if (QMC_XCD_MAP && gpb == 1) blocks = (blocks + 127) / 128 * 128;
+    if (gpb == 1) blocks = (blocks + 127) / 128 * 128;
     return (unsigned)blocks;
 }
 
@@ -362,9 +362,6 @@ static void build_dev_model(const qmc_model_params &p, DevModel &d)
         d.m_k2 = -d.k2;
     }
     d.sin_rm = (d.rm >= d.half_L) ? 1.0 : sin(QMC_PI * d.rm / d.L);
-#ifdef QMC_ABLATION     // timing experiments (tools/build_variant.sh): wrong physics
-    if (const char *env = getenv("QMCWALK_ABL_SINRM")) d.sin_rm = atof(env);
-#endif
     // sin(pi r / L) is flat near r = L/2: classify from positions there
     d.zclass = d.rm > 0.45 * d.L;
     double pi_L = QMC_PI / d.L;
@@ -538,15 +535,12 @@ static void build_ob_table(const DevModel &d, std::vector<double> &tab,
 // nothing if that takes more than QMC_TRIG_MAX_ROWS rows (128 KB).
 #define QMC_TRIG_DMAX 4.0e-3
 #define QMC_TRIG_MAX_ROWS 4096
-#ifndef QMC_TRIG_TABLE
-#define QMC_TRIG_TABLE 1       // 0: build variant without it (A/B runs)
-#endif
 static void build_trig_table(DevModel &d, std::vector<double> &tab)
 {
     tab.clear();
     d.trig_table = nullptr;
     d.tg_rows = 0;
-    if (d.is_ideal || !(d.L > 0.0) || !QMC_TRIG_TABLE) return;
+    if (d.is_ideal || !(d.L > 0.0)) return;
     const double span = fmax(QMC_PI, fabs(d.k2) * d.L);
     int rows = 256;
     while (rows <= QMC_TRIG_MAX_ROWS && span / (2.0 * rows) > QMC_TRIG_DMAX)
@@ -1474,7 +1468,7 @@ extern "C" int qmc_dmc_create(qmc_engine *e, const qmc_dmc_params *p,
     }
     // (the cached second Box-Muller normal: one particle per lane only,
     // qmc_kernels.h: DmcSpare)
-    const bool need_spare = QMC_DMC_SPARE && e->P == 1;
+    const bool need_spare = e->P == 1;
     rc = rc || dev_alloc(&d->eslot, W) ||
          (need_spare && dev_alloc(&d->spare, W * n)) ||
          dev_alloc(&d->ref, W) ||

@@ -1,7 +1,8 @@
 #!/bin/bash
 # usage: tools/build_variant.sh <name> "<extra hipcc flags>"
-# Builds build/variants/<name>/libqmcwalk.so with extra -D flags for A/B runs
-# (select it with QMCWALK_LIB=<path>; development tool).
+# Builds build/variants/<name>/libqmcwalk.so with extra -D flags for the
+# diagnostic builds (-DQMC_CUTS, -DQMC_TIMING; select it with QMCWALK_LIB=<path>;
+# development tool).
 set -eu
 R=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; shift

@@ -3,6 +3,8 @@
 #   e.g. tools/isa_one.sh 'vmc_step_kernel<64, 1, false, false, true>'
 # Compiles ONE instantiation of a kernel of qmc_kernels.h for gfx950 (device
 # only) and writes its ISA; prints the resource usage and instruction counts.
+# QMC_EXTRA="-D..." in the environment adds flags (diagnostic builds such as
+# -DQMC_CUTS or -DQMC_TIMING).
 set -eu
 R=$(cd "$(dirname "$0")/.." && pwd)
 inst=$1

@@ -1,7 +1,8 @@
 """Register / scratch / occupancy table of the PRODUCTION instantiations of a
 translation unit (same flags as csrc/Makefile, device code only; development
 tool).  usage: kernel_resources.py [shape ...]   (default: 64_1 64_2)
-QMC_EXTRA="-D..." in the environment adds flags (A/B variants)."""
+QMC_EXTRA="-D..." in the environment adds flags (diagnostic builds such as
+-DQMC_SECTIONS or -DQMC_CUTS)."""
 import os
 import re
 import subprocess

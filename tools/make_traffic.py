@@ -45,9 +45,9 @@ def main(argv):
                               capture_output=True, text=True).stdout.strip()
     except OSError:
         head = ''
+    paths = sorted({arg.split(',')[1] for arg in argv})
     res = {'source': 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE / SQ_INSTS_* in '
-                     'separate passes (tools/profile.sh), profiles/'
-                     'r06_*_pmc_summary.txt',
+                     'separate passes (tools/profile.sh), ' + ', '.join(paths),
            'correction': 'read bytes = 2 x FETCH_SIZE x 1024 (gfx950 half-count '
                          'of coalesced reads), write bytes = WRITE_SIZE x 1024',
            'head': head}

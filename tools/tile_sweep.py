@@ -1,6 +1,6 @@
 """N = 512 stress (BASELINE.json configs[4]): throughput of the batch
 evaluation (log|psi|, energy, drift), the VMC step and the DMC step for the
-library / precision it runs under (development tool; tools/tile_sweep.sh).
+library / precision it runs under (development tool).
 usage: tile_sweep.py [--fast] [--tag T] [--walkers W]"""
 import argparse
 import os
