@@ -191,6 +191,41 @@ int qmc_engine_section_cut(qmc_engine *eng, int32_t section);
  * inside the same kernel, since the last reset.  n <= 4; synchronises. */
 int qmc_engine_diag_counters(qmc_engine *eng, uint64_t *out, int32_t n,
                              int32_t reset);
+/* Diagnostic: runs one device primitive of the shipped kernels
+ * (csrc/qmc_math.h, csrc/qmc_device.h; the kernel is csrc/qmc_probe.h) on n
+ * host inputs, with this engine's model constants and device tables, and
+ * returns its outputs (test-visible evidence of what the kernels compute; no
+ * reference counterpart).  in[n][in_width] -> out[n][out_width], widths per
+ * function below.  Inputs run in order, 64 to a wavefront: wrap_box and the
+ * trig-table load decide for a whole wavefront.  Integers (Philox words,
+ * counters, keys) travel as exact doubles.  Inputs no production caller can
+ * produce are refused: non-finite ones for every function, non-positive or
+ * non-normal ones to log_pos, positions outside (-4 L, 4 L) to the functions
+ * that read a model table; a model without the table asked for is an error.
+ * Synchronises. */
+enum {
+    QMC_PROBE_FAST_DIV = 0,        /* (x, y) -> x / y */
+    QMC_PROBE_PAIR_DIV = 1,        /* (x, y) -> x / y, pair-loop form */
+    QMC_PROBE_PAIR_DIV_F32 = 2,    /* (x, y) -> float pair_div of (float) x, y */
+    QMC_PROBE_FAST_RCP = 3,        /* y -> 1 / y */
+    QMC_PROBE_FAST_SQRT = 4,       /* x -> sqrt x */
+    QMC_PROBE_SINCOS_KERNEL = 5,   /* x -> (sin x, cos x), |x| <= pi/4 */
+    QMC_PROBE_SINCOS_HALFPI = 6,   /* u -> (sin, cos)(pi u / 2) */
+    QMC_PROBE_EXP_BOUNDED = 7,     /* x -> exp x */
+    QMC_PROBE_LOG_POS = 8,         /* x -> log x */
+    QMC_PROBE_WRAP_BOX = 9,        /* z -> z wrapped into [0, L) */
+    QMC_PROBE_TRIG_TAB = 10,       /* z -> (s, c, su, cu, ok) */
+    QMC_PROBE_ONE_BODY_TAB = 11,   /* z -> (f1'/f1, log f1, barrier) */
+    QMC_PROBE_ONE_BODY = 12,       /* z -> (f1'/f1, kin_pot, f1, xoff) */
+    QMC_PROBE_VMC_MOVE_UNIT = 13,  /* w -> (w + 1/2) 2^-32 - 1/2 */
+    QMC_PROBE_NORMAL2_WORDS = 14,  /* (w0, w1) -> (g0, g1) of dmc_normal2 */
+    QMC_PROBE_NORMAL2_UNIFORMS = 15, /* (u0, u1) -> (g0, g1) of philox_normal2 */
+    QMC_PROBE_PHILOX2X32 = 16,     /* (c0, c1, k) -> (c0', c1') */
+    QMC_PROBE_PHILOX4X32 = 17,     /* (c0..c3, k0, k1) -> (c0'..c3') */
+    QMC_PROBE_COUNT = 18
+};
+int qmc_engine_probe(qmc_engine *eng, int32_t fn, int64_t n, const double *in,
+                     double *out);
 
 /* Stands in for model.core_funcs.{wf_abs_log, energy, drift,
  * ith_energy_and_drift} (qmc_base/jastrow/model.py:298-366, 476-564, 756-773,

@@ -282,6 +282,19 @@ __device__ __forceinline__ double vmc_move_unit(uint32_t w0)
     return fma((double)w0, 0x1p-32, 0x1p-33 - 0.5);
 }
 
+// Box-Muller step of philox_normal2: the two normals of two 53-bit uniforms
+// u0, u1 in [0, 1) (qmc_probe.h runs it on its own).
+__device__ __forceinline__ void normal2_from_uniforms(double u0, double u1,
+                                                      double &g0, double &g1)
+{
+    // 1 - u0 is in (0, 1]: log <= 0
+    double r = fast_sqrt(fmax(-2.0 * log_pos(1.0 - u0), 1e-300));
+    double s, c;
+    sincos_halfpi(4.0 * u1, s, c);          // angle 2 pi u1
+    g0 = r * c;
+    g1 = r * s;
+}
+
 // Box-Muller pair from one Philox block: both standard normals.
 __device__ __forceinline__ void philox_normal2(uint64_t seed, uint32_t slot,
                                                uint32_t step, uint32_t index,
@@ -290,8 +303,19 @@ __device__ __forceinline__ void philox_normal2(uint64_t seed, uint32_t slot,
 {
     double u0, u1;
     philox_uniform2(seed, slot, step, index, stream, u0, u1);
-    // 1 - u0 is in (0, 1]: log <= 0
-    double r = fast_sqrt(fmax(-2.0 * log_pos(1.0 - u0), 1e-300));
+    normal2_from_uniforms(u0, u1, g0, g1);
+}
+
+// Box-Muller step of dmc_normal2: both normals of two Philox words
+// (qmc_probe.h runs it on its own).
+__device__ __forceinline__ void normal2_from_words(uint32_t w0, uint32_t w1,
+                                                   double &g0, double &g1)
+{
+    // (one conversion and one fused multiply-add each, exact)
+    const double u0 = fma((double)w0, 0x1p-32, 0x1p-33);
+    const double u1 = fma((double)w1, 0x1p-32, 0x1p-33);
+    // u0 <= 1 - 2^-33: the logarithm is < 0
+    const double r = fast_sqrt(-2.0 * log_pos(u0));
     double s, c;
     sincos_halfpi(4.0 * u1, s, c);          // angle 2 pi u1
     g0 = r * c;
@@ -318,15 +342,7 @@ __device__ __forceinline__ void dmc_normal2(uint64_t seed, uint32_t slot,
     uint32_t w0 = ((step2 & 0x3FFFFFFu) << 6) | ((slot >> 22) & 0x3Fu);
     uint32_t w1 = ((slot & 0x3FFFFFu) << 10) | (index & 0x3FFu);
     philox2x32_10(w0, w1, key);
-    // (one conversion and one fused multiply-add each, exact)
-    const double u0 = fma((double)w0, 0x1p-32, 0x1p-33);
-    const double u1 = fma((double)w1, 0x1p-32, 0x1p-33);
-    // u0 <= 1 - 2^-33: the logarithm is < 0
-    const double r = fast_sqrt(-2.0 * log_pos(u0));
-    double s, c;
-    sincos_halfpi(4.0 * u1, s, c);          // angle 2 pi u1
-    g0 = r * c;
-    g1 = r * s;
+    normal2_from_words(w0, w1, g0, g1);
 }
 
 // ------------------------------------------------------------ helpers ----
@@ -336,12 +352,21 @@ __device__ __forceinline__ void dmc_normal2(uint64_t seed, uint32_t slot,
 // The division runs only when some lane of the wavefront is further out; the
 // test is a ballot, so the branch is wave-uniform (a scalar branch, no exec
 // mask).  Same arithmetic as the nested form: the results are bit-identical.
+// Further out, r = z - n L with n = floor(z / L) in one rounding is the
+// reference's fmod-based result whenever n is right; the rounded quotient can
+// only overshoot (z / L just below an integer rounds up to it), and then r is
+// negative and the remainder by fmod is r + L exactly as the reference forms
+// it.  (Without that step a non-integer L gave a negative position:
+// z = -6.3 - ulp, L = 2.1 gave -4.4e-16 for the reference's 2.0999999999999996,
+// tests/test_gpu_device_math.py.)
 __device__ __forceinline__ double wrap_box(double z, double L)
 {
     double zw = (z < 0.0) ? z + L : (z >= L) ? z - L : z;
     const bool far = z < -L || z >= 2.0 * L;
-    if (__builtin_expect(__ballot(far) != 0ull, 0))
-        zw = far ? z - L * floor(z / L) : zw;
+    if (__builtin_expect(__ballot(far) != 0ull, 0)) {
+        const double r = fma(-L, floor(z / L), z);
+        zw = far ? (r < 0.0 ? r + L : r) : zw;
+    }
     return zw;
 }
 

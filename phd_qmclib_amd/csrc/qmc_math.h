@@ -6,7 +6,10 @@
 // reduction for the whole double range (Payne-Hanek), denormal/inf/nan paths
 // and IEEE-exact division; the arguments here are bounded (positions in
 // [0, L), angles of a few pi, |x| < 40 for exp) and finite, so these versions
-// keep only what those ranges need.  Accuracy: <= 2 ulp, checked on the GPU
+// keep only what those ranges need.  Accuracy: <= 2 ulp (exp_bounded 2.5,
+// pair_div 2.5e-15 relative), each function checked on the GPU against
+// 40-digit references at the edges of its domain
+// (tests/test_gpu_device_math.py, through qmc_engine_probe) and, end to end,
 // against the CPU oracle through the parity tests (2e-11 relative on every
 // energy / drift / log-psi).
 #pragma once
@@ -42,7 +45,8 @@ __device__ __forceinline__ double fast_div(double x, double y)
 }
 
 // Pair-loop quotient: reciprocal estimate + ONE quotient correction (4
-// instructions).  Relative error <= eps_rcp^2 + 2^-53 ~ 8e-16 (eps_rcp = 2^-25).
+// instructions).  Relative error ~ eps_rcp^2 + 2^-53: measured 1.86e-15 on
+// the MI355X (the hardware estimate is coarser than 2^-25), bound 2.5e-15.
 __device__ __forceinline__ double pair_div(double x, double y)
 {
     double r = __builtin_amdgcn_rcp(y);
@@ -139,6 +143,7 @@ __device__ __forceinline__ void sincos_halfpi(double u, double &s, double &c)
 
 // exp(x) for |x| < 700 (no overflow/denormal handling): n = rint(x / ln 2),
 // r = x - n ln2 (hi/lo split), degree-12 Taylor-minimax on |r| <= ln2/2.
+// Accuracy 2.5 ulp (measured worst 2.25 ulp, at x = -298.4).
 __device__ __forceinline__ double exp_bounded(double x)
 {
     const double INV_LN2 = 1.44269504088896338700e+00;

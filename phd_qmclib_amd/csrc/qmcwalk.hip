@@ -10,6 +10,7 @@
 #include "qmc_inst.h"
 #include "qmc_kernels_misc.h"
 #include "../../include/qmcwalk.h"
+#include "qmc_probe.h"
 
 #include <cmath>
 #include <cstdio>
@@ -484,6 +485,8 @@ static double ob_build_region(const DevModel &d, bool barrier, int m,
 }
 
 static double g_ob_last_err[2] = { 0.0, 0.0 };   // diagnostics (info call)
+// (checked at the builder's sample points; between them the device's rows
+// reach 3.2e-15, tests/test_gpu_device_math.py)
 static constexpr double OB_TOL = 2e-15;
 static constexpr int OB_MAX_ROWS = 1024;        // per region (128 KB)
 
@@ -617,6 +620,15 @@ static int engine_create_impl(const qmc_model_params *model, int device,
         return fail("qmc_engine_create: two-body parameters outside the "
                     "model's domain (need 0 < k2 rm < pi/2, 0 <= k2 r_off <= pi/2)");
     }
+    // the sorted-row pair sums (qmc_sorted64.h) count every pair quotient in
+    // units of a_long = (pi / L) beta: a non-ideal model with beta = 0 (which
+    // the reference's matching conditions never produce, mrbp_qmc/model.py:
+    // 255-274) would lose its short-range terms there without an error
+    if (!e->dm.is_ideal && !(e->dm.a_long != 0.0)) {
+        delete e;
+        return fail("qmc_engine_create: a non-ideal model needs "
+                    "param_beta != 0");
+    }
     HIP_TRY(hipSetDevice(device));
     if (caller_stream) {
         // the caller's stream as it is; NULL is the legacy default stream
@@ -738,7 +750,8 @@ static double log_pos_host(double x)
     const double LN2_LO = 1.90821492927058770002e-10;
     int k;
     const double m = frexp(x, &k);                         // [1/2, 1)
-    const int r = (int)fma(m, (double)(2 * QMC_LOG_ROWS), -(double)QMC_LOG_ROWS);
+    const int r = (int)fma(m, (double)(2 * QMC_LOG_ROWS), -(double)QMC_LOG_ROWS) &
+                  (QMC_LOG_ROWS - 1);                      // (as on the device)
     const double inv_c = g_log_tab_host[2 * r], L = g_log_tab_host[2 * r + 1];
     const double d = fma(m, inv_c, -1.0);
     double q = fma(d, 0.2, -0.25);
@@ -989,6 +1002,63 @@ static int dev_alloc(T **p, size_t count)
     *p = nullptr;
     if (count == 0) count = 1;
     HIP_TRY(hipMalloc((void **)p, count * sizeof(T)));
+    return 0;
+}
+
+// Diagnostic: one device primitive on host inputs (qmc_probe.h); synchronises.
+extern "C" int qmc_engine_probe(qmc_engine *e, int32_t fn, int64_t n,
+                                const double *in, double *out)
+{
+    if (!e) return fail("qmc_engine_probe: null engine");
+    int nin = 0, nout = 0;
+    qmc_probe_width(fn, nin, nout);
+    if (!nin) return fail("qmc_engine_probe: unknown function id");
+    if (n < 0 || n > (1ll << 24))
+        return fail("qmc_engine_probe: n must be in [0, 2^24]");
+    if (n == 0) return 0;
+    if (!in || !out) return fail("qmc_engine_probe: null argument");
+    const DevModel &d = e->dm;
+    const bool table = fn == QMC_PROBE_TRIG_TAB || fn == QMC_PROBE_ONE_BODY_TAB;
+    if (fn == QMC_PROBE_TRIG_TAB && !d.trig_table)
+        return fail("qmc_engine_probe: this model has no trig row table");
+    if (fn == QMC_PROBE_ONE_BODY_TAB && !d.ob_table)
+        return fail("qmc_engine_probe: this model has no one-body table");
+    if (fn == QMC_PROBE_ONE_BODY && d.is_free)
+        return fail("qmc_engine_probe: a free model has no one-body factor");
+    for (int64_t i = 0; i < n * nin; ++i) {
+        const double x = in[i];
+        if (!std::isfinite(x))
+            return fail("qmc_engine_probe: non-finite input");
+        if (fn == QMC_PROBE_LOG_POS && !(x >= 2.2250738585072014e-308))
+            return fail("qmc_engine_probe: log_pos takes positive normal "
+                        "numbers");
+        if (table && !(fabs(x) < 4.0 * d.L))
+            return fail("qmc_engine_probe: table positions must lie in "
+                        "(-4 L, 4 L)");
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    double *din = nullptr, *dout = nullptr;
+    if (dev_alloc(&din, (size_t)n * nin)) return 1;
+    if (dev_alloc(&dout, (size_t)n * nout)) {
+        hipFree(din);
+        return 1;
+    }
+    hipError_t rc = hipMemcpyAsync(din, in, (size_t)n * nin * sizeof(double),
+                                   hipMemcpyHostToDevice, e->stream);
+    if (rc == hipSuccess) {
+        hipLaunchKernelGGL(probe_kernel, dim3((unsigned)((n + 63) / 64)),
+                           dim3(64), 0, e->stream, e->dm_dev, (int)fn,
+                           (long long)n, din, dout, nin, nout);
+        rc = hipGetLastError();
+    }
+    if (rc == hipSuccess)
+        rc = hipMemcpyAsync(out, dout, (size_t)n * nout * sizeof(double),
+                            hipMemcpyDeviceToHost, e->stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);
+    hipFree(din);
+    hipFree(dout);
+    if (rc != hipSuccess)
+        return fail(std::string("qmc_engine_probe: ") + hipGetErrorString(rc));
     return 0;
 }
 

@@ -204,6 +204,32 @@ class ModelEngine:
         check(self._lib.qmc_engine_diag_counters(self._h, out, 4, int(reset)))
         return int(out[0])
 
+    # qmc_engine_probe function ids (include/qmcwalk.h QMC_PROBE_*): name ->
+    # (id, input width, output width)
+    PROBE_FUNCS = {
+        'fast_div': (0, 2, 1), 'pair_div': (1, 2, 1), 'pair_div_f32': (2, 2, 1),
+        'fast_rcp': (3, 1, 1), 'fast_sqrt': (4, 1, 1),
+        'sincos_kernel': (5, 1, 2), 'sincos_halfpi': (6, 1, 2),
+        'exp_bounded': (7, 1, 1), 'log_pos': (8, 1, 1), 'wrap_box': (9, 1, 1),
+        'trig_tab': (10, 1, 5), 'one_body_tab': (11, 1, 3),
+        'one_body': (12, 1, 4), 'vmc_move_unit': (13, 1, 1),
+        'normal2_words': (14, 2, 2), 'normal2_uniforms': (15, 2, 2),
+        'philox2x32': (16, 3, 2), 'philox4x32': (17, 6, 4),
+    }
+
+    def probe(self, fn: str, inputs) -> np.ndarray:
+        """Diagnostic: the device primitive `fn` of the shipped kernels on
+        `inputs` [n, in_width] (or [n] for one input) with this engine's
+        model and tables -> [n, out_width] (see qmc_engine_probe).  Inputs run
+        64 to a wavefront, in order."""
+        fid, nin, nout = self.PROBE_FUNCS[fn]
+        x = np.ascontiguousarray(np.asarray(inputs, dtype=np.float64)
+                                 .reshape(-1, nin))
+        out = np.empty((x.shape[0], nout))
+        check(self._lib.qmc_engine_probe(self._h, fid, x.shape[0],
+                                         ptr(x), ptr(out)))
+        return out
+
     def section_names(self):
         return [self._lib.qmc_section_name(i).decode() for i in range(16)]
 

@@ -83,6 +83,9 @@ def test_library_hash_is_the_hash_of_the_sources():
     csrc = os.path.join(os.path.dirname(_lib.__file__), 'csrc')
     mk = open(os.path.join(csrc, 'Makefile')).read()
     hdrs = re.search(r'^HDRS\s*:=\s*(.*)$', mk, re.M).group(1).split()
+    # every kernel header is hashed (a header left out would let a library
+    # built from other kernels pass as current)
+    assert {f for f in os.listdir(csrc) if f.endswith('.h')} <= set(hdrs)
     flags = re.search(r'^HIPFLAGS\s*\?=\s*(.*)$', mk, re.M).group(1)
     flags = flags.replace('$(ARCH)', 'gfx950')
     srcs = sorted(f for f in os.listdir(csrc) if f.endswith('.hip'))

@@ -34,6 +34,25 @@ def test_library_exports_every_declared_symbol():
     assert lib.qmc_abi_version() == 1
 
 
+def test_probe_ids_match_header():
+    """engine.ModelEngine.PROBE_FUNCS names every QMC_PROBE_* id of the header
+    (qmc_engine_probe) with the widths of csrc/qmc_probe.h."""
+    from phd_qmclib_amd.engine import ModelEngine
+    text = open(os.path.join(ROOT, 'include', 'qmcwalk.h')).read()
+    ids = {k.lower(): int(v) for k, v in
+           re.findall(r'\bQMC_PROBE_([A-Z0-9_]+)\s*=\s*(\d+)', text)}
+    count = ids.pop('count')
+    assert {k: v[0] for k, v in ModelEngine.PROBE_FUNCS.items()} == ids
+    assert sorted(ids.values()) == list(range(count))
+    src = open(os.path.join(ROOT, 'phd_qmclib_amd', 'csrc',
+                            'qmc_probe.h')).read()
+    for name, (_, nin, nout) in ModelEngine.PROBE_FUNCS.items():
+        case = re.search(r'QMC_PROBE_%s:[^;]*?nin = (\d); nout = (\d)'
+                         % name.upper(), src, re.S)
+        assert case and (int(case.group(1)), int(case.group(2))) == \
+            (nin, nout), name
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from phd_qmclib_amd import _lib
     monkeypatch.setattr(_lib, '_lib', None)
