@@ -240,6 +240,35 @@ int qmc_evaluate_dev(qmc_engine *eng, int64_t nconf, const double *pos_dev,
                      double *wf_dev, double *energy_dev, double *ith_dev,
                      double *drift_dev);
 
+/* One-body density matrix g1(s) (qmc_base/jastrow/model.py:859-965:
+ * core_funcs.ith_one_body_density / one_body_density; the batch front end is
+ * PhysicalFuncs.one_body_density, qmc_base/jastrow/model.py:1064-1087,
+ * mrbp_qmc/model.py:801-815) over a batch of configurations and a set of
+ * shifts: g1[nconf][nshift] and, when ith is not NULL, the per-particle terms
+ * ith[nconf][nshift][N] in the particle order of pos.  Any real shift and any
+ * position are accepted, as by the reference.  g1 is symmetric in the
+ * particles, ith follows the order of the row.  Always fp64:
+ * qmc_engine_set_fast_math does not apply (csrc/qmc_obdm.h).
+ * qmc_obdm: host buffers, synchronous; nshift < 1, a NULL pos / shifts / g1
+ * or a non-finite shift is an error. */
+int qmc_obdm(qmc_engine *eng, int64_t nconf, const double *pos, int32_t nshift,
+             const double *shifts, double *g1, double *ith);
+/* Same on device-resident buffers, asynchronous on the engine's stream.  The
+ * shifts are taken as given (a non-finite one gives non-finite output, no
+ * error). */
+int qmc_obdm_dev(qmc_engine *eng, int64_t nconf, const double *pos_dev,
+                 int32_t nshift, const double *shifts_dev, double *g1_dev,
+                 double *ith_dev);
+/* Weighted sums over the configurations, device buffers, asynchronous:
+ * sums_dev[nshift][2] = sum_c w_c g1_c(s), sum_c w_c g1_c(s)^2 and (unless
+ * NULL) wsum_dev[0] = sum_c w_c; w_dev = NULL means unit weights.  Fixed
+ * summation order: two calls give the same bits.  The per-configuration values
+ * live in an engine-owned scratch filled in tiles of 2^16 configurations. */
+int qmc_obdm_reduce_dev(qmc_engine *eng, int64_t nconf, const double *pos_dev,
+                        const double *w_dev, int32_t nshift,
+                        const double *shifts_dev, double *sums_dev,
+                        double *wsum_dev);
+
 /* Plain device buffers, so that a configuration set can stay resident across
  * many qmc_evaluate_dev calls with different engines: the correlated-sampling
  * optimiser re-evaluates wf_abs_log / energy of one fixed set for every trial
@@ -282,6 +311,12 @@ int qmc_vmc_state_dev(qmc_vmc *v, double **pos, double **wf);
  * qmc_base/jastrow/vmc.py:304-351, evaluated for a whole ensemble in one
  * launch).  Host buffer; synchronous. */
 int qmc_vmc_ssf(qmc_vmc *v, int32_t num_modes, double *out);
+/* One-body density matrix parts of the CURRENT configurations summed over the
+ * chains: out[nshift][2] = sum_w g1_w(s), sum_w g1_w(s)^2 (the quantity of
+ * qmc_base/jastrow/model.py:932-965 for a whole ensemble, on the resident rows;
+ * no position leaves the device).  Host buffers; synchronous; shifts checked
+ * as by qmc_obdm. */
+int qmc_vmc_obdm(qmc_vmc *v, int32_t nshift, const double *shifts, double *out);
 /* Device addresses of the per-chain block sums of the last block
  * (sum_e[W], sum_e2[W], n_acc[W]) for on-device reductions / collectives. */
 int qmc_vmc_block_sums_dev(qmc_vmc *v, double **sum_e, double **sum_e2,

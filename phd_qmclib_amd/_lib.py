@@ -95,6 +95,11 @@ SIGNATURES = {
     'qmc_engine_timer_stop': (C.c_int, [_vp, C.POINTER(C.c_float)]),
     'qmc_evaluate': (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp, _dp, _dp]),
     'qmc_evaluate_dev': (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    'qmc_obdm': (C.c_int, [_vp, C.c_int64, _dp, C.c_int32, _dp, _dp, _dp]),
+    'qmc_obdm_dev': (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp, _vp,
+                               _vp]),
+    'qmc_obdm_reduce_dev': (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int32,
+                                      _vp, _vp, _vp]),
     'qmc_buffer_alloc': (C.c_int, [C.c_int, C.c_size_t, C.POINTER(_vp)]),
     'qmc_buffer_free': (C.c_int, [_vp]),
     'qmc_buffer_upload': (C.c_int, [_vp, _vp, C.c_size_t]),
@@ -104,6 +109,7 @@ SIGNATURES = {
     'qmc_vmc_set_state': (C.c_int, [_vp, _dp]),
     'qmc_vmc_get_state': (C.c_int, [_vp, _dp, _dp, _dp]),
     'qmc_vmc_ssf': (C.c_int, [_vp, C.c_int32, _dp]),
+    'qmc_vmc_obdm': (C.c_int, [_vp, C.c_int32, _dp, _dp]),
     'qmc_vmc_run_block': (C.c_int, [_vp, C.c_int64, _dp, _dp, _i64p, _dp, _dp,
                                     _u8p, _dp]),
     'qmc_vmc_state_dev': (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),

@@ -9,6 +9,7 @@
 // population buffers (parents / children) that swap roles every time step.
 #include "qmc_inst.h"
 #include "qmc_kernels_misc.h"
+#include "qmc_obdm.h"
 #include "../../include/qmcwalk.h"
 #include "qmc_probe.h"
 
@@ -69,6 +70,10 @@ struct qmc_engine {
     std::vector<hipEvent_t> prof_ev;
     size_t prof_used = 0;
     bool prof_on = false;
+    // one-body density matrix scratch (qmc_obdm*): the shift table and the
+    // per-configuration tile g1[tile][nshift], grown on demand
+    double *obdm_stab = nullptr, *obdm_g1 = nullptr, *obdm_sums = nullptr;
+    size_t obdm_stab_cap = 0, obdm_g1_cap = 0, obdm_sums_cap = 0;
 };
 
 // Bracket a launch of the dominant kernel with an event pair while a profile
@@ -966,6 +971,9 @@ extern "C" void qmc_engine_destroy(qmc_engine *e)
     if (e->trig_table_dev) hipFree(e->trig_table_dev);
     if (e->sec_prof_dev) hipFree(e->sec_prof_dev);
     if (e->diag_dev) hipFree(e->diag_dev);
+    if (e->obdm_stab) hipFree(e->obdm_stab);
+    if (e->obdm_g1) hipFree(e->obdm_g1);
+    if (e->obdm_sums) hipFree(e->obdm_sums);
     if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
     delete e;
 }
@@ -1351,6 +1359,203 @@ extern "C" int qmc_vmc_ssf(qmc_vmc *v, int32_t num_modes, double *out)
     HIP_TRY(hipStreamSynchronize(e->stream));
     return 0;
 }
+
+// ---- one-body density matrix (csrc/qmc_obdm.h) --------------------------
+// Configurations per launch where the entry point owns the [nconf][nshift]
+// scratch: 2^16 configurations of 64 shifts are 32 MB (2^20 chains at once
+// would be 512 MB); tiles run one after the other on the stream and the
+// reduction adds them up in tile order.
+static constexpr long long OBDM_TILE = 1ll << 16;
+// Doubles of per-configuration output (g1 and, when asked for, ith) that
+// qmc_obdm keeps on the device at a time (128 MB).
+static constexpr long long OBDM_HOST_TILE_DOUBLES = 1ll << 24;
+
+static int obdm_reserve(double **buf, size_t *cap, size_t count)
+{
+    if (count <= *cap) return 0;
+    if (*buf) { hipFree(*buf); *buf = nullptr; *cap = 0; }
+    if (dev_alloc(buf, count)) return 1;
+    *cap = count;
+    return 0;
+}
+
+// shift table of a set of device-resident shifts, on the engine's stream
+static int obdm_make_shift_table(qmc_engine *e, int32_t nshift,
+                                 const double *shifts_dev)
+{
+    if (obdm_reserve(&e->obdm_stab, &e->obdm_stab_cap,
+                     (size_t)nshift * OBDM_SROW))
+        return 1;
+    hipLaunchKernelGGL(obdm_shift_kernel, dim3((nshift + 63) / 64), dim3(64),
+                       0, e->stream, e->dm_dev, shifts_dev, (int)nshift,
+                       e->obdm_stab);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// g1 (and ith) of nconf configurations against the engine's shift table
+static int obdm_launch(qmc_engine *e, long long nconf, const double *pos_dev,
+                       int32_t nshift, double *g1_dev, double *ith_dev)
+{
+    if (nconf <= 0) return 0;
+    const int n = e->dm.n;
+    int G = 64;
+    if (n <= 8) G = 8; else if (n <= 16) G = 16; else if (n <= 32) G = 32;
+    const int unit = (64 / G) * OBDM_U;       // shifts of one wavefront pass
+    // shifts per wavefront: all of them once the batch alone fills the chip
+    // (the unshifted rows are computed once per wavefront), fewer for a small
+    // batch; the grid's second dimension holds at most 65535 chunks
+    long long chunks = std::max(1ll, std::min<long long>(
+        (nshift + unit - 1) / unit, 8192 / nconf));
+    int chunk = (int)((nshift + chunks - 1) / chunks);
+    chunk = ((chunk + unit - 1) / unit) * unit;
+    chunk = std::max(chunk, (nshift + 65534) / 65535);
+    const unsigned ny = (unsigned)((nshift + chunk - 1) / chunk);
+    const size_t lds = (size_t)n * OBDM_LDS_PER_PARTICLE * sizeof(double);
+    // a grid's first dimension holds 2^31 - 1 blocks
+    const long long XMAX = 1ll << 30;
+    for (long long c0 = 0; c0 < nconf; c0 += XMAX) {
+        const long long nc = std::min(XMAX, nconf - c0);
+        ObdmArgs a{ pos_dev + (size_t)c0 * n, e->obdm_stab,
+                    g1_dev + (size_t)c0 * nshift,
+                    ith_dev ? ith_dev + (size_t)c0 * nshift * n : nullptr, nc,
+                    (int)nshift, chunk };
+        const dim3 grid((unsigned)nc, ny);
+        switch (G) {
+        case 8: hipLaunchKernelGGL(obdm_kernel<8>, grid, dim3(64), lds, e->stream, e->dm_dev, a); break;
+        case 16: hipLaunchKernelGGL(obdm_kernel<16>, grid, dim3(64), lds, e->stream, e->dm_dev, a); break;
+        case 32: hipLaunchKernelGGL(obdm_kernel<32>, grid, dim3(64), lds, e->stream, e->dm_dev, a); break;
+        default: hipLaunchKernelGGL(obdm_kernel<64>, grid, dim3(64), lds, e->stream, e->dm_dev, a); break;
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int qmc_obdm_dev(qmc_engine *e, int64_t nconf, const double *pos,
+                            int32_t nshift, const double *shifts, double *g1,
+                            double *ith)
+{
+    if (!e || !pos || !shifts || !g1)
+        return fail("qmc_obdm_dev: null argument");
+    if (nshift < 1) return fail("qmc_obdm_dev: nshift < 1");
+    if (nconf < 0) return fail("qmc_obdm_dev: nconf < 0");
+    HIP_TRY(hipSetDevice(e->device));
+    if (obdm_make_shift_table(e, nshift, shifts)) return 1;
+    return obdm_launch(e, nconf, pos, nshift, g1, ith);
+}
+
+extern "C" int qmc_obdm_reduce_dev(qmc_engine *e, int64_t nconf,
+                                   const double *pos, const double *w,
+                                   int32_t nshift, const double *shifts,
+                                   double *sums, double *wsum)
+{
+    if (!e || !pos || !shifts || !sums)
+        return fail("qmc_obdm_reduce_dev: null argument");
+    if (nshift < 1) return fail("qmc_obdm_reduce_dev: nshift < 1");
+    if (nconf < 0) return fail("qmc_obdm_reduce_dev: nconf < 0");
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n = (size_t)e->dm.n;
+    const long long tile = std::min<long long>(std::max<long long>(nconf, 1),
+                                               OBDM_TILE);
+    if (obdm_make_shift_table(e, nshift, shifts) ||
+        obdm_reserve(&e->obdm_g1, &e->obdm_g1_cap, (size_t)tile * nshift))
+        return 1;
+    long long c0 = 0;
+    do {
+        const long long nc = std::min(tile, (long long)nconf - c0);
+        if (obdm_launch(e, nc, pos + (size_t)c0 * n, nshift, e->obdm_g1,
+                        nullptr))
+            return 1;
+        hipLaunchKernelGGL(obdm_reduce_kernel, dim3(nshift + 1), dim3(256), 0,
+                           e->stream, e->obdm_g1, w ? w + c0 : nullptr, nc,
+                           (int)nshift, c0 > 0 ? 1 : 0, sums, wsum);
+        HIP_TRY(hipGetLastError());
+        c0 += tile;
+    } while (c0 < nconf);
+    return 0;
+}
+
+static int obdm_check_host_shifts(const char *who, int32_t nshift,
+                                  const double *shifts)
+{
+    if (nshift < 1) return fail(std::string(who) + ": nshift < 1");
+    if (!shifts) return fail(std::string(who) + ": null argument");
+    for (int32_t k = 0; k < nshift; ++k)
+        if (!std::isfinite(shifts[k]))
+            return fail(std::string(who) + ": shift " + std::to_string(k) +
+                        " is not finite");
+    return 0;
+}
+
+extern "C" int qmc_obdm(qmc_engine *e, int64_t nconf, const double *pos,
+                        int32_t nshift, const double *shifts, double *g1,
+                        double *ith)
+{
+    if (!e || !pos || !g1) return fail("qmc_obdm: null argument");
+    if (obdm_check_host_shifts("qmc_obdm", nshift, shifts)) return 1;
+    if (nconf < 0) return fail("qmc_obdm: nconf < 0");
+    if (nconf == 0) return 0;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n = (size_t)e->dm.n, M = (size_t)nshift;
+    const size_t per_conf = M * (ith ? n + 1 : 1);
+    const long long tile = std::max<long long>(
+        1, std::min<long long>(nconf, OBDM_HOST_TILE_DOUBLES / (long long)per_conf));
+    double *dsh = nullptr, *dpos = nullptr, *dg1 = nullptr, *dith = nullptr;
+    int rc = dev_alloc(&dsh, M) || dev_alloc(&dpos, (size_t)tile * n) ||
+             dev_alloc(&dg1, (size_t)tile * M) ||
+             (ith && dev_alloc(&dith, (size_t)tile * M * n));
+    auto run = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(dsh, shifts, M * sizeof(double),
+                               hipMemcpyHostToDevice, e->stream));
+        if (obdm_make_shift_table(e, nshift, dsh)) return 1;
+        for (long long c0 = 0; c0 < nconf; c0 += tile) {
+            const size_t nc = (size_t)std::min(tile, (long long)nconf - c0);
+            HIP_TRY(hipMemcpyAsync(dpos, pos + (size_t)c0 * n,
+                                   nc * n * sizeof(double),
+                                   hipMemcpyHostToDevice, e->stream));
+            if (obdm_launch(e, (long long)nc, dpos, nshift, dg1, dith))
+                return 1;
+            HIP_TRY(hipMemcpyAsync(g1 + (size_t)c0 * M, dg1,
+                                   nc * M * sizeof(double),
+                                   hipMemcpyDeviceToHost, e->stream));
+            if (ith)
+                HIP_TRY(hipMemcpyAsync(ith + (size_t)c0 * M * n, dith,
+                                       nc * M * n * sizeof(double),
+                                       hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+        }
+        return 0;
+    };
+    if (!rc) rc = run();
+    hipFree(dsh); hipFree(dpos); hipFree(dg1); hipFree(dith);
+    return rc;
+}
+
+// g1 parts of the CURRENT configurations of the chains, summed over the
+// chains: the resident, position-sorted rows go to the kernel as they are (g1
+// is symmetric in the particles).
+extern "C" int qmc_vmc_obdm(qmc_vmc *v, int32_t nshift, const double *shifts,
+                            double *out)
+{
+    if (!v || !out) return fail("qmc_vmc_obdm: null argument");
+    if (obdm_check_host_shifts("qmc_vmc_obdm", nshift, shifts)) return 1;
+    qmc_engine *e = v->eng;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t M = (size_t)nshift;
+    if (obdm_reserve(&e->obdm_sums, &e->obdm_sums_cap, 3 * M)) return 1;
+    double *dsh = e->obdm_sums + 2 * M;
+    HIP_TRY(hipMemcpyAsync(dsh, shifts, M * sizeof(double),
+                           hipMemcpyHostToDevice, e->stream));
+    int rc = qmc_obdm_reduce_dev(e, v->W, v->pos, nullptr, nshift, dsh,
+                                 e->obdm_sums, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, e->obdm_sums, 2 * M * sizeof(double),
+                           hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
 
 extern "C" int qmc_vmc_block_sums_dev(qmc_vmc *v, double **se, double **se2,
                                       int64_t **na)

@@ -275,6 +275,70 @@ class ModelEngine:
         check(self._lib.qmc_evaluate_dev(self._h, int(nconf), pos_ptr, wf_ptr,
                                          energy_ptr, ith_ptr, drift_ptr))
 
+    def _shifts(self, shifts):
+        sh = np.ascontiguousarray(shifts, dtype=np.float64)
+        if sh.ndim != 1 or sh.size < 1:
+            raise ValueError('shifts must be a non-empty 1-d array')
+        return sh
+
+    def one_body_density(self, pos, shifts, ith: bool = False):
+        """One-body density matrix g1(s) of every configuration in pos[W, N]
+        for every shift -> g1[W, nshift]; with ith=True also the per-particle
+        terms -> (g1, ith[W, nshift, N])."""
+        pos = np.ascontiguousarray(pos, dtype=np.float64)
+        if pos.ndim != 2 or pos.shape[1] != self.num_particles:
+            raise ValueError('pos must have shape (W, boson_number)')
+        sh = self._shifts(shifts)
+        W, n = pos.shape
+        g1 = np.zeros((W, sh.size))
+        parts = np.zeros((W, sh.size, n)) if ith else None
+        check(self._lib.qmc_obdm(self._h, W, ptr(pos), sh.size, ptr(sh),
+                                 ptr(g1), ptr(parts)))
+        return (g1, parts) if ith else g1
+
+    def one_body_density_dev(self, nconf, pos_ptr, nshift, shifts_ptr, g1_ptr,
+                             ith_ptr=0):
+        """Asynchronous g1 on device-resident buffers (raw pointers):
+        pos[nconf, N], shifts[nshift] -> g1[nconf, nshift] and, unless 0,
+        ith[nconf, nshift, N]."""
+        check(self._lib.qmc_obdm_dev(self._h, int(nconf), pos_ptr, int(nshift),
+                                     shifts_ptr, g1_ptr, ith_ptr))
+
+    def one_body_density_reduce_dev(self, nconf, pos_ptr, w_ptr, nshift,
+                                    shifts_ptr, sums_ptr, wsum_ptr=0):
+        """Asynchronous weighted sums over the configurations, device buffers:
+        sums[nshift, 2] = sum_c w_c g1_c, sum_c w_c g1_c^2 and wsum[0] =
+        sum_c w_c (w_ptr = 0: unit weights), in a fixed summation order."""
+        check(self._lib.qmc_obdm_reduce_dev(self._h, int(nconf), pos_ptr,
+                                            w_ptr, int(nshift), shifts_ptr,
+                                            sums_ptr, wsum_ptr))
+
+    def one_body_density_weighted(self, pos, weights, shifts):
+        """sum_c w_c g1_c(s) / sum_c w_c over the configurations pos[W, N]
+        (one upload of the positions, the weighted reduction on the device)
+        -> g1[nshift]."""
+        pos = np.ascontiguousarray(pos, dtype=np.float64)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        sh = self._shifts(shifts)
+        if pos.ndim != 2 or pos.shape[1] != self.num_particles \
+                or w.shape != (pos.shape[0],):
+            raise ValueError('pos[W, boson_number] and weights[W] expected')
+        bufs = [DeviceBuffer(pos.shape, self.device).upload(pos),
+                DeviceBuffer(w.shape, self.device).upload(w),
+                DeviceBuffer(sh.shape, self.device).upload(sh),
+                DeviceBuffer((sh.size, 2), self.device),
+                DeviceBuffer((1,), self.device)]
+        try:
+            self.one_body_density_reduce_dev(pos.shape[0], bufs[0].ptr,
+                                             bufs[1].ptr, sh.size, bufs[2].ptr,
+                                             bufs[3].ptr, bufs[4].ptr)
+            self.sync()
+            sums, wsum = bufs[3].download(), bufs[4].download()
+        finally:
+            for b in bufs:
+                b.close()
+        return sums[:, 0] / wsum[0]
+
 
 class VmcEnsemble:
     """W independent Metropolis chains resident on the GPU (qmc_vmc)."""
@@ -317,6 +381,14 @@ class VmcEnsemble:
         out = np.zeros((int(num_modes), 3))
         check(self._lib.qmc_vmc_ssf(self._h, int(num_modes), ptr(out)))
         return out / self.num_chains
+
+    def obdm_parts(self, shifts) -> np.ndarray:
+        """Sums over the chains of g1(s) and g1(s)^2 of the current
+        configurations -> [nshift, 2]; computed on the resident rows."""
+        sh = self.engine._shifts(shifts)
+        out = np.zeros((sh.size, 2))
+        check(self._lib.qmc_vmc_obdm(self._h, sh.size, ptr(sh), ptr(out)))
+        return out
 
     def get_state(self):
         """-> (pos[W, N], wf_abs_log[W], energy_carry[W])"""

@@ -342,6 +342,20 @@ class Sampling:
             ens.close()
             eng.close()
 
+    def one_body_density(self, state: State, shifts):
+        """Mixed estimate of the one-body density matrix over the live walkers
+        of a State: sum_w W_w g1_w(s) / sum_w W_w (g1 of
+        qmc_base/jastrow/model.py:932-965 per walker).  The positions of the
+        `num_walkers` live walkers are uploaded once; the weighted reduction
+        runs on the device -> g1[nshift]."""
+        nw = int(state.num_walkers)
+        confs = np.asarray(state.confs, dtype=np.float64)
+        pos = confs[:nw, model.SysConfSlot.pos, :]
+        weight = np.asarray(state.props.weight, dtype=np.float64)[:nw]
+        eng = model.core_funcs._engine(*self.model_spec.cfc_spec)
+        return eng.one_body_density_weighted(pos, weight, shifts)
+
+
     @property
     def ssf_momenta(self):
         if self.ssf_est_spec is None:

@@ -21,7 +21,7 @@ from .. import ideal
 
 __all__ = ['CSWFOptimizer', 'CFCSpec', 'OBFParams', 'Params', 'Spec', 'TBFParams',
            'SysConfSlot', 'SysConfDistType', 'DIST_RAND', 'DIST_REGULAR',
-           'core_funcs']
+           'core_funcs', 'PhysicalFuncs']
 
 import enum
 
@@ -335,7 +335,114 @@ class _CoreFuncs:
                                          obf_params, tbf_params)[1]
 
 
+    def ith_one_body_density(self, i_, sz, sys_conf, model_params, obf_params,
+                             tbf_params):
+        """The term of particle `i_` in the one-body density matrix at the
+        shift `sz` (qmc_base/jastrow/model.py:859-930)."""
+        sys_conf = np.asarray(sys_conf, dtype=np.float64)
+        eng = self._engine(model_params, obf_params, tbf_params)
+        _, ith = eng.one_body_density(
+            sys_conf[SysConfSlot.pos][np.newaxis, :], [float(sz)], ith=True)
+        return float(ith[0, 0, i_])
+
+    def one_body_density(self, sz, sys_conf, model_params, obf_params,
+                         tbf_params):
+        """One-body density matrix g1(sz) of one configuration
+        (qmc_base/jastrow/model.py:932-965)."""
+        sys_conf = np.asarray(sys_conf, dtype=np.float64)
+        eng = self._engine(model_params, obf_params, tbf_params)
+        g1 = eng.one_body_density(sys_conf[SysConfSlot.pos][np.newaxis, :],
+                                  [float(sz)])
+        return float(g1[0, 0])
+
+
 core_funcs = _CoreFuncs()
+
+
+@attr.s(auto_attribs=True, frozen=True)
+class PhysicalFuncs:
+    """Functions to calculate the main physical properties of the model over
+    batches of configurations (reference: qmc_base/jastrow/model.py:1007-1122,
+    mrbp_qmc/model.py:801-815).  The members broadcast as the reference's
+    generalised ufuncs do:
+
+        wf_abs_log(sys_conf)              (ns,nop)->()
+        energy(sys_conf)                  (ns,nop)->()
+        one_body_density(sz, sys_conf)    (),(ns,nop)->()
+        fourier_density(kz_set, sys_conf) (nkz),(ns,nop)->(nkz)   complex
+
+    The loop dimensions broadcast as NumPy's; the whole broadcast batch goes to
+    the device in one call (one call per distinct set of shifts for
+    `one_body_density`).  `fourier_density` is N nkz sines and cosines per
+    configuration and stays on the host in NumPy.  Nothing touches the GPU
+    until a member is called."""
+
+    cfc_spec_nt: CFCSpec
+
+    @classmethod
+    def from_model_spec(cls, model_spec: Spec):
+        """Builds the functions for the given model Spec."""
+        return cls(model_spec.cfc_spec)
+
+    @property
+    def core_funcs(self):
+        """The core functions of the model."""
+        return core_funcs
+
+    def _engine(self):
+        return core_funcs._engine(*self.cfc_spec_nt)
+
+    @staticmethod
+    def _conf_batch(sys_conf):
+        """sys_conf[..., ns, nop] -> (loop shape, pos[nconf, nop])."""
+        sys_conf = np.asarray(sys_conf, dtype=np.float64)
+        if sys_conf.ndim < 2:
+            raise ValueError('sys_conf must have the core shape (ns, nop)')
+        pos = sys_conf[..., SysConfSlot.pos, :]
+        return pos.shape[:-1], pos.reshape(-1, pos.shape[-1])
+
+    def wf_abs_log(self, sys_conf):
+        """Logarithm of the absolute value of the trial wave function."""
+        loop, pos = self._conf_batch(sys_conf)
+        out = self._engine().evaluate(pos).wf_abs_log
+        return out.reshape(loop)[()]
+
+    def energy(self, sys_conf):
+        """Local energy."""
+        loop, pos = self._conf_batch(sys_conf)
+        out = self._engine().evaluate(pos).energy
+        return out.reshape(loop)[()]
+
+    def one_body_density(self, sz, sys_conf):
+        """One-body density matrix."""
+        sz = np.asarray(sz, dtype=np.float64)
+        loop_c, pos = self._conf_batch(sys_conf)
+        loop = np.broadcast_shapes(sz.shape, loop_c)
+        # the distinct (shift, configuration) index pairs of the broadcast
+        # batch: shifts x configurations evaluated once, then gathered
+        sz_idx = np.broadcast_to(
+            np.arange(sz.size).reshape(sz.shape), loop)
+        conf_idx = np.broadcast_to(
+            np.arange(pos.shape[0]).reshape(loop_c), loop)
+        shifts, inv = np.unique(sz.reshape(-1), return_inverse=True)
+        g1 = self._engine().one_body_density(pos, shifts)
+        out = g1[conf_idx, inv.reshape(-1)[sz_idx]]
+        return out[()]
+
+    def fourier_density(self, kz_set, sys_conf):
+        """Fourier density component with momentum k: sum_i exp(i k z_i)."""
+        kz_set = np.asarray(kz_set, dtype=np.float64)
+        if kz_set.ndim < 1:
+            raise ValueError('kz_set must have the core shape (nkz,)')
+        sys_conf = np.asarray(sys_conf, dtype=np.float64)
+        if sys_conf.ndim < 2:
+            raise ValueError('sys_conf must have the core shape (ns, nop)')
+        pos = sys_conf[..., SysConfSlot.pos, :]
+        loop = np.broadcast_shapes(kz_set.shape[:-1], pos.shape[:-1])
+        kz = np.broadcast_to(kz_set, loop + kz_set.shape[-1:])
+        z = np.broadcast_to(pos, loop + pos.shape[-1:])
+        ang = kz[..., :, np.newaxis] * z[..., np.newaxis, :]
+        return np.cos(ang).sum(axis=-1) + 1j * np.sin(ang).sum(axis=-1)
 
 
 class CSWFOptimizer:

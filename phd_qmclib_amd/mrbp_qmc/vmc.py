@@ -303,6 +303,19 @@ class EnsembleSampling:
         ssf = (parts[:, 0] - parts[:, 1] ** 2 - parts[:, 2] ** 2) / n
         return np.arange(int(num_modes)) * 2 * pi / L, ssf
 
+    def one_body_density(self, shifts):
+        """One-body density matrix g1(s) over the chains' current
+        configurations -> (shifts, mean, stderr); computed on the rows resident
+        on the device (no position is copied to the host).  The standard error
+        is that of the mean over the chains."""
+        shifts = np.ascontiguousarray(shifts, dtype=np.float64)
+        parts = self.ensemble.obdm_parts(shifts)
+        w = self.num_chains
+        mean = parts[:, 0] / w
+        var = np.maximum(parts[:, 1] / w - mean ** 2, 0.0)
+        stderr = np.sqrt(var / max(w - 1, 1))
+        return shifts, mean, stderr
+
     def close(self):
         self.ensemble.close()
         self.engine.close()
