@@ -18,7 +18,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 // --------------------------------------------------------------- errors ---
@@ -36,6 +38,41 @@ static int fail(const std::string &msg)
         if (_e != hipSuccess)                                                \
             return fail(std::string(#expr) + ": " + hipGetErrorString(_e));  \
     } while (0)
+
+// One hipMalloc allocation of T, freed with its owner: the members of the
+// handles below and the temporaries of an entry point.  hipFree synchronises
+// the device, so a temporary is declared where it may die: at the scope of the
+// entry point, never inside a step loop.
+template <typename T>
+class DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    // `count` elements in place of what it holds (an empty series: one)
+    int alloc(size_t count)
+    {
+        release();
+        if (count == 0) count = 1;
+        HIP_TRY(hipMalloc((void **)&p, count * sizeof(T)));
+        cap = count;
+        return 0;
+    }
+    // grow-only: at least `count` elements; the contents do not survive growth
+    int reserve(size_t count) { return count <= cap ? 0 : alloc(count); }
+    T *get() const { return p; }
+    operator T *() const { return p; }
+};
 
 extern "C" const char *qmc_last_error(void) { return g_err.c_str(); }
 extern "C" int qmc_abi_version(void) { return QMCWALK_ABI_VERSION; }
@@ -55,11 +92,11 @@ struct qmc_engine {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     DevModel dm;
-    DevModel *dm_dev = nullptr;
-    double *ob_table_dev = nullptr;     // one-body table rows (or null)
-    double *trig_table_dev = nullptr;   // pair-angle row table (or null)
-    unsigned long long *sec_prof_dev = nullptr;  // QMC_TIMING builds only
-    unsigned long long *diag_dev = nullptr;      // DevModel::diag (QMC_NDIAG)
+    DevBuf<DevModel> dm_dev;
+    DevBuf<double> ob_table_dev;        // one-body table rows (or null)
+    DevBuf<double> trig_table_dev;      // pair-angle row table (or null)
+    DevBuf<unsigned long long> sec_prof_dev;     // QMC_TIMING builds only
+    DevBuf<unsigned long long> diag_dev;         // DevModel::diag (QMC_NDIAG)
     qmc_model_params mp;
     int G = 64, P = 1;
     bool pad = false;
@@ -72,8 +109,19 @@ struct qmc_engine {
     bool prof_on = false;
     // one-body density matrix scratch (qmc_obdm*): the shift table and the
     // per-configuration tile g1[tile][nshift], grown on demand
-    double *obdm_stab = nullptr, *obdm_g1 = nullptr, *obdm_sums = nullptr;
-    size_t obdm_stab_cap = 0, obdm_g1_cap = 0, obdm_sums_cap = 0;
+    DevBuf<double> obdm_stab, obdm_g1, obdm_sums;
+
+    qmc_engine() = default;
+    qmc_engine(const qmc_engine &) = delete;
+    // (with the engine's device current, as every entry point makes it; the
+    // buffers go after this body)
+    ~qmc_engine()
+    {
+        for (hipEvent_t ev : prof_ev) (void)hipEventDestroy(ev);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
 };
 
 // Bracket a launch of the dominant kernel with an event pair while a profile
@@ -104,13 +152,12 @@ static int pick_shape(int n, int &G, int &P, bool &pad)
     if (const char *env = getenv("QMCWALK_SHAPE")) {
         int g = 0, p = 0;
         if (sscanf(env, "%d,%d", &g, &p) == 2 && n <= g * p) {
-            static const int ok[][2] = { {16, 1}, {16, 2}, {32, 2}, {64, 1},
-                                         {64, 2}, {64, 4}, {64, 8} };
-            for (auto &s : ok)
-                if (s[0] == g && s[1] == p) {
-                    G = g; P = p; pad = (n != G * P);
-                    return 0;
-                }
+#define QMC_LEGAL(sg, sp) || (g == sg && p == sp)
+            if (false QMC_FOR_ALL_SHAPES(QMC_LEGAL)) {
+                G = g; P = p; pad = (n != G * P);
+                return 0;
+            }
+#undef QMC_LEGAL
         }
     }
     if (n <= 16) { G = 16; P = 1; }
@@ -130,23 +177,27 @@ QMC_FOR_ALL_TUS(QMC_EXTERN_TU)
 #undef QMC_EXTERN_TU
 
 // ------------------------------------------------------------ dispatch ----
+// The masked variant is also the leaner one in registers (its per-pair guards
+// stop the compiler from keeping several pairs in flight: 110-160 VGPRs
+// against 134-282 at P = 4, 8), and occupancy is what the large shapes lack:
+// from this P on every kernel family runs it whether the model fills the shape
+// or not (and the unmasked variants never launched are not instantiated,
+// qmc_inst.h).
+// (P = 8: the unmasked dmc_evolve needs 253 registers and ran 1.7x slower,
+// profiles/r02_n512_tile_sweep.txt)
+static constexpr int MASK_FROM_P = 4;
+
 template <template <int, int, bool, bool> class L, typename... A>
 static int dispatch_shape(const qmc_engine *e, A &&...args)
 {
     const bool zc = e->dm.zclass != 0;
-    // The masked variant is also the leaner one in registers (its per-pair
-    // guards stop the compiler from keeping several pairs in flight: 110-160
-    // VGPRs against 134-282 at P = 4, 8), and occupancy is what the large
-    // shapes lack; each kernel family says from which P it wants it (and the
-    // unmasked variants it never launches are not instantiated, qmc_inst.h).
 #define QMC_CASE(g, p)                                                        \
     if (e->G == g && e->P == p) {                                             \
-        constexpr bool always = L<g, p, true, false>::want_mask(p);           \
-        if (always || e->pad) {                                               \
+        if (p >= MASK_FROM_P || e->pad) {                                     \
             if (zc) return L<g, p, true, true>::run(e, args...);              \
             return L<g, p, true, false>::run(e, args...);                     \
         }                                                                     \
-        if constexpr (!always) {                                              \
+        if constexpr (p < MASK_FROM_P) {                                      \
             if (zc) return L<g, p, false, true>::run(e, args...);             \
             return L<g, p, false, false>::run(e, args...);                    \
         }                                                                     \
@@ -191,86 +242,63 @@ static unsigned grid_for(long long nwalkers)
     return (unsigned)blocks;
 }
 
+// The one place that launches a walker kernel: lane groups of G for `nwalkers`
+// walkers, on the engine's stream, with the model constants.
+template <int G, typename A>
+static int launch_walkers(const qmc_engine *e,
+                          void (*kernel)(const DevModel *, A), size_t lds,
+                          long long nwalkers, const A &a)
+{
+    allow_lds(kernel, lds);
+    hipLaunchKernelGGL(kernel, dim3(grid_for<G>(nwalkers)),
+                       dim3(WalkBlock<G>::N), lds, e->stream, e->dm_dev, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // The float pair loop exists for the one-wavefront-per-walker shapes with
 // pairs classified from the sines (qmc_inst.h).
 template <int G, bool ZC>
 static constexpr bool has_fast() { return G == 64 && !ZC; }
 
+// f(R{}) with the pair-loop type R of this engine on this shape; f names a
+// float instantiation only where one exists.
+template <int G, bool ZC, typename F>
+static int with_pair_type(const qmc_engine *e, F f)
+{
+    if constexpr (has_fast<G, ZC>())
+        if (e->fast) return f(float{});
+    return f(double{});
+}
+
 template <int G, int P, bool PAD, bool ZC>
 struct LaunchEval {
-    static constexpr bool want_mask(int np) { return np >= 4; }
     static int run(const qmc_engine *e, const EvalArgs &a)
     {
         if (a.nconf <= 0) return 0;
-        const size_t lds = lds_bytes<G, P, ZC>();
-        if constexpr (has_fast<G, ZC>()) {
-            if (e->fast) {
-                allow_lds(evaluate_kernel<G, P, PAD, ZC, float>, lds);
-                hipLaunchKernelGGL((evaluate_kernel<G, P, PAD, ZC, float>),
-                                   dim3(grid_for<G>(a.nconf)), dim3(WalkBlock<G>::N),
-                                   lds, e->stream, e->dm_dev, a);
-                HIP_TRY(hipGetLastError());
-                return 0;
-            }
-        }
-        allow_lds(evaluate_kernel<G, P, PAD, ZC>, lds);
-        hipLaunchKernelGGL((evaluate_kernel<G, P, PAD, ZC>),
-                           dim3(grid_for<G>(a.nconf)), dim3(WalkBlock<G>::N),
-                           lds, e->stream, e->dm_dev, a);
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return with_pair_type<G, ZC>(e, [&](auto r) {
+            return launch_walkers<G>(
+                e, evaluate_kernel<G, P, PAD, ZC, decltype(r)>,
+                lds_bytes<G, P, ZC>(), a.nconf, a);
+        });
     }
 };
 
 template <int G, int P, bool PAD, bool ZC>
 struct LaunchPrep {
-    static constexpr bool want_mask(int np) { return np >= 4; }
     static int run(const qmc_engine *e, const PrepArgs &a)
     {
         if (a.nconf <= 0) return 0;
-        const size_t lds = lds_bytes<G, P, ZC>();
-        if constexpr (has_fast<G, ZC>()) {
-            if (e->fast) {
-                allow_lds(prepare_kernel<G, P, PAD, ZC, float>, lds);
-                hipLaunchKernelGGL((prepare_kernel<G, P, PAD, ZC, float>),
-                                   dim3(grid_for<G>(a.nconf)), dim3(WalkBlock<G>::N),
-                                   lds, e->stream, e->dm_dev, a);
-                HIP_TRY(hipGetLastError());
-                return 0;
-            }
-        }
-        allow_lds(prepare_kernel<G, P, PAD, ZC>, lds);
-        hipLaunchKernelGGL((prepare_kernel<G, P, PAD, ZC>),
-                           dim3(grid_for<G>(a.nconf)), dim3(WalkBlock<G>::N),
-                           lds, e->stream, e->dm_dev, a);
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return with_pair_type<G, ZC>(e, [&](auto r) {
+            return launch_walkers<G>(
+                e, prepare_kernel<G, P, PAD, ZC, decltype(r)>,
+                lds_bytes<G, P, ZC>(), a.nconf, a);
+        });
     }
 };
 
 template <int G, int P, bool PAD, bool ZC>
 struct LaunchVmc {
-    static constexpr bool want_mask(int np) { return np >= 4; }
-    template <typename R, bool LEAN, bool STEADY>
-    static void launch(const qmc_engine *e, const VmcArgs &a, size_t lds)
-    {
-        allow_lds(vmc_step_kernel<G, P, PAD, ZC, LEAN, R, STEADY>, lds);
-        hipLaunchKernelGGL((vmc_step_kernel<G, P, PAD, ZC, LEAN, R, STEADY>),
-                           dim3(grid_for<G>(a.W)), dim3(WalkBlock<G>::N), lds,
-                           e->stream, e->dm_dev, a);
-    }
-    template <typename R>
-    static void launch(const qmc_engine *e, const VmcArgs &a, size_t lds,
-                       bool lean, bool steady)
-    {
-        // (the steady variant: every yield of a block after its first)
-        if (steady)
-            launch<R, true, true>(e, a, lds);
-        else if (lean)
-            launch<R, true, false>(e, a, lds);
-        else
-            launch<R, false, false>(e, a, lds);
-    }
     // One launch from yield a.y on; *ran = the yields it ran: 1, or on a
     // VmcFused shape all a.nsteps steady yields left in the block.
     static int run(const qmc_engine *e, const VmcArgs &a, long long *ran)
@@ -278,47 +306,30 @@ struct LaunchVmc {
         const size_t lds = step_lds_bytes<G, P, PAD, ZC>();
         const bool lean = !a.tape && !a.gaussian && !a.ser_wf && !a.ser_e &&
                           !a.ser_stat && !a.ser_pos;
+        // (the steady variant: every yield of a block after its first)
         const bool steady = lean && !a.forced && !a.reset_sums;
         *ran = (steady && VmcFused<G, P, ZC>::ON) ? (long long)a.nsteps : 1;
         ProfScope prof(e);
-        if constexpr (has_fast<G, ZC>()) {
-            if (e->fast) {
-                launch<float>(e, a, lds, lean, steady);
-                HIP_TRY(hipGetLastError());
-                return 0;
-            }
-        }
-        launch<double>(e, a, lds, lean, steady);
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return with_pair_type<G, ZC>(e, [&](auto r) {
+            using R = decltype(r);
+            auto kernel = steady ? vmc_step_kernel<G, P, PAD, ZC, true, R, true>
+                          : lean ? vmc_step_kernel<G, P, PAD, ZC, true, R, false>
+                                 : vmc_step_kernel<G, P, PAD, ZC, false, R, false>;
+            return launch_walkers<G>(e, kernel, lds, a.W, a);
+        });
     }
 };
 
 template <int G, int P, bool PAD, bool ZC>
 struct LaunchEvolve {
-    // (P = 8: the unmasked variant needs 253 registers and ran 1.7x slower,
-    // profiles/r02_n512_tile_sweep.txt)
-    static constexpr bool want_mask(int np) { return np >= 4; }
     static int run(const qmc_engine *e, const EvolveArgs &a)
     {
-        const size_t lds = step_lds_bytes<G, P, PAD, ZC, true>();
         ProfScope prof(e);
-        if constexpr (has_fast<G, ZC>()) {
-            if (e->fast) {
-                allow_lds(dmc_evolve_kernel<G, P, PAD, ZC, float>, lds);
-                hipLaunchKernelGGL((dmc_evolve_kernel<G, P, PAD, ZC, float>),
-                                   dim3(grid_for<G>(a.maxw)), dim3(WalkBlock<G>::N),
-                                   lds, e->stream, e->dm_dev, a);
-                HIP_TRY(hipGetLastError());
-                return 0;
-            }
-        }
-        allow_lds(dmc_evolve_kernel<G, P, PAD, ZC>, lds);
-        hipLaunchKernelGGL((dmc_evolve_kernel<G, P, PAD, ZC>),
-                           dim3(grid_for<G>(a.maxw)), dim3(WalkBlock<G>::N),
-                           lds, e->stream, e->dm_dev, a);
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return with_pair_type<G, ZC>(e, [&](auto r) {
+            return launch_walkers<G>(
+                e, dmc_evolve_kernel<G, P, PAD, ZC, decltype(r)>,
+                step_lds_bytes<G, P, PAD, ZC, true>(), a.maxw, a);
+        });
     }
 };
 
@@ -604,13 +615,12 @@ static int engine_create_impl(const qmc_model_params *model, int device,
     if (ndev <= 0) return fail("qmc_engine_create: no HIP device");
     if (device < 0 || device >= ndev)
         return fail("qmc_engine_create: bad device index");
-    qmc_engine *e = new qmc_engine();
+    // (nothing of the device is held before hipSetDevice below)
+    std::unique_ptr<qmc_engine> e(new qmc_engine());
     e->device = device;
     e->mp = *model;
-    if (pick_shape((int)model->boson_number, e->G, e->P, e->pad)) {
-        delete e;
+    if (pick_shape((int)model->boson_number, e->G, e->P, e->pad))
         return fail("qmc_engine_create: boson_number must be in [1, 512]");
-    }
     build_dev_model(*model, e->dm);
     // lanes of a group the rotation runs over: all of them when the model
     // fills the shape, else the smallest even number that holds it
@@ -620,20 +630,16 @@ static int engine_create_impl(const qmc_model_params *model, int device,
     // and k2 rm in (0, pi/2) for every repulsive model
     if (!e->dm.is_ideal &&
         (e->dm.sphi < 0.0 || e->dm.cphi < 0.0 ||
-         e->dm.k2 * e->dm.rm >= 0.5 * QMC_PI || e->dm.k2 <= 0.0)) {
-        delete e;
+         e->dm.k2 * e->dm.rm >= 0.5 * QMC_PI || e->dm.k2 <= 0.0))
         return fail("qmc_engine_create: two-body parameters outside the "
                     "model's domain (need 0 < k2 rm < pi/2, 0 <= k2 r_off <= pi/2)");
-    }
     // the sorted-row pair sums (qmc_sorted64.h) count every pair quotient in
     // units of a_long = (pi / L) beta: a non-ideal model with beta = 0 (which
     // the reference's matching conditions never produce, mrbp_qmc/model.py:
     // 255-274) would lose its short-range terms there without an error
-    if (!e->dm.is_ideal && !(e->dm.a_long != 0.0)) {
-        delete e;
+    if (!e->dm.is_ideal && !(e->dm.a_long != 0.0))
         return fail("qmc_engine_create: a non-ideal model needs "
                     "param_beta != 0");
-    }
     HIP_TRY(hipSetDevice(device));
     if (caller_stream) {
         // the caller's stream as it is; NULL is the legacy default stream
@@ -649,8 +655,7 @@ static int engine_create_impl(const qmc_model_params *model, int device,
         int m1 = 0, m2 = 0;
         build_ob_table(e->dm, tab, m1, m2);
         if (!tab.empty()) {
-            HIP_TRY(hipMalloc((void **)&e->ob_table_dev,
-                              tab.size() * sizeof(double)));
+            if (e->ob_table_dev.alloc(tab.size())) return 1;
             HIP_TRY(hipMemcpy(e->ob_table_dev, tab.data(),
                               tab.size() * sizeof(double),
                               hipMemcpyHostToDevice));
@@ -666,8 +671,7 @@ static int engine_create_impl(const qmc_model_params *model, int device,
         std::vector<double> tab;
         build_trig_table(e->dm, tab);
         if (!tab.empty()) {
-            HIP_TRY(hipMalloc((void **)&e->trig_table_dev,
-                              tab.size() * sizeof(double)));
+            if (e->trig_table_dev.alloc(tab.size())) return 1;
             HIP_TRY(hipMemcpy(e->trig_table_dev, tab.data(),
                               tab.size() * sizeof(double),
                               hipMemcpyHostToDevice));
@@ -675,20 +679,18 @@ static int engine_create_impl(const qmc_model_params *model, int device,
         }
     }
 #if defined(QMC_TIMING)
-    HIP_TRY(hipMalloc((void **)&e->sec_prof_dev, (size_t)QMC_SEC_COPIES * 2 *
-                      QMC_NSEC * sizeof(unsigned long long)));
+    if (e->sec_prof_dev.alloc((size_t)QMC_SEC_COPIES * 2 * QMC_NSEC)) return 1;
     HIP_TRY(hipMemset(e->sec_prof_dev, 0, (size_t)QMC_SEC_COPIES * 2 *
                       QMC_NSEC * sizeof(unsigned long long)));
     e->dm.sec_prof = e->sec_prof_dev;
 #endif
-    HIP_TRY(hipMalloc((void **)&e->diag_dev,
-                      QMC_NDIAG * sizeof(unsigned long long)));
+    if (e->diag_dev.alloc(QMC_NDIAG)) return 1;
     HIP_TRY(hipMemset(e->diag_dev, 0, QMC_NDIAG * sizeof(unsigned long long)));
     e->dm.diag = e->diag_dev;
-    HIP_TRY(hipMalloc((void **)&e->dm_dev, sizeof(DevModel)));
+    if (e->dm_dev.alloc(1)) return 1;
     HIP_TRY(hipMemcpy(e->dm_dev, &e->dm, sizeof(DevModel),
                       hipMemcpyHostToDevice));
-    *out = e;
+    *out = e.release();
     return 0;
 }
 
@@ -962,25 +964,13 @@ extern "C" const char *qmc_section_name(int32_t i)
 extern "C" void qmc_engine_destroy(qmc_engine *e)
 {
     if (!e) return;
-    hipSetDevice(e->device);
-    for (hipEvent_t ev : e->prof_ev) hipEventDestroy(ev);
-    if (e->ev0) hipEventDestroy(e->ev0);
-    if (e->ev1) hipEventDestroy(e->ev1);
-    if (e->dm_dev) hipFree(e->dm_dev);
-    if (e->ob_table_dev) hipFree(e->ob_table_dev);
-    if (e->trig_table_dev) hipFree(e->trig_table_dev);
-    if (e->sec_prof_dev) hipFree(e->sec_prof_dev);
-    if (e->diag_dev) hipFree(e->diag_dev);
-    if (e->obdm_stab) hipFree(e->obdm_stab);
-    if (e->obdm_g1) hipFree(e->obdm_g1);
-    if (e->obdm_sums) hipFree(e->obdm_sums);
-    if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
+    (void)hipSetDevice(e->device);
     delete e;
 }
 
 extern "C" int qmc_engine_sync(qmc_engine *e)
 {
-    if (!e) return fail("null engine");
+    if (!e) return fail("qmc_engine_sync: null argument");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return 0;
@@ -988,7 +978,7 @@ extern "C" int qmc_engine_sync(qmc_engine *e)
 
 extern "C" int qmc_engine_timer_start(qmc_engine *e)
 {
-    if (!e) return fail("null engine");
+    if (!e) return fail("qmc_engine_timer_start: null argument");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipEventRecord(e->ev0, e->stream));
     return 0;
@@ -996,20 +986,11 @@ extern "C" int qmc_engine_timer_start(qmc_engine *e)
 
 extern "C" int qmc_engine_timer_stop(qmc_engine *e, float *ms)
 {
-    if (!e || !ms) return fail("null argument");
+    if (!e || !ms) return fail("qmc_engine_timer_stop: null argument");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipEventRecord(e->ev1, e->stream));
     HIP_TRY(hipEventSynchronize(e->ev1));
     HIP_TRY(hipEventElapsedTime(ms, e->ev0, e->ev1));
-    return 0;
-}
-
-template <typename T>
-static int dev_alloc(T **p, size_t count)
-{
-    *p = nullptr;
-    if (count == 0) count = 1;
-    HIP_TRY(hipMalloc((void **)p, count * sizeof(T)));
     return 0;
 }
 
@@ -1045,28 +1026,17 @@ extern "C" int qmc_engine_probe(qmc_engine *e, int32_t fn, int64_t n,
                         "(-4 L, 4 L)");
     }
     HIP_TRY(hipSetDevice(e->device));
-    double *din = nullptr, *dout = nullptr;
-    if (dev_alloc(&din, (size_t)n * nin)) return 1;
-    if (dev_alloc(&dout, (size_t)n * nout)) {
-        hipFree(din);
-        return 1;
-    }
-    hipError_t rc = hipMemcpyAsync(din, in, (size_t)n * nin * sizeof(double),
-                                   hipMemcpyHostToDevice, e->stream);
-    if (rc == hipSuccess) {
-        hipLaunchKernelGGL(probe_kernel, dim3((unsigned)((n + 63) / 64)),
-                           dim3(64), 0, e->stream, e->dm_dev, (int)fn,
-                           (long long)n, din, dout, nin, nout);
-        rc = hipGetLastError();
-    }
-    if (rc == hipSuccess)
-        rc = hipMemcpyAsync(out, dout, (size_t)n * nout * sizeof(double),
-                            hipMemcpyDeviceToHost, e->stream);
-    if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);
-    hipFree(din);
-    hipFree(dout);
-    if (rc != hipSuccess)
-        return fail(std::string("qmc_engine_probe: ") + hipGetErrorString(rc));
+    DevBuf<double> din, dout;
+    if (din.alloc((size_t)n * nin) || dout.alloc((size_t)n * nout)) return 1;
+    HIP_TRY(hipMemcpyAsync(din, in, (size_t)n * nin * sizeof(double),
+                           hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(probe_kernel, dim3((unsigned)((n + 63) / 64)),
+                       dim3(64), 0, e->stream, e->dm_dev, (int)fn,
+                       (long long)n, din, dout, nin, nout);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, dout, (size_t)n * nout * sizeof(double),
+                           hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return 0;
 }
 
@@ -1121,26 +1091,23 @@ extern "C" int qmc_evaluate(qmc_engine *e, int64_t nconf, const double *pos,
     if (nconf <= 0) return 0;
     HIP_TRY(hipSetDevice(e->device));
     const size_t n = (size_t)e->dm.n, W = (size_t)nconf;
-    double *dpos, *dwf, *den, *dith, *ddr;
-    if (dev_alloc(&dpos, W * n) || dev_alloc(&dwf, W) || dev_alloc(&den, W) ||
-        dev_alloc(&dith, W * n) || dev_alloc(&ddr, W * n))
+    DevBuf<double> dpos, dwf, den, dith, ddr;
+    if (dpos.alloc(W * n) || dwf.alloc(W) || den.alloc(W) ||
+        dith.alloc(W * n) || ddr.alloc(W * n))
         return 1;
     HIP_TRY(hipMemcpyAsync(dpos, pos, W * n * sizeof(double),
                            hipMemcpyHostToDevice, e->stream));
-    int rc = qmc_evaluate_dev(e, nconf, dpos, dwf, den, dith, ddr);
-    if (!rc) {
-        if (wf) HIP_TRY(hipMemcpyAsync(wf, dwf, W * sizeof(double),
+    if (qmc_evaluate_dev(e, nconf, dpos, dwf, den, dith, ddr)) return 1;
+    if (wf) HIP_TRY(hipMemcpyAsync(wf, dwf, W * sizeof(double),
+                                   hipMemcpyDeviceToHost, e->stream));
+    if (energy) HIP_TRY(hipMemcpyAsync(energy, den, W * sizeof(double),
                                        hipMemcpyDeviceToHost, e->stream));
-        if (energy) HIP_TRY(hipMemcpyAsync(energy, den, W * sizeof(double),
-                                           hipMemcpyDeviceToHost, e->stream));
-        if (ith) HIP_TRY(hipMemcpyAsync(ith, dith, W * n * sizeof(double),
-                                        hipMemcpyDeviceToHost, e->stream));
-        if (drift) HIP_TRY(hipMemcpyAsync(drift, ddr, W * n * sizeof(double),
-                                          hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    hipFree(dpos); hipFree(dwf); hipFree(den); hipFree(dith); hipFree(ddr);
-    return rc;
+    if (ith) HIP_TRY(hipMemcpyAsync(ith, dith, W * n * sizeof(double),
+                                    hipMemcpyDeviceToHost, e->stream));
+    if (drift) HIP_TRY(hipMemcpyAsync(drift, ddr, W * n * sizeof(double),
+                                      hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return 0;
 }
 
 // Sort every configuration by position; label[w][lane] = original particle
@@ -1179,20 +1146,19 @@ struct qmc_vmc {
     qmc_engine *eng = nullptr;
     qmc_vmc_params p;
     long long W = 0;
-    double *pos = nullptr, *wf = nullptr, *ecarry = nullptr;
-    unsigned short *label = nullptr;
-    double *sum_e = nullptr, *sum_e2 = nullptr;
-    long long *n_acc = nullptr;
+    DevBuf<double> pos, wf, ecarry;
+    DevBuf<unsigned short> label;
+    DevBuf<double> sum_e, sum_e2;
+    DevBuf<long long> n_acc;
     // the per-chain scalars the step kernel reads and writes; wf, ecarry,
     // sum_e, sum_e2 and n_acc above are their copies for the C ABI, refreshed
     // at the end of every run_block
-    VmcRec *rec = nullptr;
-    double *tape = nullptr;
+    DevBuf<VmcRec> rec;
+    DevBuf<double> tape;
     long long tape_steps = 0, tape_used = 0;
     unsigned int step = 0;
     int yield_initial = 1;
-    double *ssf_partial = nullptr, *ssf_out = nullptr;   // qmc_vmc_ssf scratch
-    int ssf_cap = 0;
+    DevBuf<double> ssf_partial, ssf_out;                 // qmc_vmc_ssf scratch
 };
 
 extern "C" int qmc_vmc_create(qmc_engine *e, const qmc_vmc_params *p,
@@ -1201,31 +1167,23 @@ extern "C" int qmc_vmc_create(qmc_engine *e, const qmc_vmc_params *p,
     if (!e || !p || !out) return fail("qmc_vmc_create: null argument");
     if (p->num_chains <= 0) return fail("qmc_vmc_create: num_chains <= 0");
     HIP_TRY(hipSetDevice(e->device));
-    qmc_vmc *v = new qmc_vmc();
+    std::unique_ptr<qmc_vmc> v(new qmc_vmc());
     v->eng = e;
     v->p = *p;
     v->W = p->num_chains;
     const size_t W = (size_t)v->W, n = (size_t)e->dm.n;
-    if (dev_alloc(&v->pos, W * n) || dev_alloc(&v->label, W * n) ||
-        dev_alloc(&v->wf, W) || dev_alloc(&v->ecarry, W) || dev_alloc(&v->sum_e, W) ||
-        dev_alloc(&v->sum_e2, W) || dev_alloc(&v->n_acc, W) ||
-        dev_alloc(&v->rec, W)) {
-        delete v;
+    if (v->pos.alloc(W * n) || v->label.alloc(W * n) || v->wf.alloc(W) ||
+        v->ecarry.alloc(W) || v->sum_e.alloc(W) || v->sum_e2.alloc(W) ||
+        v->n_acc.alloc(W) || v->rec.alloc(W))
         return 1;
-    }
-    *out = v;
+    *out = v.release();
     return 0;
 }
 
 extern "C" void qmc_vmc_destroy(qmc_vmc *v)
 {
     if (!v) return;
-    hipSetDevice(v->eng->device);
-    hipFree(v->pos); hipFree(v->label); hipFree(v->wf); hipFree(v->ecarry);
-    if (v->ssf_partial) hipFree(v->ssf_partial);
-    if (v->ssf_out) hipFree(v->ssf_out);
-    hipFree(v->sum_e); hipFree(v->sum_e2); hipFree(v->n_acc); hipFree(v->rec);
-    if (v->tape) hipFree(v->tape);
+    (void)hipSetDevice(v->eng->device);
     delete v;
 }
 
@@ -1292,12 +1250,12 @@ extern "C" int qmc_vmc_set_tape(qmc_vmc *v, const double *tape, int64_t steps)
     if (!v) return fail("qmc_vmc_set_tape: null argument");
     qmc_engine *e = v->eng;
     HIP_TRY(hipSetDevice(e->device));
-    if (v->tape) { hipFree(v->tape); v->tape = nullptr; }
+    v->tape.release();
     v->tape_steps = 0;
     v->tape_used = 0;
     if (!tape || steps <= 0) return 0;
     size_t cnt = (size_t)v->W * (size_t)steps * (size_t)(e->dm.n + 1);
-    if (dev_alloc(&v->tape, cnt)) return 1;
+    if (v->tape.alloc(cnt)) return 1;
     HIP_TRY(hipMemcpy(v->tape, tape, cnt * sizeof(double),
                       hipMemcpyHostToDevice));
     v->tape_steps = steps;
@@ -1306,7 +1264,7 @@ extern "C" int qmc_vmc_set_tape(qmc_vmc *v, const double *tape, int64_t steps)
 
 extern "C" int qmc_vmc_state_dev(qmc_vmc *v, double **pos, double **wf)
 {
-    if (!v) return fail("null argument");
+    if (!v) return fail("qmc_vmc_state_dev: null argument");
     if (pos) *pos = v->pos;
     if (wf) *wf = v->wf;
     return 0;
@@ -1324,14 +1282,9 @@ extern "C" int qmc_vmc_ssf(qmc_vmc *v, int32_t num_modes, double *out)
     qmc_engine *e = v->eng;
     HIP_TRY(hipSetDevice(e->device));
     const int M = num_modes;
-    if (M > v->ssf_cap) {
-        if (v->ssf_partial) { hipFree(v->ssf_partial); hipFree(v->ssf_out); }
-        v->ssf_partial = v->ssf_out = nullptr;
-        if (dev_alloc(&v->ssf_partial, (size_t)EST_BLOCKS * M * 3) ||
-            dev_alloc(&v->ssf_out, (size_t)M * 3))
-            return 1;
-        v->ssf_cap = M;
-    }
+    if (v->ssf_partial.reserve((size_t)EST_BLOCKS * M * 3) ||
+        v->ssf_out.reserve((size_t)M * 3))
+        return 1;
     EstArgs a;
     a.ppos = v->pos; a.ref = nullptr; a.ctl = nullptr;
     a.aux_prev = nullptr; a.aux_act = nullptr; a.partial = v->ssf_partial;
@@ -1370,22 +1323,11 @@ static constexpr long long OBDM_TILE = 1ll << 16;
 // qmc_obdm keeps on the device at a time (128 MB).
 static constexpr long long OBDM_HOST_TILE_DOUBLES = 1ll << 24;
 
-static int obdm_reserve(double **buf, size_t *cap, size_t count)
-{
-    if (count <= *cap) return 0;
-    if (*buf) { hipFree(*buf); *buf = nullptr; *cap = 0; }
-    if (dev_alloc(buf, count)) return 1;
-    *cap = count;
-    return 0;
-}
-
 // shift table of a set of device-resident shifts, on the engine's stream
 static int obdm_make_shift_table(qmc_engine *e, int32_t nshift,
                                  const double *shifts_dev)
 {
-    if (obdm_reserve(&e->obdm_stab, &e->obdm_stab_cap,
-                     (size_t)nshift * OBDM_SROW))
-        return 1;
+    if (e->obdm_stab.reserve((size_t)nshift * OBDM_SROW)) return 1;
     hipLaunchKernelGGL(obdm_shift_kernel, dim3((nshift + 63) / 64), dim3(64),
                        0, e->stream, e->dm_dev, shifts_dev, (int)nshift,
                        e->obdm_stab);
@@ -1459,7 +1401,7 @@ extern "C" int qmc_obdm_reduce_dev(qmc_engine *e, int64_t nconf,
     const long long tile = std::min<long long>(std::max<long long>(nconf, 1),
                                                OBDM_TILE);
     if (obdm_make_shift_table(e, nshift, shifts) ||
-        obdm_reserve(&e->obdm_g1, &e->obdm_g1_cap, (size_t)tile * nshift))
+        e->obdm_g1.reserve((size_t)tile * nshift))
         return 1;
     long long c0 = 0;
     do {
@@ -1501,35 +1443,29 @@ extern "C" int qmc_obdm(qmc_engine *e, int64_t nconf, const double *pos,
     const size_t per_conf = M * (ith ? n + 1 : 1);
     const long long tile = std::max<long long>(
         1, std::min<long long>(nconf, OBDM_HOST_TILE_DOUBLES / (long long)per_conf));
-    double *dsh = nullptr, *dpos = nullptr, *dg1 = nullptr, *dith = nullptr;
-    int rc = dev_alloc(&dsh, M) || dev_alloc(&dpos, (size_t)tile * n) ||
-             dev_alloc(&dg1, (size_t)tile * M) ||
-             (ith && dev_alloc(&dith, (size_t)tile * M * n));
-    auto run = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(dsh, shifts, M * sizeof(double),
+    DevBuf<double> dsh, dpos, dg1, dith;
+    if (dsh.alloc(M) || dpos.alloc((size_t)tile * n) ||
+        dg1.alloc((size_t)tile * M) || (ith && dith.alloc((size_t)tile * M * n)))
+        return 1;
+    HIP_TRY(hipMemcpyAsync(dsh, shifts, M * sizeof(double),
+                           hipMemcpyHostToDevice, e->stream));
+    if (obdm_make_shift_table(e, nshift, dsh)) return 1;
+    for (long long c0 = 0; c0 < nconf; c0 += tile) {
+        const size_t nc = (size_t)std::min(tile, (long long)nconf - c0);
+        HIP_TRY(hipMemcpyAsync(dpos, pos + (size_t)c0 * n,
+                               nc * n * sizeof(double),
                                hipMemcpyHostToDevice, e->stream));
-        if (obdm_make_shift_table(e, nshift, dsh)) return 1;
-        for (long long c0 = 0; c0 < nconf; c0 += tile) {
-            const size_t nc = (size_t)std::min(tile, (long long)nconf - c0);
-            HIP_TRY(hipMemcpyAsync(dpos, pos + (size_t)c0 * n,
-                                   nc * n * sizeof(double),
-                                   hipMemcpyHostToDevice, e->stream));
-            if (obdm_launch(e, (long long)nc, dpos, nshift, dg1, dith))
-                return 1;
-            HIP_TRY(hipMemcpyAsync(g1 + (size_t)c0 * M, dg1,
-                                   nc * M * sizeof(double),
+        if (obdm_launch(e, (long long)nc, dpos, nshift, dg1, dith)) return 1;
+        HIP_TRY(hipMemcpyAsync(g1 + (size_t)c0 * M, dg1,
+                               nc * M * sizeof(double),
+                               hipMemcpyDeviceToHost, e->stream));
+        if (ith)
+            HIP_TRY(hipMemcpyAsync(ith + (size_t)c0 * M * n, dith,
+                                   nc * M * n * sizeof(double),
                                    hipMemcpyDeviceToHost, e->stream));
-            if (ith)
-                HIP_TRY(hipMemcpyAsync(ith + (size_t)c0 * M * n, dith,
-                                       nc * M * n * sizeof(double),
-                                       hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(hipStreamSynchronize(e->stream));
-        }
-        return 0;
-    };
-    if (!rc) rc = run();
-    hipFree(dsh); hipFree(dpos); hipFree(dg1); hipFree(dith);
-    return rc;
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    return 0;
 }
 
 // g1 parts of the CURRENT configurations of the chains, summed over the
@@ -1543,7 +1479,7 @@ extern "C" int qmc_vmc_obdm(qmc_vmc *v, int32_t nshift, const double *shifts,
     qmc_engine *e = v->eng;
     HIP_TRY(hipSetDevice(e->device));
     const size_t M = (size_t)nshift;
-    if (obdm_reserve(&e->obdm_sums, &e->obdm_sums_cap, 3 * M)) return 1;
+    if (e->obdm_sums.reserve(3 * M)) return 1;
     double *dsh = e->obdm_sums + 2 * M;
     HIP_TRY(hipMemcpyAsync(dsh, shifts, M * sizeof(double),
                            hipMemcpyHostToDevice, e->stream));
@@ -1560,10 +1496,10 @@ extern "C" int qmc_vmc_obdm(qmc_vmc *v, int32_t nshift, const double *shifts,
 extern "C" int qmc_vmc_block_sums_dev(qmc_vmc *v, double **se, double **se2,
                                       int64_t **na)
 {
-    if (!v) return fail("null argument");
+    if (!v) return fail("qmc_vmc_block_sums_dev: null argument");
     if (se) *se = v->sum_e;
     if (se2) *se2 = v->sum_e2;
-    if (na) *na = (int64_t *)v->n_acc;
+    if (na) *na = (int64_t *)v->n_acc.get();
     return 0;
 }
 
@@ -1580,19 +1516,13 @@ extern "C" int qmc_vmc_run_block(qmc_vmc *v, int64_t nyield, double *sum_e,
     const long long real = nyield - (v->yield_initial ? 1 : 0);
     if (v->tape && v->tape_used + real > v->tape_steps)
         return fail("qmc_vmc_run_block: tape exhausted");
-    double *dwf = nullptr, *de = nullptr;
-    unsigned char *dst = nullptr;
-    double *dpos = nullptr;
-    if ((ser_pos && dev_alloc(&dpos, ny * W * (size_t)e->dm.n)) ||
-        (ser_wf && dev_alloc(&dwf, ny * W)) ||
-        (ser_e && dev_alloc(&de, ny * W)) ||
-        (ser_stat && dev_alloc(&dst, ny * W))) {
-        if (dpos) hipFree(dpos);
-        if (dwf) hipFree(dwf);
-        if (de) hipFree(de);
-        if (dst) hipFree(dst);
+    // (the series of this block; they go when the entry point returns)
+    DevBuf<double> dwf, de, dpos;
+    DevBuf<unsigned char> dst;
+    if ((ser_pos && dpos.alloc(ny * W * (size_t)e->dm.n)) ||
+        (ser_wf && dwf.alloc(ny * W)) || (ser_e && de.alloc(ny * W)) ||
+        (ser_stat && dst.alloc(ny * W)))
         return 1;
-    }
     VmcArgs a;
     a.pos = v->pos; a.label = v->label; a.rec = v->rec;
     a.ser_wf = dwf; a.ser_e = de; a.ser_stat = dst; a.ser_pos = dpos;
@@ -1639,10 +1569,6 @@ extern "C" int qmc_vmc_run_block(qmc_vmc *v, int64_t nyield, double *sum_e,
                    ny * W * (size_t)e->dm.n * sizeof(double),
                    hipMemcpyDeviceToHost, e->stream)); need_sync = true; }
     if (need_sync) HIP_TRY(hipStreamSynchronize(e->stream));
-    if (dpos) hipFree(dpos);
-    if (dwf) hipFree(dwf);
-    if (de) hipFree(de);
-    if (dst) hipFree(dst);
     return 0;
 }
 
@@ -1653,24 +1579,23 @@ struct qmc_dmc {
     long long maxw = 0;
     int nblocks = 0;
     // two population buffers: [0]/[1] alternate parent / child roles
-    double *pos[2] = { nullptr, nullptr }, *drift[2] = { nullptr, nullptr };
-    unsigned short *label[2] = { nullptr, nullptr };
-    double *energy[2] = { nullptr, nullptr }, *weight[2] = { nullptr, nullptr };
+    DevBuf<double> pos[2], drift[2];
+    DevBuf<unsigned short> label[2];
+    DevBuf<double> energy[2], weight[2];
     int cur = 0;                 // index of the parent buffer
-    double *eslot = nullptr;
-    double *spare = nullptr;
-    long long *ref = nullptr;
-    int *count = nullptr;
-    long long *block_tot = nullptr, *block_off = nullptr;
-    double *block_esum = nullptr;
-    DmcCtl *ctl = nullptr;
-    // per-step series (device), capacity ser_cap steps
-    double *ser_e = nullptr, *ser_w = nullptr, *ser_ref = nullptr,
-           *ser_acc = nullptr;
-    unsigned long long *ser_nw = nullptr;
+    DevBuf<double> eslot;
+    DevBuf<double> spare;        // (one particle per lane only: DmcSpare)
+    DevBuf<long long> ref;
+    DevBuf<int> count;
+    DevBuf<long long> block_tot, block_off;
+    DevBuf<double> block_esum;
+    DevBuf<DmcCtl> ctl;
+    // per-step series (device), capacity ser_cap steps: the five grow together
+    DevBuf<double> ser_e, ser_w, ser_ref, ser_acc;
+    DevBuf<unsigned long long> ser_nw;
     long long ser_cap = 0, ser_len = 0;
     // tapes (test only)
-    double *u_tape = nullptr, *g_tape = nullptr;
+    DevBuf<double> u_tape, g_tape;
     std::vector<long long> u_off, g_off;
     long long tape_step = 0;
     bool stepped = false;        // a step has run since the last set_state
@@ -1681,11 +1606,10 @@ struct qmc_dmc {
     // estimators (f1)
     qmc_dmc_est_params est;
     bool have_est = false;
-    double *ssf_aux[2] = { nullptr, nullptr };   // [maxw][M][3]
-    double *dens_aux[2] = { nullptr, nullptr };  // [maxw][B]
-    double *est_partial = nullptr;               // [EST_BLOCKS][max(3M, B)]
-    double *iter_ssf = nullptr, *iter_dens = nullptr;
-    size_t iter_ssf_cap = 0, iter_dens_cap = 0;   // capacities in doubles
+    DevBuf<double> ssf_aux[2];                   // [maxw][M][3]
+    DevBuf<double> dens_aux[2];                  // [maxw][B]
+    DevBuf<double> est_partial;                  // [EST_BLOCKS][max(3M, B)]
+    DevBuf<double> iter_ssf, iter_dens;          // per-step outputs, grown on demand
     long long est_block_steps = 0;  // steps of the estimator block in progress
     int est_last_act = 1;           // aux buffer the last estimator step wrote
 };
@@ -1693,32 +1617,14 @@ struct qmc_dmc {
 static int dmc_reserve_series(qmc_dmc *d, long long nsteps)
 {
     if (nsteps <= d->ser_cap) return 0;
-    if (d->ser_e) hipFree(d->ser_e);
-    if (d->ser_w) hipFree(d->ser_w);
-    if (d->ser_ref) hipFree(d->ser_ref);
-    if (d->ser_acc) hipFree(d->ser_acc);
-    if (d->ser_nw) hipFree(d->ser_nw);
-    d->ser_e = d->ser_w = d->ser_ref = d->ser_acc = nullptr;
-    d->ser_nw = nullptr;
-    d->ser_cap = 0;
-    if (dev_alloc(&d->ser_e, nsteps) || dev_alloc(&d->ser_w, nsteps) ||
-        dev_alloc(&d->ser_ref, nsteps) || dev_alloc(&d->ser_acc, nsteps) ||
-        dev_alloc(&d->ser_nw, nsteps)) {
-        // dev_alloc nulls what it could not allocate
-        if (d->ser_e) hipFree(d->ser_e);
-        if (d->ser_w) hipFree(d->ser_w);
-        if (d->ser_ref) hipFree(d->ser_ref);
-        if (d->ser_acc) hipFree(d->ser_acc);
-        if (d->ser_nw) hipFree(d->ser_nw);
-        d->ser_e = d->ser_w = d->ser_ref = d->ser_acc = nullptr;
-        d->ser_nw = nullptr;
+    d->ser_cap = 0;             // (nothing is recorded into a partly grown set)
+    const size_t ns = (size_t)nsteps;
+    if (d->ser_e.alloc(ns) || d->ser_w.alloc(ns) || d->ser_ref.alloc(ns) ||
+        d->ser_acc.alloc(ns) || d->ser_nw.alloc(ns))
         return 1;
-    }
     d->ser_cap = nsteps;
     return 0;
 }
-
-extern "C" void qmc_dmc_destroy(qmc_dmc *d);
 
 extern "C" int qmc_dmc_create(qmc_engine *e, const qmc_dmc_params *p,
                               qmc_dmc **out)
@@ -1728,59 +1634,37 @@ extern "C" int qmc_dmc_create(qmc_engine *e, const qmc_dmc_params *p,
         return fail("qmc_dmc_create: walker counts must be positive");
     if (!(p->time_step > 0)) return fail("qmc_dmc_create: time_step <= 0");
     HIP_TRY(hipSetDevice(e->device));
-    qmc_dmc *d = new qmc_dmc();
+    std::unique_ptr<qmc_dmc> d(new qmc_dmc());
     d->eng = e;
     d->p = *p;
     d->maxw = p->max_num_walkers;
     d->nblocks = (int)((d->maxw + BR_TILE - 1) / BR_TILE);
     d->global_target = (double)p->target_num_walkers;
     const size_t W = (size_t)d->maxw, n = (size_t)e->dm.n;
-    int rc = 0;
-    for (int b = 0; b < 2 && !rc; ++b) {
-        rc |= dev_alloc(&d->pos[b], W * n) || dev_alloc(&d->drift[b], W * n) ||
-              dev_alloc(&d->label[b], W * n) ||
-              dev_alloc(&d->energy[b], W) || dev_alloc(&d->weight[b], W);
-    }
+    for (int b = 0; b < 2; ++b)
+        if (d->pos[b].alloc(W * n) || d->drift[b].alloc(W * n) ||
+            d->label[b].alloc(W * n) || d->energy[b].alloc(W) ||
+            d->weight[b].alloc(W))
+            return 1;
     // (the cached second Box-Muller normal: one particle per lane only,
     // qmc_kernels.h: DmcSpare)
     const bool need_spare = e->P == 1;
-    rc = rc || dev_alloc(&d->eslot, W) ||
-         (need_spare && dev_alloc(&d->spare, W * n)) ||
-         dev_alloc(&d->ref, W) ||
-         dev_alloc(&d->count, W) || dev_alloc(&d->block_tot, d->nblocks) ||
-         dev_alloc(&d->block_off, d->nblocks) ||
-         dev_alloc(&d->block_esum, d->nblocks) || dev_alloc(&d->ctl, 1);
-    if (rc) { qmc_dmc_destroy(d); return 1; }
+    if (d->eslot.alloc(W) || (need_spare && d->spare.alloc(W * n)) ||
+        d->ref.alloc(W) || d->count.alloc(W) ||
+        d->block_tot.alloc(d->nblocks) || d->block_off.alloc(d->nblocks) ||
+        d->block_esum.alloc(d->nblocks) || d->ctl.alloc(1))
+        return 1;
     HIP_TRY(hipMemset(d->ctl, 0, sizeof(DmcCtl)));
     HIP_TRY(hipMemset(d->ref, 0, W * sizeof(long long)));
     HIP_TRY(hipMemset(d->eslot, 0, W * sizeof(double)));
-    *out = d;
+    *out = d.release();
     return 0;
 }
 
 extern "C" void qmc_dmc_destroy(qmc_dmc *d)
 {
     if (!d) return;
-    hipSetDevice(d->eng->device);
-    // (hipFree(nullptr) is a no-op: a partly built ensemble is fine here)
-    for (int b = 0; b < 2; ++b) {
-        hipFree(d->pos[b]); hipFree(d->drift[b]); hipFree(d->label[b]);
-        hipFree(d->energy[b]); hipFree(d->weight[b]);
-    }
-    hipFree(d->eslot); hipFree(d->spare); hipFree(d->ref); hipFree(d->count);
-    hipFree(d->block_tot); hipFree(d->block_off); hipFree(d->block_esum);
-    hipFree(d->ctl);
-    if (d->ser_e) { hipFree(d->ser_e); hipFree(d->ser_w); hipFree(d->ser_ref);
-                    hipFree(d->ser_acc); hipFree(d->ser_nw); }
-    if (d->u_tape) hipFree(d->u_tape);
-    if (d->g_tape) hipFree(d->g_tape);
-    for (int k = 0; k < 2; ++k) {
-        if (d->ssf_aux[k]) hipFree(d->ssf_aux[k]);
-        if (d->dens_aux[k]) hipFree(d->dens_aux[k]);
-    }
-    if (d->est_partial) hipFree(d->est_partial);
-    if (d->iter_ssf) hipFree(d->iter_ssf);
-    if (d->iter_dens) hipFree(d->iter_dens);
+    (void)hipSetDevice(d->eng->device);
     delete d;
 }
 
@@ -1967,15 +1851,15 @@ extern "C" int qmc_dmc_set_tape(qmc_dmc *d, const double *u, int64_t nu,
 {
     if (!d) return fail("qmc_dmc_set_tape: null argument");
     HIP_TRY(hipSetDevice(d->eng->device));
-    if (d->u_tape) { hipFree(d->u_tape); d->u_tape = nullptr; }
-    if (d->g_tape) { hipFree(d->g_tape); d->g_tape = nullptr; }
+    d->u_tape.release();
+    d->g_tape.release();
     d->u_off.clear(); d->g_off.clear();
     d->tape_step = 0;
     if (!u || !g || nsteps <= 0) return 0;
     // pad so that a step may read up to maxw uniforms / maxw*N normals
     size_t upad = (size_t)nu + (size_t)d->maxw;
     size_t gpad = (size_t)ng + (size_t)d->maxw * (size_t)d->eng->dm.n;
-    if (dev_alloc(&d->u_tape, upad) || dev_alloc(&d->g_tape, gpad)) return 1;
+    if (d->u_tape.alloc(upad) || d->g_tape.alloc(gpad)) return 1;
     HIP_TRY(hipMemset(d->u_tape, 0, upad * sizeof(double)));
     HIP_TRY(hipMemset(d->g_tape, 0, gpad * sizeof(double)));
     HIP_TRY(hipMemcpy(d->u_tape, u, (size_t)nu * sizeof(double),
@@ -1992,9 +1876,9 @@ static FinishArgs dmc_finish_args(qmc_dmc *d, const double *total_dev,
 {
     FinishArgs f;
     f.ctl = d->ctl; f.total = total_dev;
-    f.block_esum = (!total_dev && d->sums_pending) ? d->block_esum : nullptr;
+    f.block_esum = (!total_dev && d->sums_pending) ? d->block_esum.get() : nullptr;
     const bool rec = ser_idx >= 0;
-    f.ser_e = rec ? d->ser_e : nullptr; f.ser_w = d->ser_w;
+    f.ser_e = rec ? d->ser_e.get() : nullptr; f.ser_w = d->ser_w;
     f.ser_ref = d->ser_ref; f.ser_acc = d->ser_acc; f.ser_nw = d->ser_nw;
     f.ser_idx = ser_idx;
     f.kappa = d->p.num_walkers_control_factor; f.dt = d->p.time_step;
@@ -2178,15 +2062,17 @@ extern "C" int qmc_dmc_set_estimators(qmc_dmc *d, const qmc_dmc_est_params *p)
                     "[0, 256]");
     qmc_engine *e = d->eng;
     HIP_TRY(hipSetDevice(e->device));
-    for (int k = 0; k < 2; ++k) {
-        if (d->ssf_aux[k]) { hipFree(d->ssf_aux[k]); d->ssf_aux[k] = nullptr; }
-        if (d->dens_aux[k]) { hipFree(d->dens_aux[k]); d->dens_aux[k] = nullptr; }
-    }
-    if (d->est_partial) { hipFree(d->est_partial); d->est_partial = nullptr; }
+    const auto drop = [d]() {
+        for (int k = 0; k < 2; ++k) {
+            d->ssf_aux[k].release();
+            d->dens_aux[k].release();
+        }
+        d->est_partial.release();
+    };
+    drop();
     // the per-step output buffers are sized for the old mode / bin counts
-    if (d->iter_ssf) { hipFree(d->iter_ssf); d->iter_ssf = nullptr; }
-    if (d->iter_dens) { hipFree(d->iter_dens); d->iter_dens = nullptr; }
-    d->iter_ssf_cap = d->iter_dens_cap = 0;
+    d->iter_ssf.release();
+    d->iter_dens.release();
     d->est_block_steps = 0;
     d->est_last_act = 1;
     d->have_est = false;
@@ -2199,22 +2085,18 @@ extern "C" int qmc_dmc_set_estimators(qmc_dmc *d, const qmc_dmc_est_params *p)
     bool failed = false;
     if (p->num_modes > 0)
         for (int k = 0; k < 2 && !failed; ++k)
-            failed = dev_alloc(&d->ssf_aux[k], W * (size_t)p->num_modes * 3) != 0;
+            failed = d->ssf_aux[k].alloc(W * (size_t)p->num_modes * 3) != 0;
     if (p->num_bins > 0)
         for (int k = 0; k < 2 && !failed; ++k)
-            failed = dev_alloc(&d->dens_aux[k], W * (size_t)p->num_bins) != 0;
+            failed = d->dens_aux[k].alloc(W * (size_t)p->num_bins) != 0;
     size_t kc = (size_t)(p->num_modes * 3 > p->num_bins ? p->num_modes * 3
                                                         : p->num_bins);
     if (want && !failed)
-        failed = dev_alloc(&d->est_partial, EST_BLOCKS * kc) != 0;
+        failed = d->est_partial.alloc(EST_BLOCKS * kc) != 0;
     if (failed) {
-        for (int k = 0; k < 2; ++k) {
-            if (d->ssf_aux[k]) { hipFree(d->ssf_aux[k]); d->ssf_aux[k] = nullptr; }
-            if (d->dens_aux[k]) { hipFree(d->dens_aux[k]); d->dens_aux[k] = nullptr; }
-        }
-        if (d->est_partial) { hipFree(d->est_partial); d->est_partial = nullptr; }
+        drop();
         d->est.num_modes = d->est.num_bins = 0;
-        return 1;            // (dev_alloc has set the message)
+        return 1;            // (alloc has set the message)
     }
     d->have_est = want;
     return 0;
@@ -2284,18 +2166,7 @@ static int dmc_est_begin_block(qmc_dmc *d, long long nsteps)
     const size_t W = (size_t)d->maxw;
     const size_t need_s = (size_t)nsteps * (M3 ? M3 : 1);
     const size_t need_d = (size_t)nsteps * (B ? B : 1);
-    if (need_s > d->iter_ssf_cap) {
-        if (d->iter_ssf) { hipFree(d->iter_ssf); d->iter_ssf = nullptr; }
-        d->iter_ssf_cap = 0;
-        if (dev_alloc(&d->iter_ssf, need_s)) return 1;
-        d->iter_ssf_cap = need_s;
-    }
-    if (need_d > d->iter_dens_cap) {
-        if (d->iter_dens) { hipFree(d->iter_dens); d->iter_dens = nullptr; }
-        d->iter_dens_cap = 0;
-        if (dev_alloc(&d->iter_dens, need_d)) return 1;
-        d->iter_dens_cap = need_d;
-    }
+    if (d->iter_ssf.reserve(need_s) || d->iter_dens.reserve(need_d)) return 1;
     HIP_TRY(hipMemsetAsync(d->iter_ssf, 0, need_s * 8, e->stream));
     HIP_TRY(hipMemsetAsync(d->iter_dens, 0, need_d * 8, e->stream));
     for (int k = 0; k < 2; ++k) {
@@ -2380,8 +2251,9 @@ extern "C" int qmc_dmc_est_iter_dev(qmc_dmc *d, double **iter_ssf,
                                     double **iter_density)
 {
     if (!d) return fail("qmc_dmc_est_iter_dev: null argument");
-    if (iter_ssf) *iter_ssf = d->est.num_modes > 0 ? d->iter_ssf : nullptr;
-    if (iter_density) *iter_density = d->est.num_bins > 0 ? d->iter_dens : nullptr;
+    if (iter_ssf) *iter_ssf = d->est.num_modes > 0 ? d->iter_ssf.get() : nullptr;
+    if (iter_density)
+        *iter_density = d->est.num_bins > 0 ? d->iter_dens.get() : nullptr;
     return 0;
 }
 
@@ -2399,11 +2271,11 @@ extern "C" int qmc_dmc_step_finish(qmc_dmc *d, const double *total_dev)
     if (d->ser_len >= d->ser_cap) {
         // grow geometrically, keeping what was recorded
         long long ncap = d->ser_cap ? d->ser_cap * 2 : 1024;
-        double *oe = d->ser_e, *ow = d->ser_w, *orf = d->ser_ref,
-               *oa = d->ser_acc;
-        unsigned long long *on = d->ser_nw;
+        DevBuf<double> oe(std::move(d->ser_e)), ow(std::move(d->ser_w)),
+            orf(std::move(d->ser_ref)), oa(std::move(d->ser_acc));
+        DevBuf<unsigned long long> on(std::move(d->ser_nw));
         long long olen = d->ser_len;
-        d->ser_e = nullptr; d->ser_cap = 0;
+        d->ser_cap = 0;
         if (dmc_reserve_series(d, ncap)) return 1;
         if (oe) {
             hipStream_t s = d->eng->stream;
@@ -2413,8 +2285,8 @@ extern "C" int qmc_dmc_step_finish(qmc_dmc *d, const double *total_dev)
             HIP_TRY(hipMemcpyAsync(d->ser_acc, oa, olen * 8, hipMemcpyDeviceToDevice, s));
             HIP_TRY(hipMemcpyAsync(d->ser_nw, on, olen * 8, hipMemcpyDeviceToDevice, s));
             HIP_TRY(hipStreamSynchronize(s));
-            hipFree(oe); hipFree(ow); hipFree(orf); hipFree(oa); hipFree(on);
         }
+        // (the old series go here, after the copies)
     }
     int rc = dmc_enqueue_finish(d, total_dev, d->ser_len);
     if (rc) return rc;
@@ -2460,8 +2332,8 @@ extern "C" int qmc_dmc_get_state(qmc_dmc *d, double *confs, double *energy,
             // yielded walkers are the parents selected by the cloning table;
             // the parent buffer of the last step is the one that is not `cur`
             const int par = 1 - d->cur;
-            double *tmp;
-            if (dev_alloc(&tmp, (size_t)nw * 2 * n)) return 1;
+            DevBuf<double> tmp;
+            if (tmp.alloc((size_t)nw * 2 * n)) return 1;
             long long tot = nw * (long long)n;
             hipLaunchKernelGGL(dmc_gather_state_kernel,
                                dim3((unsigned)((tot + 255) / 256)), dim3(256),
@@ -2470,7 +2342,6 @@ extern "C" int qmc_dmc_get_state(qmc_dmc *d, double *confs, double *energy,
             HIP_TRY(hipMemcpyAsync(confs, tmp, (size_t)nw * 2 * n * 8,
                                    hipMemcpyDeviceToHost, e->stream));
             HIP_TRY(hipStreamSynchronize(e->stream));
-            hipFree(tmp);
         } else {
             std::vector<double> hp((size_t)nw * n), hd((size_t)nw * n);
             std::vector<unsigned short> hl((size_t)nw * n);
@@ -2526,9 +2397,9 @@ static WalkerRecArgs walker_rec_args(qmc_dmc *d, long long first,
     a.eslot = d->eslot;
     // the rows the next estimator step reads as "previous"
     a.ssf_aux = d->est.num_modes > 0 && d->have_est
-                    ? d->ssf_aux[d->est_last_act] : nullptr;
+                    ? d->ssf_aux[d->est_last_act].get() : nullptr;
     a.dens_aux = d->est.num_bins > 0 && d->have_est
-                     ? d->dens_aux[d->est_last_act] : nullptr;
+                     ? d->dens_aux[d->est_last_act].get() : nullptr;
     a.first = first; a.count = count;
     a.n = d->eng->dm.n;
     a.m3 = a.ssf_aux ? d->est.num_modes * 3 : 0;
