@@ -269,6 +269,38 @@ int qmc_obdm_reduce_dev(qmc_engine *eng, int64_t nconf, const double *pos_dev,
                         const double *shifts_dev, double *sums_dev,
                         double *wsum_dev);
 
+/* Pair distribution function g2(r): per configuration the histogram of the
+ * N (N - 1) / 2 minimum-image pair distances r_ij = |min_distance(z_i, z_j, L)|
+ * (qmc_base/utils.py:35-51, reached through _real_distance,
+ * mrbp_qmc/model.py:555-562) over num_bins uniform bins of [0, L/2]:
+ * bin = min(floor(r / delta), num_bins - 1), delta = (L/2) / num_bins, the
+ * `int(z // bin_size)` convention of mrbp_qmc/dmc.py:522-545; a pair at
+ * exactly L/2 counts in the last bin.  counts[nconf][num_bins] holds unordered
+ * pairs, so every row adds up to N (N - 1) / 2, and
+ * g2(r_b) = counts[b] L / (N (N - 1) delta) at r_b = (b + 1/2) delta.
+ * Positions outside [0, L) are brought into the box first; the particle order
+ * is irrelevant.  Always fp64: qmc_engine_set_fast_math does not apply
+ * (csrc/qmc_pairdist.h).
+ * qmc_pair_dist: host buffers, synchronous; a NULL pos / counts or num_bins
+ * outside [1, 4096] is an error. */
+int qmc_pair_dist(qmc_engine *eng, int64_t nconf, const double *pos,
+                  int32_t num_bins, uint32_t *counts);
+/* Same on device-resident buffers, asynchronous on the engine's stream. */
+int qmc_pair_dist_dev(qmc_engine *eng, int64_t nconf, const double *pos_dev,
+                      int32_t num_bins, uint32_t *counts_dev);
+/* Weighted sums over the configurations, device buffers, asynchronous:
+ * sums_dev[num_bins][2] = sum_c w_c H_c[b], sum_c w_c H_c[b]^2 and (unless
+ * NULL) wsum_dev[0] = sum_c w_c; w_dev = NULL means unit weights (the mixed
+ * estimate sum W H / sum W of a DMC State, the twin of mrbp_qmc/dmc.py:345-356,
+ * and the ensemble mean of qmc_vmc_pair_dist).  Fixed summation order: two
+ * calls give the same bits; with unit weights both sums are exact integers.
+ * The per-configuration histograms live in an engine-owned scratch filled in
+ * tiles of at most 2^16 configurations. */
+int qmc_pair_dist_reduce_dev(qmc_engine *eng, int64_t nconf,
+                             const double *pos_dev, const double *w_dev,
+                             int32_t num_bins, double *sums_dev,
+                             double *wsum_dev);
+
 /* Plain device buffers, so that a configuration set can stay resident across
  * many qmc_evaluate_dev calls with different engines: the correlated-sampling
  * optimiser re-evaluates wf_abs_log / energy of one fixed set for every trial
@@ -317,6 +349,12 @@ int qmc_vmc_ssf(qmc_vmc *v, int32_t num_modes, double *out);
  * no position leaves the device).  Host buffers; synchronous; shifts checked
  * as by qmc_obdm. */
 int qmc_vmc_obdm(qmc_vmc *v, int32_t nshift, const double *shifts, double *out);
+/* Pair-distance histogram parts of the CURRENT configurations summed over the
+ * chains: out[num_bins][2] = sum_w H_w[b], sum_w H_w[b]^2 (H as qmc_pair_dist,
+ * distances as qmc_base/utils.py:35-51), on the resident rows; no position
+ * leaves the device and the chain state is not touched.  Host buffer;
+ * synchronous; num_bins checked as by qmc_pair_dist. */
+int qmc_vmc_pair_dist(qmc_vmc *v, int32_t num_bins, double *out);
 /* Device addresses of the per-chain block sums of the last block
  * (sum_e[W], sum_e2[W], n_acc[W]) for on-device reductions / collectives. */
 int qmc_vmc_block_sums_dev(qmc_vmc *v, double **sum_e, double **sum_e2,

@@ -1,0 +1,122 @@
+// qmc_pairdist.h -- pair distribution function g2(r): the histogram of the
+// minimum-image pair distances of a configuration (the distance is
+// `min_distance`, qmc_base/utils.py:35-51, reached through `_real_distance`,
+// mrbp_qmc/model.py:555-562; the bin rule is the `int(z // bin_size)` of the
+// density estimator, mrbp_qmc/dmc.py:522-545).
+//
+//   z_i    the position brought into [0, L) (wrap_box)
+//   r_ij   = |z_i - z_j|, or L - |z_i - z_j| where that exceeds L/2
+//   b_ij   = min(floor(r_ij / delta), B - 1),  delta = (L/2) / B
+//   H[b]   = number of unordered pairs i < j with b_ij = b
+//
+// so that sum_b H[b] = N (N - 1) / 2 for every configuration and a pair at
+// exactly r = L/2 counts in the last bin.  g2(r_b) = H[b] L / (N (N - 1) delta)
+// is formed by the callers; the kernel hands out the integers.
+//
+// Layout.  One wavefront per configuration; where N <= 32, groups of
+// G = 8, 16, 32 lanes take one configuration each (the host widens G again
+// when 64 / G histograms would not fit the LDS budget).  A group publishes the
+// wrapped positions of its configuration in LDS and clears a histogram of B
+// 32-bit counters there.  The pair loop runs by rotation: the lane that owns
+// particle i meets i + 1, i + 2, ..., i + floor((N - 1) / 2) (indices modulo
+// N), and for an even N the particles i < N/2 meet i + N/2 as well: every
+// unordered pair once, N (N - 1) / 2 in all.  N > G runs in passes over the
+// own particles, i = lane + G p.  Per pair: one LDS read of the partner (the
+// lanes of a group read consecutive doubles), one subtraction, the image
+// select, one multiplication by 1 / delta, the conversion, one clamp and one
+// LDS integer add.  The histogram leaves the wavefront with plain vector
+// stores, as 32-bit counts or as doubles (exact: a count is below 2^17) for
+// the reduction over configurations.
+//
+// Counts are integers, so the order in which the LDS adds arrive cannot change
+// the result: the kernel is deterministic.  There is no floating-point atomic
+// and no global atomic.  Positions and distances are fp64 whatever
+// qmc_engine_set_fast_math says.
+//
+// The rounding of r / delta is the only freedom: the kernel multiplies by the
+// host's 1 / delta where the definition divides, and forms L - |d| where the
+// reference forms -L/2 + (d + L/2) % L.  Both differ from the definition by a
+// few ulp of r, which moves a pair only if it sits within that of a bin edge
+// (tests/_pairdist_restatement.py lists such pairs; with L and B powers of two
+// and positions on a binary grid every operation is exact).
+//
+// The reduction over configurations is obdm_reduce_kernel (qmc_obdm.h) on the
+// double-valued histograms: fixed summation order, and exact with unit weights
+// since every partial sum is an integer below 2^53.
+#pragma once
+
+#include "qmc_device.h"
+
+static constexpr int PD_MAX_BINS = 4096;
+// LDS a wavefront may take for positions and histograms of its groups
+static constexpr size_t PD_LDS_BUDGET = 32768;
+
+struct PairDistArgs {
+    const double *pos;     // [nconf][n]
+    void *out;             // [nconf][nbins], OutT
+    long long nconf;
+    int n, nbins;
+    double L, half;        // supercell size, L / 2
+    double inv_delta;      // nbins / (L / 2)
+};
+
+__device__ __forceinline__ void pd_count(unsigned *__restrict__ h, double zi,
+                                         double zj, const PairDistArgs &a,
+                                         bool active)
+{
+    const double ad = __builtin_fabs(zi - zj);
+    const double r = (ad > a.half) ? a.L - ad : ad;
+    int b = (int)(r * a.inv_delta);            // r >= 0: truncation is floor
+    b = min(max(b, 0), a.nbins - 1);
+    if (active) atomicAdd(&h[b], 1u);
+}
+
+// G: lanes of a configuration group (8, 16, 32, 64).
+template <int G, typename OutT>
+__global__ void __launch_bounds__(64)
+pair_dist_kernel(PairDistArgs a)
+{
+    extern __shared__ double pd_smem[];
+    constexpr int GPW = 64 / G;                 // configurations of a wavefront
+    const int n = a.n, B = a.nbins;
+    const int lane = threadIdx.x, grp = lane / G, gl = lane % G;
+    double *z = pd_smem + grp * n;                               // [GPW][n]
+    unsigned *h = (unsigned *)(pd_smem + GPW * n) + grp * B;     // [GPW][B]
+    const long long c = (long long)blockIdx.x * GPW + grp;
+    const bool live = c < a.nconf;
+    const double *row = a.pos + (size_t)(live ? c : 0) * n;
+    const int npass = (n + G - 1) / G;
+
+    for (int p = 0; p < npass; ++p) {
+        const int i = gl + G * p;
+        const double zw = wrap_box((live && i < n) ? row[i] : 0.0, a.L);
+        if (i < n) z[i] = zw;
+    }
+    for (int b = gl; b < B; b += G) h[b] = 0u;
+    __syncthreads();
+
+    const int kfull = (n - 1) / 2;              // offsets every particle takes
+    for (int p = 0; p < npass; ++p) {
+        const int i = gl + G * p;
+        const int ic = min(i, n - 1);
+        const bool own = live && i < n;
+        const double zi = z[ic];
+#pragma unroll 4
+        for (int k = 1; k <= kfull; ++k) {
+            int j = ic + k;
+            j = (j >= n) ? j - n : j;
+            pd_count(h, zi, z[j], a, own);
+        }
+        if (!(n & 1)) {
+            // even N: the offset N/2 joins each pair from both ends; the
+            // lower half of the particles takes it
+            const int j = min(ic + n / 2, n - 1);
+            pd_count(h, zi, z[j], a, own && i < n / 2);
+        }
+    }
+    __syncthreads();
+
+    OutT *out = (OutT *)a.out + (size_t)(live ? c : 0) * B;
+    for (int b = gl; b < B; b += G)
+        if (live) out[b] = (OutT)h[b];
+}

@@ -10,6 +10,7 @@
 #include "qmc_inst.h"
 #include "qmc_kernels_misc.h"
 #include "qmc_obdm.h"
+#include "qmc_pairdist.h"
 #include "../../include/qmcwalk.h"
 #include "qmc_probe.h"
 
@@ -110,6 +111,9 @@ struct qmc_engine {
     // one-body density matrix scratch (qmc_obdm*): the shift table and the
     // per-configuration tile g1[tile][nshift], grown on demand
     DevBuf<double> obdm_stab, obdm_g1, obdm_sums;
+    // pair distribution scratch (qmc_pair_dist*): the per-configuration tile
+    // of histograms as doubles and the sums of qmc_vmc_pair_dist
+    DevBuf<double> pd_hist, pd_sums;
 
     qmc_engine() = default;
     qmc_engine(const qmc_engine &) = delete;
@@ -1487,6 +1491,143 @@ extern "C" int qmc_vmc_obdm(qmc_vmc *v, int32_t nshift, const double *shifts,
                                  e->obdm_sums, nullptr);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, e->obdm_sums, 2 * M * sizeof(double),
+                           hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+// ---- pair distribution g2(r) (csrc/qmc_pairdist.h) ----------------------
+// Configurations per launch of the reduction (as OBDM_TILE), fewer where the
+// tile of histograms would exceed PD_SCRATCH_ELEMS doubles (128 MB): 2^16 up to
+// 256 bins, 2^12 at 4096.  The same count of 32-bit counters bounds what
+// qmc_pair_dist keeps on the device at a time.
+static constexpr long long PD_TILE = 1ll << 16;
+static constexpr long long PD_SCRATCH_ELEMS = 1ll << 24;
+
+static int pair_dist_check(const char *who, int64_t nconf, int32_t num_bins)
+{
+    if (num_bins < 1 || num_bins > PD_MAX_BINS)
+        return fail(std::string(who) + ": num_bins outside [1, " +
+                    std::to_string(PD_MAX_BINS) + "]");
+    if (nconf < 0) return fail(std::string(who) + ": nconf < 0");
+    return 0;
+}
+
+// histograms of nconf device-resident configurations -> out[nconf][B]
+template <typename OutT>
+static int pair_dist_launch(qmc_engine *e, long long nconf,
+                            const double *pos_dev, int32_t B, OutT *out)
+{
+    if (nconf <= 0) return 0;
+    const int n = e->dm.n;
+    int G = 64;
+    if (n <= 8) G = 8; else if (n <= 16) G = 16; else if (n <= 32) G = 32;
+    const size_t per_conf = (size_t)n * sizeof(double) + (size_t)B * sizeof(unsigned);
+    while (G < 64 && (64 / G) * per_conf > PD_LDS_BUDGET) G *= 2;
+    const int gpw = 64 / G;
+    const size_t lds = gpw * per_conf;
+    const double L = e->dm.L, half = 0.5 * L;
+    // a grid's first dimension holds 2^31 - 1 blocks
+    const long long XMAX = (1ll << 30) * gpw;
+    for (long long c0 = 0; c0 < nconf; c0 += XMAX) {
+        const long long nc = std::min(XMAX, nconf - c0);
+        PairDistArgs a{ pos_dev + (size_t)c0 * n, out + (size_t)c0 * B, nc, n,
+                        (int)B, L, half, (double)B / half };
+        const dim3 grid((unsigned)((nc + gpw - 1) / gpw));
+        switch (G) {
+        case 8: hipLaunchKernelGGL((pair_dist_kernel<8, OutT>), grid, dim3(64), lds, e->stream, a); break;
+        case 16: hipLaunchKernelGGL((pair_dist_kernel<16, OutT>), grid, dim3(64), lds, e->stream, a); break;
+        case 32: hipLaunchKernelGGL((pair_dist_kernel<32, OutT>), grid, dim3(64), lds, e->stream, a); break;
+        default: hipLaunchKernelGGL((pair_dist_kernel<64, OutT>), grid, dim3(64), lds, e->stream, a); break;
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int qmc_pair_dist_dev(qmc_engine *e, int64_t nconf,
+                                 const double *pos, int32_t num_bins,
+                                 uint32_t *counts)
+{
+    if (!e || !pos || !counts)
+        return fail("qmc_pair_dist_dev: null argument");
+    if (pair_dist_check("qmc_pair_dist_dev", nconf, num_bins)) return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    return pair_dist_launch(e, nconf, pos, num_bins, counts);
+}
+
+extern "C" int qmc_pair_dist_reduce_dev(qmc_engine *e, int64_t nconf,
+                                        const double *pos, const double *w,
+                                        int32_t num_bins, double *sums,
+                                        double *wsum)
+{
+    if (!e || !pos || !sums)
+        return fail("qmc_pair_dist_reduce_dev: null argument");
+    if (pair_dist_check("qmc_pair_dist_reduce_dev", nconf, num_bins)) return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n = (size_t)e->dm.n;
+    const long long tile = std::min<long long>(
+        std::max<long long>(nconf, 1),
+        std::min(PD_TILE, PD_SCRATCH_ELEMS / num_bins));
+    if (e->pd_hist.reserve((size_t)tile * num_bins)) return 1;
+    long long c0 = 0;
+    do {
+        const long long nc = std::min(tile, (long long)nconf - c0);
+        if (pair_dist_launch(e, nc, pos + (size_t)c0 * n, num_bins,
+                             e->pd_hist.get()))
+            return 1;
+        hipLaunchKernelGGL(obdm_reduce_kernel, dim3(num_bins + 1), dim3(256), 0,
+                           e->stream, e->pd_hist, w ? w + c0 : nullptr, nc,
+                           (int)num_bins, c0 > 0 ? 1 : 0, sums, wsum);
+        HIP_TRY(hipGetLastError());
+        c0 += tile;
+    } while (c0 < nconf);
+    return 0;
+}
+
+extern "C" int qmc_pair_dist(qmc_engine *e, int64_t nconf, const double *pos,
+                             int32_t num_bins, uint32_t *counts)
+{
+    if (!e || !pos || !counts) return fail("qmc_pair_dist: null argument");
+    if (pair_dist_check("qmc_pair_dist", nconf, num_bins)) return 1;
+    if (nconf == 0) return 0;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n = (size_t)e->dm.n, B = (size_t)num_bins;
+    const long long tile = std::max<long long>(
+        1, std::min<long long>(nconf, PD_SCRATCH_ELEMS / (long long)std::max(n, B)));
+    DevBuf<double> dpos;
+    DevBuf<uint32_t> dcnt;
+    if (dpos.alloc((size_t)tile * n) || dcnt.alloc((size_t)tile * B)) return 1;
+    for (long long c0 = 0; c0 < nconf; c0 += tile) {
+        const size_t nc = (size_t)std::min(tile, (long long)nconf - c0);
+        HIP_TRY(hipMemcpyAsync(dpos, pos + (size_t)c0 * n,
+                               nc * n * sizeof(double),
+                               hipMemcpyHostToDevice, e->stream));
+        if (pair_dist_launch(e, (long long)nc, dpos, num_bins, dcnt.get()))
+            return 1;
+        HIP_TRY(hipMemcpyAsync(counts + (size_t)c0 * B, dcnt,
+                               nc * B * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    return 0;
+}
+
+// Histogram sums of the CURRENT configurations of the chains: the resident
+// rows go to the kernel as they are (the particle order is irrelevant); the
+// chain state is only read.
+extern "C" int qmc_vmc_pair_dist(qmc_vmc *v, int32_t num_bins, double *out)
+{
+    if (!v || !out) return fail("qmc_vmc_pair_dist: null argument");
+    if (pair_dist_check("qmc_vmc_pair_dist", 0, num_bins)) return 1;
+    qmc_engine *e = v->eng;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t B = (size_t)num_bins;
+    if (e->pd_sums.reserve(2 * B)) return 1;
+    int rc = qmc_pair_dist_reduce_dev(e, v->W, v->pos, nullptr, num_bins,
+                                      e->pd_sums, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, e->pd_sums, 2 * B * sizeof(double),
                            hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return 0;

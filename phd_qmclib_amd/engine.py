@@ -57,6 +57,26 @@ def _current_device():
     return 0
 
 
+MAX_PAIR_DIST_BINS = 4096      # PD_MAX_BINS of csrc/qmc_pairdist.h
+
+
+def pair_distribution_bins(supercell_size, num_bins):
+    """Bin centres r_b = (b + 1/2) delta, delta = (L/2) / num_bins, of the
+    pair-distance histograms -> r[num_bins]."""
+    nb = ModelEngine._num_bins(num_bins)
+    delta = 0.5 * float(supercell_size) / nb
+    return (np.arange(nb) + 0.5) * delta
+
+
+def pair_distribution_norm(counts, boson_number, supercell_size):
+    """g2 = H L / (N (N - 1) delta) of (mean) histograms H[..., num_bins]: 1 on
+    average for uncorrelated uniform particles."""
+    counts = np.asarray(counts, dtype=np.float64)
+    n, L = int(boson_number), float(supercell_size)
+    delta = 0.5 * L / counts.shape[-1]
+    return counts * (L / (n * (n - 1) * delta))
+
+
 class DeviceBuffer:
     """A plain fp64 array in HBM (qmc_buffer_*): inputs / outputs of
     `ModelEngine.evaluate_dev` that stay resident across calls."""
@@ -339,6 +359,69 @@ class ModelEngine:
                 b.close()
         return sums[:, 0] / wsum[0]
 
+    @staticmethod
+    def _num_bins(num_bins):
+        nb = int(num_bins)
+        if nb != num_bins or not 1 <= nb <= MAX_PAIR_DIST_BINS:
+            raise ValueError('num_bins must be an integer in [1, %d]'
+                             % MAX_PAIR_DIST_BINS)
+        return nb
+
+    def pair_distribution(self, pos, num_bins):
+        """Pair-distance histogram of every configuration in pos[W, N]:
+        counts[W, num_bins] (uint32) of the unordered pairs over num_bins
+        uniform bins of the minimum-image distance in [0, L/2]; every row adds
+        up to N (N - 1) / 2.  `pair_distribution_norm` turns counts into
+        g2."""
+        pos = np.ascontiguousarray(pos, dtype=np.float64)
+        if pos.ndim != 2 or pos.shape[1] != self.num_particles:
+            raise ValueError('pos must have shape (W, boson_number)')
+        nb = self._num_bins(num_bins)
+        counts = np.zeros((pos.shape[0], nb), dtype=np.uint32)
+        check(self._lib.qmc_pair_dist(self._h, pos.shape[0], ptr(pos), nb,
+                                      ptr(counts, _lib._u32p)))
+        return counts
+
+    def pair_distribution_dev(self, nconf, pos_ptr, num_bins, counts_ptr):
+        """Asynchronous histograms on device-resident buffers (raw pointers):
+        pos[nconf, N] (fp64) -> counts[nconf, num_bins] (uint32)."""
+        check(self._lib.qmc_pair_dist_dev(self._h, int(nconf), pos_ptr,
+                                          int(num_bins), counts_ptr))
+
+    def pair_distribution_reduce_dev(self, nconf, pos_ptr, w_ptr, num_bins,
+                                     sums_ptr, wsum_ptr=0):
+        """Asynchronous weighted sums over the configurations, device buffers:
+        sums[num_bins, 2] = sum_c w_c H_c, sum_c w_c H_c^2 and wsum[0] =
+        sum_c w_c (w_ptr = 0: unit weights), in a fixed summation order."""
+        check(self._lib.qmc_pair_dist_reduce_dev(self._h, int(nconf), pos_ptr,
+                                                 w_ptr, int(num_bins),
+                                                 sums_ptr, wsum_ptr))
+
+    def pair_distribution_weighted(self, pos, weights, num_bins):
+        """sum_c w_c H_c / sum_c w_c over the configurations pos[W, N] (one
+        upload of the positions, the weighted reduction on the device)
+        -> mean histogram[num_bins]."""
+        pos = np.ascontiguousarray(pos, dtype=np.float64)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        nb = self._num_bins(num_bins)
+        if pos.ndim != 2 or pos.shape[1] != self.num_particles \
+                or w.shape != (pos.shape[0],):
+            raise ValueError('pos[W, boson_number] and weights[W] expected')
+        bufs = [DeviceBuffer(pos.shape, self.device).upload(pos),
+                DeviceBuffer(w.shape, self.device).upload(w),
+                DeviceBuffer((nb, 2), self.device),
+                DeviceBuffer((1,), self.device)]
+        try:
+            self.pair_distribution_reduce_dev(pos.shape[0], bufs[0].ptr,
+                                              bufs[1].ptr, nb, bufs[2].ptr,
+                                              bufs[3].ptr)
+            self.sync()
+            sums, wsum = bufs[2].download(), bufs[3].download()
+        finally:
+            for b in bufs:
+                b.close()
+        return sums[:, 0] / wsum[0]
+
 
 class VmcEnsemble:
     """W independent Metropolis chains resident on the GPU (qmc_vmc)."""
@@ -388,6 +471,15 @@ class VmcEnsemble:
         sh = self.engine._shifts(shifts)
         out = np.zeros((sh.size, 2))
         check(self._lib.qmc_vmc_obdm(self._h, sh.size, ptr(sh), ptr(out)))
+        return out
+
+    def pair_dist_parts(self, num_bins) -> np.ndarray:
+        """Sums over the chains of the pair-distance histogram H and of H^2
+        of the current configurations -> [num_bins, 2]; computed on the
+        resident rows, which are only read."""
+        nb = ModelEngine._num_bins(num_bins)
+        out = np.zeros((nb, 2))
+        check(self._lib.qmc_vmc_pair_dist(self._h, nb, ptr(out)))
         return out
 
     def get_state(self):

@@ -21,7 +21,8 @@ import attr
 import numpy as np
 
 from .. import utils
-from ..engine import DmcEnsemble, ModelEngine
+from ..engine import (DmcEnsemble, ModelEngine, pair_distribution_bins,
+                      pair_distribution_norm)
 from ..qmc_base import dmc as dmc_base
 from . import model
 
@@ -354,6 +355,24 @@ class Sampling:
         weight = np.asarray(state.props.weight, dtype=np.float64)[:nw]
         eng = model.core_funcs._engine(*self.model_spec.cfc_spec)
         return eng.one_body_density_weighted(pos, weight, shifts)
+
+    def pair_distribution(self, state: State, num_bins):
+        """Mixed estimate of the pair distribution function over the live
+        walkers of a State: sum_w W_w H_w / sum_w W_w, H the pair-distance
+        histogram of a walker (distances of qmc_base/utils.py:35-51), normalised
+        to g2 -> (r[num_bins], g2[num_bins]).  Slots beyond `num_walkers` do
+        not count.  The positions are uploaded once; the weighted reduction
+        runs on the device."""
+        nw = int(state.num_walkers)
+        confs = np.asarray(state.confs, dtype=np.float64)
+        pos = confs[:nw, model.SysConfSlot.pos, :]
+        weight = np.asarray(state.props.weight, dtype=np.float64)[:nw]
+        eng = model.core_funcs._engine(*self.model_spec.cfc_spec)
+        spec = self.model_spec
+        hist = eng.pair_distribution_weighted(pos, weight, num_bins)
+        return (pair_distribution_bins(spec.supercell_size, num_bins),
+                pair_distribution_norm(hist, spec.boson_number,
+                                       spec.supercell_size))
 
 
     @property

@@ -21,7 +21,7 @@ from .. import ideal
 
 __all__ = ['CSWFOptimizer', 'CFCSpec', 'OBFParams', 'Params', 'Spec', 'TBFParams',
            'SysConfSlot', 'SysConfDistType', 'DIST_RAND', 'DIST_REGULAR',
-           'core_funcs', 'PhysicalFuncs']
+           'core_funcs', 'PhysicalFuncs', 'pair_distribution_bins']
 
 import enum
 
@@ -369,6 +369,7 @@ class PhysicalFuncs:
         wf_abs_log(sys_conf)              (ns,nop)->()
         energy(sys_conf)                  (ns,nop)->()
         one_body_density(sz, sys_conf)    (),(ns,nop)->()
+        pair_distribution(num_bins, sys_conf)  (ns,nop)->(B)
         fourier_density(kz_set, sys_conf) (nkz),(ns,nop)->(nkz)   complex
 
     The loop dimensions broadcast as NumPy's; the whole broadcast batch goes to
@@ -429,6 +430,19 @@ class PhysicalFuncs:
         out = g1[conf_idx, inv.reshape(-1)[sz_idx]]
         return out[()]
 
+    def pair_distribution(self, num_bins, sys_conf):
+        """Pair distribution function g2(r_b) of every configuration at the
+        `num_bins` bin centres of `pair_distribution_bins`: the histogram of
+        the minimum-image pair distances (qmc_base/utils.py:35-51) times
+        L / (N (N - 1) delta).  `num_bins` is a scalar (it fixes the core
+        dimension B); the loop dimensions of sys_conf broadcast."""
+        from ..engine import pair_distribution_norm
+        loop, pos = self._conf_batch(sys_conf)
+        counts = self._engine().pair_distribution(pos, num_bins)
+        mp = self.cfc_spec_nt.model_params
+        g2 = pair_distribution_norm(counts, mp.boson_number, mp.supercell_size)
+        return g2.reshape(loop + g2.shape[-1:])
+
     def fourier_density(self, kz_set, sys_conf):
         """Fourier density component with momentum k: sum_i exp(i k z_i)."""
         kz_set = np.asarray(kz_set, dtype=np.float64)
@@ -443,6 +457,14 @@ class PhysicalFuncs:
         z = np.broadcast_to(pos, loop + pos.shape[-1:])
         ang = kz[..., :, np.newaxis] * z[..., np.newaxis, :]
         return np.cos(ang).sum(axis=-1) + 1j * np.sin(ang).sum(axis=-1)
+
+
+def pair_distribution_bins(model_spec, num_bins):
+    """Bin centres r_b = (b + 1/2) delta, delta = (L/2) / num_bins, of the
+    pair distribution function of a model Spec (or CFCSpec) -> r[num_bins]."""
+    from ..engine import pair_distribution_bins as bins
+    mp = getattr(model_spec, 'model_params', model_spec)
+    return bins(mp.supercell_size, num_bins)
 
 
 class CSWFOptimizer:

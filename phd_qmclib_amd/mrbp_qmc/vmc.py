@@ -17,7 +17,8 @@ import attr
 import numpy as np
 
 from .. import utils
-from ..engine import ModelEngine, VmcEnsemble
+from ..engine import (ModelEngine, VmcEnsemble, pair_distribution_bins,
+                      pair_distribution_norm)
 from ..qmc_base import vmc as vmc_base
 from . import model
 
@@ -315,6 +316,22 @@ class EnsembleSampling:
         var = np.maximum(parts[:, 1] / w - mean ** 2, 0.0)
         stderr = np.sqrt(var / max(w - 1, 1))
         return shifts, mean, stderr
+
+    def pair_distribution(self, num_bins):
+        """Pair distribution function g2(r) over the chains' current
+        configurations -> (r, mean, stderr) at the bin centres; computed on the
+        rows resident on the device (no position is copied to the host, the
+        chains are not touched).  The standard error is that of the mean over
+        the chains."""
+        parts = self.ensemble.pair_dist_parts(num_bins)
+        w = self.num_chains
+        n, L = self.model_spec.boson_number, self.model_spec.supercell_size
+        mean = parts[:, 0] / w
+        var = np.maximum(parts[:, 1] / w - mean ** 2, 0.0)
+        stderr = np.sqrt(var / max(w - 1, 1))
+        return (pair_distribution_bins(L, num_bins),
+                pair_distribution_norm(mean, n, L),
+                pair_distribution_norm(stderr, n, L))
 
     def close(self):
         self.ensemble.close()

@@ -16,6 +16,7 @@ vmc.init_random(seed=0)
 for blk in islice(vmc.blocks(64), 2):
     print(blk.energy.mean() / 64, blk.accept_rate.mean())
 shifts, g1, g1_err = vmc.one_body_density(np.linspace(0, 32, 17))   # one-body density matrix g1(s)
+r, g2, g2_err = vmc.pair_distribution(64)                            # pair distribution function g2(r)
 dmc = mrbp_qmc.dmc.Sampling(spec, time_step=6.25e-4, max_num_walkers=4400,
                             target_num_walkers=4096, num_walkers_control_factor=0.5, rng_seed=1)
 confs = np.zeros((4096, 2, 64)); confs[:, 0] = vmc.confs()
