@@ -413,6 +413,21 @@ int qmc_dmc_run_block_est(qmc_dmc *d, int64_t nsteps, int eval_estimators,
 int qmc_dmc_est_begin_block(qmc_dmc *d, int64_t nsteps);
 int qmc_dmc_step_estimators(qmc_dmc *d, int64_t step_idx);
 int qmc_dmc_est_iter_dev(qmc_dmc *d, double **iter_ssf, double **iter_density);
+/* Pair distribution g2(r) as a third block estimator (an extension: the
+ * reference has none).  Per time step and bin, the pair-distance histograms
+ * (as qmc_pair_dist: num_bins uniform bins over [0, L/2]) summed over the
+ * yielded walkers: mixed, or pure with the per-walker rows carried through the
+ * cloning table for pfw steps and divided by min(step + 1, pfw), the S(k)
+ * transport.  num_bins in [1, 256]; 0 switches it off.  Set on its own:
+ * neither this call nor qmc_dmc_set_estimators disturbs the other's settings,
+ * and run_block_est / est_begin_block / step_estimators evaluate whichever of
+ * the three are set.  read_pair_dist copies the first nsteps rows of the last
+ * estimator block to the host, iter_out[nsteps][num_bins] (synchronises);
+ * rows of a block run with eval_estimators == 0 are zero.  The rows are not
+ * part of the walker record: single-GPU only. */
+int qmc_dmc_set_pair_dist_estimator(qmc_dmc *d, int32_t num_bins, int32_t pure,
+                                    int64_t pfw);
+int qmc_dmc_read_pair_dist(qmc_dmc *d, int64_t nsteps, double *iter_out);
 /* The yielded ("actual") State after the last step (qmc_base/dmc.py:773-780):
  * confs[maxw][2][N], energy/weight[maxw], mask[maxw], cloning_ref[maxw];
  * scalars[5] = energy, weight, ref_energy, accum_energy, num_walkers. */

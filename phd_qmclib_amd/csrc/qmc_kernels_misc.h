@@ -295,6 +295,8 @@ struct EstArgs {
     int pure;
     double scale;             // S(k): 4 / L (angle k_m z = (pi/2) * m * scale * z)
                               // density: bin size L / num_bins
+                              // g2(r): supercell size L
+    double scale2;            // g2(r): 1 / delta = num_bins / (L / 2)
 };
 
 static constexpr int EST_BLOCKS = 1024;

@@ -46,6 +46,7 @@
 #pragma once
 
 #include "qmc_device.h"
+#include "qmc_kernels_misc.h"
 
 static constexpr int PD_MAX_BINS = 4096;
 // LDS a wavefront may take for positions and histograms of its groups
@@ -119,4 +120,115 @@ pair_dist_kernel(PairDistArgs a)
     OutT *out = (OutT *)a.out + (size_t)(live ? c : 0) * B;
     for (int b = gl; b < B; b += G)
         if (live) out[b] = (OutT)h[b];
+}
+
+// ---- g2(r) as a DMC block estimator ------------------------------------
+// The pair histogram of every yielded walker of a time step, mixed or pure
+// (forward walking), in the frame of the S(k) and density estimators
+// (qmc_kernels_misc.h: EstArgs, est_reduce_kernel).  Walker s carries the
+// configuration of its parent, parents[ref[s]]; H_s is its histogram as above.
+//
+//   mixed   iter[t][b] = sum_{s live} H_s[b]
+//   pure    aux_t[s][b] = aux_{t-1}[ref_t[s]][b] + (t < pfw ? H_s[b] : 0)
+//           iter[t][b] = sum_{s live} aux_t[s][b] / min(t + 1, pfw)
+//
+// The per-walker rows travel through the cloning table, as the S(k) parts do
+// (a clone inherits the history of its parent, a dead walker's history ends);
+// the slot-wise copy and the ever-growing mixed buffer of the density
+// estimator are quirks reproduced there for parity and have no place here.
+//
+// One wavefront per walker slot, grid-striding over the live slots; particle
+// i = lane + 64 p in pass p, the rotation pair loop of pair_dist_kernel<64>.
+// Positions and histogram of a wavefront live in LDS and are only touched by
+// that wavefront, so wave-level fences order them (as dmc_density_kernel).
+// Every quantity is an integer held in a double, exact below 2^53: neither the
+// lane sums, nor the block reduction, nor est_reduce_kernel can round, and the
+// one division is of an integer by an integer.  fp64 whatever fast_math says.
+static constexpr int PD_EST_MAXN = 512;     // particles (the engine's limit)
+
+__global__ void __launch_bounds__(BLOCK) dmc_pair_dist_kernel(EstArgs a)
+{
+    constexpr int NWAVE = BLOCK / 64;
+    static_assert(PD_EST_MAXN >= EST_MAXK,
+                  "the block reduction reuses the position rows");
+    __shared__ double zs[NWAVE][PD_EST_MAXN];
+    __shared__ unsigned hs[NWAVE][EST_MAXK];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n = a.n, B = a.K;
+    double *z = zs[wave];
+    unsigned *h = hs[wave];
+    PairDistArgs g;
+    g.pos = nullptr; g.out = nullptr; g.nconf = 0;
+    g.n = n; g.nbins = B;
+    g.L = a.scale; g.half = 0.5 * a.scale; g.inv_delta = a.scale2;
+    const long long nw = a.ctl->nw;
+    const long long wstride = (long long)gridDim.x * NWAVE;
+    double acc[EST_CH];
+#pragma unroll
+    for (int c = 0; c < EST_CH; ++c) acc[c] = 0.0;
+    const bool count_now = !a.pure || a.step_idx < a.pfw;
+    const int npass = (n + 63) / 64;
+    const int kfull = (n - 1) / 2;              // offsets every particle takes
+    for (long long s = (long long)blockIdx.x * NWAVE + wave; s < nw;
+         s += wstride) {
+        const long long par = a.ref[s];
+        if (count_now) {
+            const double *row = a.ppos + (size_t)par * n;
+            for (int p = 0; p < npass; ++p) {
+                const int i = lane + 64 * p;
+                const double zw = wrap_box(i < n ? row[i] : 0.0, g.L);
+                if (i < n) z[i] = zw;
+            }
+            for (int b = lane; b < B; b += 64) h[b] = 0u;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            for (int p = 0; p < npass; ++p) {
+                const int i = lane + 64 * p;
+                const int ic = min(i, n - 1);
+                const bool own = i < n;
+                const double zi = z[ic];
+#pragma unroll 4
+                for (int k = 1; k <= kfull; ++k) {
+                    int j = ic + k;
+                    j = (j >= n) ? j - n : j;
+                    pd_count(h, zi, z[j], g, own);
+                }
+                if (!(n & 1)) {
+                    // even N: the lower half of the particles takes the
+                    // offset N/2 (pair_dist_kernel)
+                    const int j = min(ic + n / 2, n - 1);
+                    pd_count(h, zi, z[j], g, own && i < n / 2);
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+#pragma unroll
+        for (int c = 0; c < EST_CH; ++c) {
+            const int b = c * 64 + lane;
+            if (c * 64 >= B) break;
+            if (b < B) {
+                double v = count_now ? (double)h[b] : 0.0;
+                if (a.pure) {
+                    v += a.aux_prev[(size_t)par * B + b];
+                    a.aux_act[(size_t)s * B + b] = v;
+                }
+                acc[c] += v;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();    // z and h are rewritten next
+    }
+    // fixed-order block reduction (the position rows are free now), then
+    // est_reduce_kernel sums the blocks in index order
+    __syncthreads();
+    double *red = &zs[0][0];                    // [NWAVE][EST_MAXK]
+#pragma unroll
+    for (int c = 0; c < EST_CH; ++c) red[wave * EST_MAXK + c * 64 + lane] = acc[c];
+    __syncthreads();
+    for (int b = threadIdx.x; b < B; b += BLOCK) {
+        double t = 0.0;
+        for (int w = 0; w < NWAVE; ++w) t += red[w * EST_MAXK + b];
+        a.partial[(size_t)blockIdx.x * B + b] = t;
+    }
 }

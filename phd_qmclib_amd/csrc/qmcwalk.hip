@@ -1293,7 +1293,7 @@ extern "C" int qmc_vmc_ssf(qmc_vmc *v, int32_t num_modes, double *out)
     a.ppos = v->pos; a.ref = nullptr; a.ctl = nullptr;
     a.aux_prev = nullptr; a.aux_act = nullptr; a.partial = v->ssf_partial;
     a.maxw = v->W; a.step_idx = 0; a.pfw = 0; a.n = e->dm.n; a.K = M;
-    a.pure = 0; a.scale = 4.0 / e->dm.L;
+    a.pure = 0; a.scale = 4.0 / e->dm.L; a.scale2 = 0.0;
     if (M <= 64) {
         const size_t lds = (size_t)(BLOCK / 64) * SsfShape<8>::WAVE_DOUBLES *
                            sizeof(double);
@@ -1753,7 +1753,34 @@ struct qmc_dmc {
     DevBuf<double> iter_ssf, iter_dens;          // per-step outputs, grown on demand
     long long est_block_steps = 0;  // steps of the estimator block in progress
     int est_last_act = 1;           // aux buffer the last estimator step wrote
+    // pair distribution estimator (qmc_pairdist.h: dmc_pair_dist_kernel),
+    // set on its own by qmc_dmc_set_pair_dist_estimator; pd_bins == 0: off
+    int pd_bins = 0, pd_pure = 0;
+    long long pd_pfw = 1;
+    DevBuf<double> pd_aux[2];                    // [maxw][pd_bins] (pure only)
+    DevBuf<double> iter_pd;                      // [steps][pd_bins]
+    bool any_est() const { return have_est || pd_bins > 0; }
 };
+
+// est_partial holds the block partial sums of one estimator at a time:
+// [EST_BLOCKS][max(3 M, B, B_g2)] over the estimators that are set.
+static int dmc_size_est_partial(qmc_dmc *d)
+{
+    size_t kc = 0;
+    if (d->have_est)
+        kc = (size_t)std::max(d->est.num_modes * 3, d->est.num_bins);
+    kc = std::max(kc, (size_t)d->pd_bins);
+    d->est_partial.release();
+    return kc ? d->est_partial.alloc(EST_BLOCKS * kc) : 0;
+}
+
+static void dmc_drop_pair_dist(qmc_dmc *d)
+{
+    d->pd_aux[0].release();
+    d->pd_aux[1].release();
+    d->iter_pd.release();
+    d->pd_bins = 0; d->pd_pure = 0; d->pd_pfw = 1;
+}
 
 static int dmc_reserve_series(qmc_dmc *d, long long nsteps)
 {
@@ -2230,16 +2257,84 @@ extern "C" int qmc_dmc_set_estimators(qmc_dmc *d, const qmc_dmc_est_params *p)
     if (p->num_bins > 0)
         for (int k = 0; k < 2 && !failed; ++k)
             failed = d->dens_aux[k].alloc(W * (size_t)p->num_bins) != 0;
-    size_t kc = (size_t)(p->num_modes * 3 > p->num_bins ? p->num_modes * 3
-                                                        : p->num_bins);
-    if (want && !failed)
-        failed = d->est_partial.alloc(EST_BLOCKS * kc) != 0;
     if (failed) {
         drop();
         d->est.num_modes = d->est.num_bins = 0;
+        // (the pair distribution estimator keeps its settings and gets the
+        // partial sums it needs back)
+        if (dmc_size_est_partial(d)) dmc_drop_pair_dist(d);
         return 1;            // (alloc has set the message)
     }
     d->have_est = want;
+    if (dmc_size_est_partial(d)) {
+        // nothing can run without the partial sums: everything off
+        drop();
+        d->est.num_modes = d->est.num_bins = 0;
+        d->have_est = false;
+        dmc_drop_pair_dist(d);
+        return 1;
+    }
+    return 0;
+}
+
+// The pair distribution estimator is set on its own: the S(k) / density
+// settings and buffers stay as they are (and the other way round).
+extern "C" int qmc_dmc_set_pair_dist_estimator(qmc_dmc *d, int32_t num_bins,
+                                               int32_t pure, int64_t pfw)
+{
+    if (!d) return fail("qmc_dmc_set_pair_dist_estimator: null argument");
+    if (num_bins < 0 || num_bins > EST_MAXK)
+        return fail("qmc_dmc_set_pair_dist_estimator: num_bins must be in "
+                    "[0, 256]");
+    if (num_bins > 0 && pure && pfw < 1)
+        return fail("qmc_dmc_set_pair_dist_estimator: pfw must be >= 1");
+    static_assert(PD_EST_MAXN >= 512, "every engine's boson_number fits");
+    qmc_engine *e = d->eng;
+    HIP_TRY(hipSetDevice(e->device));
+    dmc_drop_pair_dist(d);
+    d->est_block_steps = 0;
+    bool failed = false;
+    if (num_bins > 0 && pure)
+        for (int k = 0; k < 2 && !failed; ++k)
+            failed = d->pd_aux[k].alloc((size_t)d->maxw * (size_t)num_bins) != 0;
+    if (!failed) {
+        d->pd_bins = num_bins; d->pd_pure = pure ? 1 : 0;
+        d->pd_pfw = pure ? pfw : 1;
+        failed = dmc_size_est_partial(d) != 0;
+    }
+    if (failed) {
+        dmc_drop_pair_dist(d);
+        // (the other two get their partial sums back; if even that fails
+        // they are off as well)
+        if (dmc_size_est_partial(d)) {
+            for (int k = 0; k < 2; ++k) {
+                d->ssf_aux[k].release();
+                d->dens_aux[k].release();
+            }
+            d->est.num_modes = d->est.num_bins = 0;
+            d->have_est = false;
+        }
+        return 1;            // (alloc has set the message)
+    }
+    return 0;
+}
+
+extern "C" int qmc_dmc_read_pair_dist(qmc_dmc *d, int64_t nsteps,
+                                      double *iter_out)
+{
+    if (!d || !iter_out) return fail("qmc_dmc_read_pair_dist: null argument");
+    if (d->pd_bins <= 0)
+        return fail("qmc_dmc_read_pair_dist: the pair distribution estimator "
+                    "is not set");
+    if (nsteps <= 0 || nsteps > d->est_block_steps)
+        return fail("qmc_dmc_read_pair_dist: nsteps outside the last "
+                    "estimator block");
+    qmc_engine *e = d->eng;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpyAsync(iter_out, d->iter_pd,
+                           (size_t)nsteps * (size_t)d->pd_bins * 8,
+                           hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return 0;
 }
 
@@ -2255,6 +2350,7 @@ static int dmc_enqueue_estimators(qmc_dmc *d, long long step_idx)
     a.ppos = d->pos[par]; a.ref = d->ref; a.ctl = d->ctl;
     a.maxw = d->maxw; a.step_idx = step_idx; a.n = e->dm.n;
     a.partial = d->est_partial;
+    a.scale2 = 0.0;
     if (d->est.num_modes > 0) {
         const int M = d->est.num_modes;
         a.aux_prev = d->ssf_aux[prev]; a.aux_act = d->ssf_aux[act];
@@ -2294,6 +2390,23 @@ static int dmc_enqueue_estimators(qmc_dmc *d, long long step_idx)
                            0, e->stream, d->est_partial, EST_BLOCKS, B, div,
                            d->iter_dens + (size_t)step_idx * B);
     }
+    if (d->pd_bins > 0) {
+        const int B = d->pd_bins;
+        // (mixed: no per-walker rows are kept)
+        a.aux_prev = d->pd_pure ? d->pd_aux[prev].get() : nullptr;
+        a.aux_act = d->pd_pure ? d->pd_aux[act].get() : nullptr;
+        a.K = B; a.pure = d->pd_pure; a.pfw = d->pd_pfw;
+        a.scale = e->dm.L;
+        a.scale2 = (double)B / (0.5 * e->dm.L);     // as pair_dist_launch
+        hipLaunchKernelGGL(dmc_pair_dist_kernel, dim3(EST_BLOCKS), dim3(BLOCK),
+                           0, e->stream, a);
+        double div = 1.0;
+        if (a.pure) div = step_idx < a.pfw ? (double)(step_idx + 1)
+                                           : (double)a.pfw;
+        hipLaunchKernelGGL(est_reduce_kernel, dim3((B + 31) / 32), dim3(256),
+                           0, e->stream, d->est_partial, EST_BLOCKS, B, div,
+                           d->iter_pd + (size_t)step_idx * B);
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -2314,6 +2427,14 @@ static int dmc_est_begin_block(qmc_dmc *d, long long nsteps)
         if (M3) HIP_TRY(hipMemsetAsync(d->ssf_aux[k], 0, W * M3 * 8, e->stream));
         if (B) HIP_TRY(hipMemsetAsync(d->dens_aux[k], 0, W * B * 8, e->stream));
     }
+    if (d->pd_bins > 0) {
+        const size_t PB = (size_t)d->pd_bins, need_p = (size_t)nsteps * PB;
+        if (d->iter_pd.reserve(need_p)) return 1;
+        HIP_TRY(hipMemsetAsync(d->iter_pd, 0, need_p * 8, e->stream));
+        if (d->pd_pure)
+            for (int k = 0; k < 2; ++k)
+                HIP_TRY(hipMemsetAsync(d->pd_aux[k], 0, W * PB * 8, e->stream));
+    }
     d->est_block_steps = nsteps;
     d->est_last_act = 1;
     return 0;
@@ -2331,7 +2452,7 @@ extern "C" int qmc_dmc_run_block_est(qmc_dmc *d, int64_t nsteps,
         return fail("qmc_dmc_run_block_est: ensemble was created for "
                     "external_reduce; drive it with est_begin_block / "
                     "step_local / step_finish / step_estimators");
-    if (!d->have_est)
+    if (!d->any_est())
         return qmc_dmc_run_block(d, nsteps, energy, weight, num_walkers,
                                  ref_energy, accum_energy);
     qmc_engine *e = d->eng;
@@ -2367,7 +2488,7 @@ extern "C" int qmc_dmc_run_block_est(qmc_dmc *d, int64_t nsteps,
 extern "C" int qmc_dmc_est_begin_block(qmc_dmc *d, int64_t nsteps)
 {
     if (!d) return fail("qmc_dmc_est_begin_block: null argument");
-    if (!d->have_est)
+    if (!d->any_est())
         return fail("qmc_dmc_est_begin_block: no estimators are set");
     if (nsteps <= 0) return fail("qmc_dmc_est_begin_block: nsteps must be >= 1");
     HIP_TRY(hipSetDevice(d->eng->device));
@@ -2377,7 +2498,7 @@ extern "C" int qmc_dmc_est_begin_block(qmc_dmc *d, int64_t nsteps)
 extern "C" int qmc_dmc_step_estimators(qmc_dmc *d, int64_t step_idx)
 {
     if (!d) return fail("qmc_dmc_step_estimators: null argument");
-    if (!d->have_est)
+    if (!d->any_est())
         return fail("qmc_dmc_step_estimators: no estimators are set");
     if (step_idx < 0 || step_idx >= d->est_block_steps)
         return fail("qmc_dmc_step_estimators: step index outside the block "

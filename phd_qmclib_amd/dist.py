@@ -164,6 +164,12 @@ class DistributedDmc:
         population lives on this rank alone whatever the process group's size
         (bench.py: the one-GPU strong-scaling reference timed by rank 0 inside
         a multi-rank run); no collective is issued."""
+        if getattr(ensemble, 'pair_dist_bins', 0):
+            raise NotImplementedError(
+                'the pair distribution estimator is single-GPU only: its '
+                'forward-walking rows are not part of the walker record that '
+                'the population rebalance moves between ranks; switch it off '
+                '(set_pair_dist_estimator(0)) for a distributed run')
         self.ens = ensemble
         self.n = int(num_particles)
         self.device = torch.device(device)

@@ -686,6 +686,24 @@ class DmcEnsemble:
             ptr(nw, _u64p), ptr(r), ptr(a), ptr(ssf), ptr(dens)))
         return DmcSeries(e, w, nw, r, a), ssf, dens
 
+    def set_pair_dist_estimator(self, num_bins, pure=False, pfw=1):
+        """Enable the pair distribution estimator g2(r) of the estimator
+        blocks: `num_bins` bins over [0, L/2] (1..256; 0 disables it), mixed
+        or pure with forward-walking length `pfw`.  Independent of
+        `set_estimators`."""
+        nb = int(num_bins)
+        check(self._lib.qmc_dmc_set_pair_dist_estimator(
+            self._h, nb, int(bool(pure)), int(pfw)))
+        self.pair_dist_bins = nb
+
+    def read_pair_dist(self, nsteps: int) -> np.ndarray:
+        """Rows of the last estimator block -> iter_pair_dist[nsteps, B]:
+        per time step the pair histograms summed over the walkers (pure: the
+        forward-walking rows over min(step + 1, pfw))."""
+        out = np.zeros((int(nsteps), getattr(self, 'pair_dist_bins', 0)))
+        check(self._lib.qmc_dmc_read_pair_dist(self._h, int(nsteps), ptr(out)))
+        return out
+
     def read_series(self, nsteps: int) -> DmcSeries:
         e, w = np.zeros(nsteps), np.zeros(nsteps)
         nw = np.zeros(nsteps, dtype=np.uint64)

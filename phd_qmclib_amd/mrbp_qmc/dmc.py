@@ -13,6 +13,9 @@ reproduces the reference's branching weight, True uses the
 parent's energy.  The density / S(k) estimators (mixed and pure /
 forward-walking) run on the device after every kept
 time step and reproduce the reference's semantics, per-block resets included.
+The pair distribution g2(r) is a third such estimator and an extension (the
+reference has none): its forward walking goes through the cloning table, as
+that of S(k).
 """
 import typing as t
 from math import pi, sqrt
@@ -26,8 +29,8 @@ from ..engine import (DmcEnsemble, ModelEngine, pair_distribution_bins,
 from ..qmc_base import dmc as dmc_base
 from . import model
 
-__all__ = ['CFCSpec', 'DDFParams', 'DensityEstSpec', 'Sampling', 'SSFEstSpec',
-           'State', 'StateError']
+__all__ = ['CFCSpec', 'DDFParams', 'DensityEstSpec', 'PairDistEstSpec',
+           'Sampling', 'SSFEstSpec', 'State', 'StateError']
 
 State = dmc_base.State
 
@@ -89,6 +92,20 @@ class SSFEstSpec:
 
 
 @attr.s(auto_attribs=True, frozen=True)
+class PairDistEstSpec:
+    """Pair distribution g2(r) as a block estimator: `num_bins` uniform bins
+    over [0, L/2] (1..256); pure (forward walking over `pfw_num_time_steps`
+    steps) or mixed."""
+    num_bins: int
+    as_pure_est: bool = True
+    pfw_num_time_steps: t.Optional[int] = None
+
+    def __attrs_post_init__(self):
+        if self.pfw_num_time_steps is None:
+            object.__setattr__(self, 'pfw_num_time_steps', 99999999)
+
+
+@attr.s(auto_attribs=True, frozen=True)
 class Sampling:
     """A class to realize a DMC sampling (mrbp_qmc/dmc.py:143-160)."""
 
@@ -103,6 +120,7 @@ class Sampling:
     jit_parallel: bool = True
     jit_fastmath: bool = False
     fix_stale_energy: bool = False
+    pair_dist_est_spec: t.Optional[PairDistEstSpec] = None
 
     def __attrs_post_init__(self):
         if self.rng_seed is None:
@@ -142,6 +160,15 @@ class Sampling:
             raise TypeError('the density spec has no been specified')
         return np.linspace(0, self.model_spec.supercell_size,
                            self.density_est_spec.num_bins + 1)
+
+    @property
+    def pair_dist_bins(self) -> np.ndarray:
+        """Bin centres r_b of the pair distribution estimator."""
+        if self.pair_dist_est_spec is None:
+            raise TypeError('the pair distribution spec has not been '
+                            'specified')
+        return pair_distribution_bins(self.model_spec.supercell_size,
+                                      self.pair_dist_est_spec.num_bins)
 
     @property
     def cfc_spec(self) -> CFCSpec:
@@ -286,8 +313,12 @@ class Sampling:
         nts = int(num_time_steps_block)
         eng, ens = self._start(ini_state)
         dp, sp = self.density_params, self.ssf_params
-        with_est = not (dp.assume_none and sp.assume_none)
-        if with_est:
+        pd = self.pair_dist_est_spec
+        with_est = not (dp.assume_none and sp.assume_none) or pd is not None
+        if pd is not None:
+            ens.set_pair_dist_estimator(pd.num_bins, pd.as_pure_est,
+                                        pd.pfw_num_time_steps)
+        if not (dp.assume_none and sp.assume_none):
             ens.set_estimators(
                 0 if sp.assume_none else sp.num_modes, sp.as_pure_est,
                 sp.pfw_num_time_steps,
@@ -296,12 +327,14 @@ class Sampling:
         block_idx = 0
         try:
             while True:
-                iter_ssf = iter_density = None
+                iter_ssf = iter_density = iter_pair_dist = None
                 if with_est:
                     # estimators only once the burn-in blocks are over
                     # (qmc_base/dmc.py:916, 928)
                     ser, iter_ssf, iter_density = ens.run_block_est(
                         nts, block_idx >= burn_in_blocks)
+                    if pd is not None:
+                        iter_pair_dist = ens.read_pair_dist(nts)
                 else:
                     ser = ens.run_block(nts)
                 props = dmc_base.PropsData(ser.energy, ser.weight,
@@ -309,7 +342,7 @@ class Sampling:
                                            ser.accum_energy)
                 last = self._to_state(ens.get_state())
                 yield dmc_base.SamplingBlock(props, iter_density, iter_ssf,
-                                             last)
+                                             last, iter_pair_dist)
                 block_idx += 1
         finally:
             ens.close()

@@ -13,8 +13,8 @@ from ..qmc_exec import proc as proc_base
 from . import dmc, model
 from .vmc_exec import ModelSysConfSpec, _as_int, _opt
 
-__all__ = ['DensityEstSpec', 'ModelSysConfSpec', 'Proc', 'ProcInput',
-           'ProcResult', 'SSFEstSpec']
+__all__ = ['DensityEstSpec', 'ModelSysConfSpec', 'PairDistEstSpec', 'Proc',
+           'ProcInput', 'ProcResult', 'SSFEstSpec']
 
 ProcInputError = proc_base.ProcInputError
 
@@ -32,6 +32,14 @@ class SSFEstSpec:
     """dmc_exec/proc.py:84-94."""
     num_modes: int = attr.ib(converter=_as_int,
                              validator=attr.validators.instance_of(int))
+    as_pure_est: bool = attr.ib(default=True, converter=bool)
+
+
+@attr.s(auto_attribs=True, frozen=True)
+class PairDistEstSpec:
+    """Pair distribution g2(r) (an extension; dmc.PairDistEstSpec)."""
+    num_bins: int = attr.ib(converter=_as_int,
+                            validator=attr.validators.instance_of(int))
     as_pure_est: bool = attr.ib(default=True, converter=bool)
 
 
@@ -87,6 +95,7 @@ class Proc:
     jit_parallel: bool = attr.ib(default=True, converter=bool)
     jit_fastmath: bool = attr.ib(default=False, converter=bool)
     verbose: bool = attr.ib(default=False, converter=bool)
+    pair_dist_spec: t.Optional[t.Any] = None
 
     @classmethod
     def from_config(cls, config: t.Mapping):
@@ -112,8 +121,14 @@ class Proc:
             ssf_cfg = dict(ssf_cfg)
             ssf_cfg.pop('pfw_num_time_steps', None)
             ssf = SSFEstSpec(**ssf_cfg)
+        pd_cfg = cfg.pop('pair_dist_spec', None)
+        pair_dist = None
+        if pd_cfg is not None:
+            pd_cfg = dict(pd_cfg)
+            pd_cfg.pop('pfw_num_time_steps', None)
+            pair_dist = PairDistEstSpec(**pd_cfg)
         return cls(model_spec=model_spec, density_spec=dens, ssf_spec=ssf,
-                   **cfg)
+                   pair_dist_spec=pair_dist, **cfg)
 
     def as_config(self):
         return attr.asdict(self, filter=attr.filters.exclude(type(None)))
@@ -126,12 +141,20 @@ class Proc:
     def should_eval_ssf(self):
         return self.ssf_spec is not None
 
+    @property
+    def should_eval_pair_dist(self):
+        return self.pair_dist_spec is not None
+
     @functools.cached_property
     def sampling(self) -> dmc.Sampling:
         """dmc_exec/proc.py:336-371: the forward walking of the pure
         estimators spans one block."""
         pfw = self.num_time_steps_block
-        dens = ssf = None
+        dens = ssf = pair_dist = None
+        if self.should_eval_pair_dist:
+            pair_dist = dmc.PairDistEstSpec(self.pair_dist_spec.num_bins,
+                                            self.pair_dist_spec.as_pure_est,
+                                            pfw)
         if self.should_eval_density:
             dens = dmc.DensityEstSpec(self.density_spec.num_bins,
                                       self.density_spec.as_pure_est, pfw)
@@ -141,7 +164,8 @@ class Proc:
         return dmc.Sampling(self.model_spec, self.time_step,
                             self.max_num_walkers, self.target_num_walkers,
                             self.num_walkers_control_factor, self.rng_seed,
-                            density_est_spec=dens, ssf_est_spec=ssf)
+                            density_est_spec=dens, ssf_est_spec=ssf,
+                            pair_dist_est_spec=pair_dist)
 
     def build_result(self, state, data):
         return ProcResult(state, self, data)

@@ -92,6 +92,8 @@ class SamplingBlock(t.NamedTuple):
     iter_density: t.Optional[np.ndarray]
     iter_ssf: t.Optional[np.ndarray] = None
     last_state: t.Optional[State] = None
+    #: pair histograms per time step [nts, num_bins] (an extension: g2(r))
+    iter_pair_dist: t.Optional[np.ndarray] = None
 
 
 class SamplingStateDataBlock(t.NamedTuple):

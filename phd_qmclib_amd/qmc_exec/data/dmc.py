@@ -11,7 +11,8 @@ import numpy as np
 
 from ...stats import reblock
 
-__all__ = ['DensityBlocks', 'EnergyBlocks', 'NumWalkersBlocks', 'PropBlocks',
+__all__ = ['DensityBlocks', 'EnergyBlocks', 'NumWalkersBlocks',
+           'PairDistBlocks', 'PropBlocks',
            'SSFBlocks', 'SSFPartBlocks',
            'PropsDataBlocks', 'PropsDataSeries', 'SamplingData', 'UnWeightedPropBlocks',
            'WeightBlocks']
@@ -188,6 +189,34 @@ class DensityBlocks(SetPropBlocks):
 
 
 @attr.s(auto_attribs=True, frozen=True)
+class PairDistBlocks(SetPropBlocks):
+    """Pair-distance histograms in blocks (an extension: the reference has no
+    g2): totals[num_blocks, num_bins] are sums over walkers (and, for the
+    mixed estimator, over the time steps of a block) of the integer
+    histograms; `pair_distribution` normalises their weighted mean to g2(r)."""
+    totals: np.ndarray
+    weight_totals: np.ndarray
+
+    @classmethod
+    def from_data(cls, num_time_steps_block, pair_dist_data, props_data,
+                  reduce_data=True, as_pure_est=True,
+                  pure_est_reduce_factor=None):
+        return cls(*_est_totals(num_time_steps_block, pair_dist_data,
+                                props_data.weight, reduce_data, as_pure_est,
+                                pure_est_reduce_factor))
+
+    def pair_distribution(self, model_spec):
+        """-> (r[num_bins], g2[num_bins], g2_err[num_bins]): bin centres, the
+        weighted mean histogram normalised to g2 and its error."""
+        from ...engine import pair_distribution_bins, pair_distribution_norm
+        n, size = model_spec.boson_number, model_spec.supercell_size
+        num_bins = np.asarray(self.totals).shape[-1]
+        return (pair_distribution_bins(size, num_bins),
+                pair_distribution_norm(self.mean, n, size),
+                pair_distribution_norm(self.mean_error, n, size))
+
+
+@attr.s(auto_attribs=True, frozen=True)
 class SSFPartBlocks(SetPropBlocks):
     totals: np.ndarray
     weight_totals: np.ndarray
@@ -238,6 +267,7 @@ class PropsDataBlocks:
     num_walkers: NumWalkersBlocks
     density: t.Optional[t.Any] = None
     ss_factor: t.Optional[t.Any] = None
+    pair_dist: t.Optional[t.Any] = None
 
 
 @attr.s(auto_attribs=True, frozen=True)
@@ -246,6 +276,8 @@ class PropsDataSeries:
     (qmc_exec/data/dmc.py:624-660)."""
     iter_props_blocks: t.Any
     ssf_blocks: t.Optional[np.ndarray] = None
+    #: pair histograms per block and time step [num_blocks, nts, num_bins]
+    pair_dist_blocks: t.Optional[np.ndarray] = None
 
     @property
     def props(self):
@@ -261,7 +293,8 @@ class SamplingData:
 
 # ---- HDF5 layout (qmc_exec/data/dmc.py:99-120, 192-211, 581-613, 683-735,
 # 770-793): <group>/totals [, weight_totals]; ss_factor/{fdk_sqr_abs,fdk_real,
-# fdk_imag}/...; blocks/{energy,weight,num_walkers[,density][,ss_factor]} ----
+# fdk_imag}/...; blocks/{energy,weight,num_walkers[,density][,ss_factor]
+# [,pair_dist]} ----
 def _export_weighted(self, group):
     group.create_dataset('totals', data=self.totals)
     group.create_dataset('weight_totals', data=self.weight_totals)
@@ -310,15 +343,19 @@ def _blocks_export(self, group):
         self.density.hdf5_export(group.require_group('density'))
     if self.ss_factor is not None:
         self.ss_factor.hdf5_export(group.require_group('ss_factor'))
+    if self.pair_dist is not None:
+        self.pair_dist.hdf5_export(group.require_group('pair_dist'))
 
 
 def _blocks_import(cls, group):
     dens, ssf = group.get('density'), group.get('ss_factor')
+    pdist = group.get('pair_dist')
     return cls(EnergyBlocks.from_hdf5_data(group.get('energy')),
                WeightBlocks.from_hdf5_data(group.get('weight')),
                NumWalkersBlocks.from_hdf5_data(group.get('num_walkers')),
                None if dens is None else DensityBlocks.from_hdf5_data(dens),
-               None if ssf is None else SSFBlocks.from_hdf5_data(ssf))
+               None if ssf is None else SSFBlocks.from_hdf5_data(ssf),
+               None if pdist is None else PairDistBlocks.from_hdf5_data(pdist))
 
 
 PropsDataBlocks.hdf5_export = _blocks_export

@@ -72,7 +72,7 @@ def exec_vmc(proc, proc_input):
 
 def exec_dmc(proc, proc_input):
     """qmc_exec/dmc/proc.py:136-415: energy / weight / walkers series and the
-    density / S(k) estimators of the kept blocks."""
+    density / S(k) / g2(r) estimators of the kept blocks."""
     from ..mrbp_qmc.dmc_exec import ProcInput
     num_blocks, nts = proc.num_blocks, proc.num_time_steps_block
     keep = proc.keep_iter_data
@@ -84,6 +84,7 @@ def exec_dmc(proc, proc_input):
         raise ProcInputError('the input data for the DMC procedure is '
                              'not valid')
     dens_spec, ssf_spec = proc.density_spec, proc.ssf_spec
+    pd_spec = getattr(proc, 'pair_dist_spec', None)
     blocks_iter = proc.sampling.blocks(proc_input.state, nts, burn)
     block = None
     try:
@@ -102,6 +103,11 @@ def exec_dmc(proc, proc_input):
             nm = ssf_spec.num_modes
             ssf = np.zeros((num_blocks, nts, nm, 3) if keep
                            else (num_blocks, nm, 3))
+        pdist = None
+        if pd_spec is not None:
+            npb = pd_spec.num_bins
+            pdist = np.zeros((num_blocks, nts, npb) if keep
+                             else (num_blocks, npb))
         pure_fac = np.ones(num_blocks)
         for b, block in enumerate(islice(blocks_iter, num_blocks)):
             p = block.iter_props
@@ -112,6 +118,8 @@ def exec_dmc(proc, proc_input):
                     dens[b] = block.iter_density
                 if ssf is not None:
                     ssf[b] = block.iter_ssf
+                if pdist is not None:
+                    pdist[b] = block.iter_pair_dist
             else:
                 wsum = p.weight.sum()
                 e[b], w[b] = p.energy.sum(), wsum
@@ -125,13 +133,20 @@ def exec_dmc(proc, proc_input):
                 if ssf is not None:
                     ssf[b] = (block.iter_ssf[nts - 1] if ssf_spec.as_pure_est
                               else block.iter_ssf.sum(axis=0))
+                if pdist is not None:
+                    pdist[b] = (block.iter_pair_dist[nts - 1]
+                                if pd_spec.as_pure_est
+                                else block.iter_pair_dist.sum(axis=0))
     finally:
         blocks_iter.close()
     exec_logger.info('DMC sampling completed.')
     last_state = None if block is None else block.last_state
     props = dmc_base.PropsData(e, w, nw, re, ae)
     reduce_data = bool(keep)
-    dens_blocks = ssf_blocks = None
+    dens_blocks = ssf_blocks = pd_blocks = None
+    if pdist is not None:
+        pd_blocks = dmc_data.PairDistBlocks.from_data(
+            nts, pdist, props, reduce_data, pd_spec.as_pure_est, pure_fac)
     if dens is not None:
         dens_blocks = dmc_data.DensityBlocks.from_data(
             nts, dens[..., 0], props, reduce_data, dens_spec.as_pure_est,
@@ -143,7 +158,8 @@ def exec_dmc(proc, proc_input):
         dmc_data.EnergyBlocks.from_data(props, reduce_data),
         dmc_data.WeightBlocks.from_data(props, reduce_data),
         dmc_data.NumWalkersBlocks.from_data(props, reduce_data),
-        dens_blocks, ssf_blocks)
+        dens_blocks, ssf_blocks, pd_blocks)
     data = dmc_data.SamplingData(
-        blocks, dmc_data.PropsDataSeries(props, ssf) if keep else None)
+        blocks,
+        dmc_data.PropsDataSeries(props, ssf, pdist) if keep else None)
     return proc.build_result(last_state, data)

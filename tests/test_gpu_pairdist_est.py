@@ -1,0 +1,303 @@
+"""The DMC pair distribution estimator on the GPU, mixed and pure, against the
+NumPy forward walking (tests/_pairdist_fw_restatement.py) on the states of a
+twin ensemble.
+
+Ensemble A and ensemble B start from the same positions with the same seed, so
+they follow the same trajectory (test_gpu_sampling.py::
+test_dmc_split_step_equals_block).  A runs one time step at a time and hands
+out its State after each; B runs one estimator block.  Every device quantity is
+an integer held in a double and the one division is of an integer by an
+integer: the rows must be EQUAL to the restatement's, whatever the order of the
+sums.  The only freedom is the rounding of r / delta at a bin edge; the seeds
+below were picked so that no pair of any case sits within 1e-9 of one.
+"""
+import functools
+from itertools import islice
+from math import pi
+
+import numpy as np
+import pytest
+
+from . import _pairdist_fw_restatement as fw
+
+pytestmark = pytest.mark.gpu
+
+TIME_STEP = 1e-3
+
+
+def box(n, cut=0.25):
+    from phd_qmclib_amd.mrbp_qmc import Spec
+    return Spec(lattice_depth=5 * pi ** 2, lattice_ratio=1,
+                interaction_strength=2, boson_number=n, supercell_size=n,
+                tbf_contact_cutoff=cut * n)
+
+
+# tag: (N, contact cutoff / L, bins, start walkers, max walkers, steps, pfw,
+#       seed).  The smallest shapes that still reach every path of the kernel:
+# an odd N with fewer bins than lanes; a single bin; more than 64 bins (the
+# lane = bin chunks); N = 64, one particle per lane, with pfw inside the block
+# (both divisors); N = 100, two passes over the own particles, at the largest
+# bin count; a population that starts at the cap.
+CASES = {
+    'odd':      (5, 0.25, 7, 40, 64, 8, 3, 1100),
+    'one_bin':  (16, 0.25, 1, 48, 64, 6, 3, 12),
+    'many':     (16, 0.25, 200, 48, 64, 6, 3, 13),
+    'wave':     (64, 0.25, 64, 300, 512, 10, 4, 14),
+    'two_pass': (100, 0.1, 256, 64, 96, 6, 3, 15),
+    'cap':      (16, 0.25, 16, 64, 64, 8, 3, 1600),
+}
+
+
+def start_positions(tag):
+    n, _, _, nw0, _, _, _, seed = CASES[tag]
+    return n * np.random.RandomState(seed).random_sample((nw0, n))
+
+
+def _ensemble(eng, tag):
+    from phd_qmclib_amd.engine import DmcEnsemble
+    _, _, _, nw0, maxw, _, _, seed = CASES[tag]
+    d = DmcEnsemble(eng, TIME_STEP, maxw, nw0, 0.5, rng_seed=seed)
+    d.set_state(start_positions(tag))
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def reference(tag):
+    """Ensemble A: the per-step states of the block and the restatement's rows
+    on them, computed once per case -> dict."""
+    from phd_qmclib_amd.engine import ModelEngine
+    n, cut, B, _, _, T, pfw, _ = CASES[tag]
+    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
+    a = _ensemble(eng, tag)
+    steps, energy = [], []
+    for _ in range(T):
+        ser = a.run_block(1)
+        s = a.get_state()
+        steps.append((s.confs[:, 0, :].copy(), s.cloning_ref.copy(),
+                      int(s.num_walkers)))
+        energy.append(ser.energy[0])
+    a.close()
+    eng.close()
+    mixed, pure, amb = fw.forward_walk(steps, float(n), B, pfw)
+    for arr in (mixed, pure):
+        arr.setflags(write=False)
+    return dict(steps=steps, mixed=mixed, pure=pure, ambiguous=amb,
+                energy=np.array(energy),
+                num_walkers=np.array([s[2] for s in steps]))
+
+
+def run_block_b(tag, pure, eval_estimators=True, others=False, order=0,
+                with_g2=True):
+    """Ensemble B: one estimator block -> (series, ssf, dens, g2 rows);
+    `others` sets S(k) and the density as well, before (order 0) or after
+    (order 1) the pair distribution."""
+    from phd_qmclib_amd.engine import ModelEngine
+    n, cut, B, _, _, T, pfw, _ = CASES[tag]
+    B = B if with_g2 else 0
+    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
+    b = _ensemble(eng, tag)
+    est = dict(num_modes=8, ssf_pure=True, ssf_pfw=pfw, num_bins=12,
+               dens_pure=False)
+    if others and order == 0:
+        b.set_estimators(**est)
+    if B:
+        b.set_pair_dist_estimator(B, pure=pure, pfw=pfw)
+    if others and order == 1:
+        b.set_estimators(**est)
+    ser, ssf, dens = b.run_block_est(T, eval_estimators)
+    rows = b.read_pair_dist(T) if B else None
+    b.close()
+    eng.close()
+    return ser, ssf, dens, rows
+
+
+@pytest.mark.parametrize('pure', [False, True], ids=['mixed', 'pure'])
+@pytest.mark.parametrize('tag', list(CASES))
+def test_rows_equal_the_forward_walking(tag, pure):
+    n, _, B, nw0, maxw, T, pfw, _ = CASES[tag]
+    ref = reference(tag)
+    assert ref['ambiguous'] == [], \
+        'a pair sits on a bin edge: choose another seed ' + \
+        repr(ref['ambiguous'][:4])
+    # the transport is exercised: a step whose cloning table is not the
+    # identity, and a population that changes
+    assert any(not np.array_equal(r[:nw], np.arange(nw))
+               for _, r, nw in ref['steps'])
+    assert len(set(ref['num_walkers']) | {nw0}) > 1
+    if tag == 'cap':
+        assert nw0 == maxw
+    if pure:
+        assert 1 < pfw < T          # both divisors, min(t + 1, pfw)
+    ser, _, _, rows = run_block_b(tag, pure)
+    print(tag, 'pure' if pure else 'mixed', 'walkers', ref['num_walkers'])
+    assert np.array_equal(ser.num_walkers, ref['num_walkers'])
+    assert np.array_equal(ser.energy, ref['energy'])
+    want = ref['pure'] if pure else ref['mixed']
+    assert rows.shape == (T, B)
+    assert np.array_equal(rows, want), np.argwhere(rows != want)[:8]
+    # every walker holds N (N - 1) / 2 pairs, at every step, mixed and pure.
+    # A pure entry is the rounded quotient of an integer by min(t + 1, pfw)
+    # (thirds, say), and a float sum of such quotients is not exact: the
+    # invariant is checked on the integer numerators, which each entry must
+    # give back bit for bit.
+    div = np.minimum(np.arange(T) + 1, pfw if pure else 1)[:, None]
+    counts = np.rint(rows * div)
+    assert np.array_equal(counts / div, rows)
+    assert np.array_equal(counts.sum(axis=1),
+                          ref['num_walkers'] * div[:, 0] * (n * (n - 1) // 2))
+
+
+@pytest.mark.parametrize('pure', [False, True], ids=['mixed', 'pure'])
+def test_deterministic_and_burn_in(pure):
+    tag = 'wave'
+    _, _, B, _, _, T, _, _ = CASES[tag]
+    s1, _, _, r1 = run_block_b(tag, pure)
+    s2, _, _, r2 = run_block_b(tag, pure)
+    assert r1.tobytes() == r2.tobytes()
+    assert r1.any()
+    # a burn-in block propagates the same walkers and leaves the rows zero
+    s0, _, _, r0 = run_block_b(tag, pure, eval_estimators=False)
+    assert r0.shape == (T, B) and not r0.any()
+    assert np.array_equal(s0.energy, s1.energy)
+    assert np.array_equal(s0.num_walkers, s1.num_walkers)
+
+
+@pytest.mark.parametrize('pure', [False, True], ids=['mixed', 'pure'])
+def test_independent_of_the_other_estimators(pure):
+    tag = 'many'
+    n, cut, B, _, _, T, _, _ = CASES[tag]
+    alone = run_block_b(tag, pure)
+    first = run_block_b(tag, pure, others=True, order=0)
+    second = run_block_b(tag, pure, others=True, order=1)
+    without = run_block_b(tag, pure, others=True, with_g2=False)
+    for both in (first, second):
+        assert np.array_equal(both[3], alone[3])
+        assert both[1].any() and both[2].any()
+        assert both[1].tobytes() == without[1].tobytes()
+        assert both[2].tobytes() == without[2].tobytes()
+    # the walk itself does not know about the estimator
+    ref = reference(tag)
+    for run in (alone, first, second, without):
+        assert np.array_equal(run[0].energy, ref['energy'])
+        assert np.array_equal(run[0].num_walkers, ref['num_walkers'])
+
+
+def test_switching_off_and_errors():
+    from phd_qmclib_amd.engine import ModelEngine
+    from phd_qmclib_amd._lib import QmcError
+    tag = 'odd'
+    n, cut, B, _, _, T, pfw, _ = CASES[tag]
+    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
+    d = _ensemble(eng, tag)
+    with pytest.raises(QmcError):
+        d.set_pair_dist_estimator(257)
+    with pytest.raises(QmcError):
+        d.set_pair_dist_estimator(-1)
+    with pytest.raises(QmcError):
+        d.set_pair_dist_estimator(8, pure=True, pfw=0)
+    d.set_pair_dist_estimator(B, pure=True, pfw=pfw)
+    with pytest.raises(QmcError):
+        d.read_pair_dist(1)                  # no estimator block yet
+    d.run_block_est(T)
+    assert d.read_pair_dist(T).any()
+    with pytest.raises(QmcError):
+        d.read_pair_dist(T + 1)
+    d.set_pair_dist_estimator(0)
+    ser, ssf, dens = d.run_block_est(2)      # falls through to run_block
+    assert ssf is None and dens is None and len(ser.energy) == 2
+    with pytest.raises(QmcError):
+        d.read_pair_dist(1)
+    d.close()
+    eng.close()
+
+
+def test_distributed_dmc_refuses_the_estimator():
+    from phd_qmclib_amd.dist import DistributedDmc
+    import torch
+    from phd_qmclib_amd.engine import DmcEnsemble, ModelEngine
+    eng = ModelEngine(box(16).cfc_spec,
+                      stream=torch.cuda.current_stream().cuda_stream)
+    d = DmcEnsemble(eng, TIME_STEP, 64, 48, 0.5, rng_seed=2,
+                    external_reduce=True)
+    d.set_state(start_positions('many'))
+    d.set_pair_dist_estimator(16)
+    with pytest.raises(NotImplementedError, match='pair distribution'):
+        DistributedDmc(d, 16, 'cuda', solo=True)
+    d.set_pair_dist_estimator(0)
+    DistributedDmc(d, 16, 'cuda', solo=True)
+    d.close()
+    eng.close()
+
+
+# ---- top level ------------------------------------------------------------
+def test_sampling_blocks_fill_iter_pair_dist():
+    from phd_qmclib_amd import mrbp_qmc
+    spec = box(16)
+    confs = np.zeros((48, 2, 16))
+    confs[:, 0, :] = start_positions('many')
+    kw = dict(max_num_walkers=64, target_num_walkers=48, rng_seed=13)
+    plain = mrbp_qmc.dmc.Sampling(spec, TIME_STEP, **kw)
+    with_pd = mrbp_qmc.dmc.Sampling(
+        spec, TIME_STEP, pair_dist_est_spec=mrbp_qmc.dmc.PairDistEstSpec(
+            20, as_pure_est=True, pfw_num_time_steps=3), **kw)
+    assert with_pd.pair_dist_bins.shape == (20,)
+    ini = plain.build_state(confs)
+    b0 = list(islice(plain.blocks(ini, 6, 0), 2))
+    b1 = list(islice(with_pd.blocks(ini, 6, 1), 2))
+    for p, q in zip(b0, b1):
+        assert p.iter_pair_dist is None and p.iter_density is None
+        assert q.iter_density is None and q.iter_ssf is None
+        assert q.iter_pair_dist.shape == (6, 20)
+        assert np.array_equal(p.iter_props.energy, q.iter_props.energy)
+    assert not b1[0].iter_pair_dist.any()            # the burn-in block
+    nw = b1[1].iter_props.num_walkers.astype(np.int64)
+    # (the integer numerators: a float sum of thirds is not exact)
+    div = np.minimum(np.arange(6) + 1, 3)[:, None]
+    counts = np.rint(b1[1].iter_pair_dist * div)
+    assert np.array_equal(counts / div, b1[1].iter_pair_dist)
+    assert np.array_equal(counts.sum(axis=1), nw * div[:, 0] * 120)
+
+
+def test_proc_exec_pure_and_mixed_kept():
+    from phd_qmclib_amd import mrbp_qmc
+    from phd_qmclib_amd.qmc_exec.data import dmc as dd
+    spec = box(16)
+    B = 32
+    np.random.seed(5)
+    kw = dict(max_num_walkers=512, target_num_walkers=480, rng_seed=7,
+              num_blocks=4, num_time_steps_block=16, burn_in_blocks=1)
+    pure = mrbp_qmc.dmc_exec.Proc(
+        spec, TIME_STEP, pair_dist_spec=mrbp_qmc.dmc_exec.PairDistEstSpec(B),
+        **kw)
+    din = mrbp_qmc.dmc_exec.ProcInput.from_model_sys_conf_spec(
+        mrbp_qmc.dmc_exec.ModelSysConfSpec('RANDOM'), pure)
+    res = pure.exec(din)
+    pd = res.data.blocks.pair_dist
+    assert isinstance(pd, dd.PairDistBlocks)
+    assert pd.totals.shape == (4, B) and pd.weight_totals.shape == (4, 1)
+    assert res.data.blocks.density is None and res.data.series is None
+    # the last row of a block: every walker's pairs of the 16 steps, over 16
+    nw_last = np.rint(pd.weight_totals[:, 0])
+    assert np.allclose(pd.weight_totals[:, 0], nw_last, rtol=1e-14, atol=0)
+    assert np.array_equal(pd.totals.sum(axis=1), nw_last * 120)
+    r, g2, err = pd.pair_distribution(spec)
+    assert r.shape == g2.shape == err.shape == (B,)
+    assert np.isfinite(g2).all() and (g2 >= 0).all()
+    # the histogram of a whole population averages to one
+    assert abs(g2.mean() - 1.0) < 1e-12
+    mixed = mrbp_qmc.dmc_exec.Proc(
+        spec, TIME_STEP, keep_iter_data=True,
+        pair_dist_spec=mrbp_qmc.dmc_exec.PairDistEstSpec(B, False), **kw)
+    kres = mixed.exec(din)
+    kept = kres.data.series.pair_dist_blocks
+    assert kept.shape == (4, 16, B)
+    nw = kres.data.series.iter_props_blocks.num_walkers.astype(np.int64)
+    assert np.array_equal(kept.sum(axis=2), nw * 120)
+    kpd = kres.data.blocks.pair_dist
+    assert np.array_equal(kpd.totals, kept.sum(axis=1))
+    assert np.isfinite(kpd.pair_distribution(spec)[1]).all()
+    # the walk is the same with and without the estimator
+    off = mrbp_qmc.dmc_exec.Proc(spec, TIME_STEP, **kw).exec(din)
+    assert off.data.blocks.pair_dist is None
+    assert np.array_equal(off.data.blocks.energy.totals,
+                          res.data.blocks.energy.totals)

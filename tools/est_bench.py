@@ -1,5 +1,9 @@
 """Cost of the DMC estimators next to the plain time step (development tool).
-usage: est_bench.py [--bosons N] [--walkers W] [--steps K] [--modes M] [--bins B]"""
+usage: est_bench.py [--bosons N] [--walkers W] [--steps K] [--modes M] [--bins B]
+                    [--pair-bins P] [--repeats R] [--only plain,g2]
+(groups: plain, ssf, density, g2 = g2mixed + g2pure)
+Every line is the median over R timed blocks of K steps (after a warm-up
+block), with the shortest and the longest next to it."""
 import argparse
 import os
 import sys
@@ -18,6 +22,10 @@ ap.add_argument('--walkers', type=int, default=1 << 17)
 ap.add_argument('--steps', type=int, default=16)
 ap.add_argument('--modes', type=int, default=64)
 ap.add_argument('--bins', type=int, default=128)
+ap.add_argument('--pair-bins', type=int, default=64)
+ap.add_argument('--repeats', type=int, default=5)
+ap.add_argument('--only', default='plain,ssf,density,g2',
+                help='comma-separated groups to time')
 a = ap.parse_args()
 n = a.bosons
 spec = Spec(lattice_depth=5 * pi ** 2, lattice_ratio=1, interaction_strength=2,
@@ -27,27 +35,46 @@ pos = n * np.random.RandomState(1).random_sample((a.walkers, n))
 maxw = ((a.walkers * 512 // 480) + 255) // 256 * 256
 
 
-def timed(tag, **est):
+def timed(tag, pair=None, **est):
     d = DmcEnsemble(eng, 6.25e-4, maxw, a.walkers, 0.5, rng_seed=1)
     d.set_state(pos)
     if est:
         d.set_estimators(**est)
+    if pair:
+        d.set_pair_dist_estimator(**pair)
+    if est or pair:
         run = lambda k: d.run_block_est(k, True)
     else:
         run = lambda k: d.run_block(k)
-    run(4)
-    eng.sync()
-    t0 = time.perf_counter()
     run(a.steps)
     eng.sync()
-    dt = time.perf_counter() - t0
-    print(f'{tag:28s} {dt / a.steps * 1e3:8.3f} ms/step', flush=True)
+    ts = []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        run(a.steps)
+        eng.sync()
+        ts.append((time.perf_counter() - t0) / a.steps * 1e3)
+    print(f'{tag:28s} {np.median(ts):8.3f} ms/step  (min {min(ts):.3f}, '
+          f'max {max(ts):.3f}, {a.repeats} x {a.steps} steps)', flush=True)
     d.close()
-    return dt
+    return float(np.median(ts))
 
 
-base = timed('plain')
-timed(f'ssf mixed M={a.modes}', num_modes=a.modes)
-timed(f'ssf pure  M={a.modes}', num_modes=a.modes, ssf_pure=True, ssf_pfw=8)
-timed(f'density mixed B={a.bins}', num_bins=a.bins)
-timed(f'density pure  B={a.bins}', num_bins=a.bins, dens_pure=True, dens_pfw=8)
+only = a.only.split(',')
+if 'plain' in only:
+    timed('plain')
+if 'ssf' in only:
+    timed(f'ssf mixed M={a.modes}', num_modes=a.modes)
+    timed(f'ssf pure  M={a.modes}', num_modes=a.modes, ssf_pure=True,
+          ssf_pfw=8)
+if 'density' in only:
+    timed(f'density mixed B={a.bins}', num_bins=a.bins)
+    timed(f'density pure  B={a.bins}', num_bins=a.bins, dens_pure=True,
+          dens_pfw=8)
+if 'g2' in only or 'g2mixed' in only:
+    timed(f'g2 mixed B={a.pair_bins}', pair=dict(num_bins=a.pair_bins))
+if 'g2' in only or 'g2pure' in only:
+    timed(f'g2 pure  B={a.pair_bins}',
+          pair=dict(num_bins=a.pair_bins, pure=True, pfw=a.steps))
+if 'plain' in only:
+    timed('plain (again)')
