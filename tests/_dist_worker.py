@@ -16,13 +16,21 @@ class OracleShard:
     """engine.DmcEnsemble look-alike over oracle/qmc_oracle.c."""
 
     def __init__(self, orc, model, pos, dt, local_max, global_target, kappa,
-                 seed, slot0):
+                 seed, slot0, ref_energy=None, fix_stale_energy=False,
+                 nthreads=1, import_sets_slot_energy=False):
         self.orc = orc
         self.n = model.boson_number
         self.maxw = local_max
         self.ens = orc.DmcEnsemble(model, pos, dt, local_max, global_target,
-                                   kappa, seed=seed, slot0=slot0)
-        # build_state used the local mean as E_ref; keep it
+                                   kappa, seed=seed, ref_energy=ref_energy,
+                                   slot0=slot0,
+                                   fix_stale_energy=fix_stale_energy,
+                                   nthreads=nthreads)
+        # the device's rule for the slot ("stale") energy of an imported
+        # walker (csrc/qmc_kernels_misc.h, unpack_walkers_kernel): off by
+        # default, the gloo workers run as they always did
+        self.import_sets_slot_energy = import_sets_slot_energy
+        # ref_energy=None: build_state used the local mean as E_ref; keep it
         self.dt, self.kappa, self.target = dt, kappa, float(global_target)
         self.series = []
         self._saved = None
@@ -88,6 +96,11 @@ class OracleShard:
         confs[first:first + count, 1] = src[:, self.n:2 * self.n]
         en[first:first + count] = src[:, 3 * self.n]
         wt[first:first + count] = src[:, 3 * self.n + 1]
+        if self.import_sets_slot_energy:
+            # the slot's previous occupant is gone: the energy quirk D1 reads
+            # for this slot becomes the newcomer's own
+            self.ens.bufs['actual_energy'][first:first + count] = \
+                src[:, 3 * self.n]
         self.ens.st.prev_num_walkers = first + count
 
     def import_walkers(self, count, buf_ptr):
