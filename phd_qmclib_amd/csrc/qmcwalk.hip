@@ -1274,6 +1274,35 @@ extern "C" int qmc_vmc_state_dev(qmc_vmc *v, double **pos, double **wf)
     return 0;
 }
 
+// `count` doubles of a device result to the host, complete on return
+static int read_doubles(const qmc_engine *e, double *out, const double *dev,
+                        size_t count)
+{
+    HIP_TRY(hipMemcpyAsync(out, dev, count * sizeof(double),
+                           hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+template <int KD>
+static void launch_ssf_kd(const qmc_engine *e, const EstArgs &a)
+{
+    const size_t lds = (size_t)(BLOCK / 64) * SsfShape<KD>::WAVE_DOUBLES *
+                       sizeof(double);
+    allow_lds(dmc_ssf_mfma_kernel<KD>, lds);
+    hipLaunchKernelGGL(dmc_ssf_mfma_kernel<KD>, dim3(EST_BLOCKS), dim3(BLOCK),
+                       lds, e->stream, a);
+}
+
+// The one place that launches the matrix-core S(k) kernel: 8 rows of modes
+// per pass up to 64 modes, 16 beyond (the caller checks the launch with the
+// reduction that follows).
+static void launch_ssf(const qmc_engine *e, const EstArgs &a)
+{
+    if (a.K <= 64) launch_ssf_kd<8>(e, a);
+    else launch_ssf_kd<16>(e, a);
+}
+
 // Static structure factor parts of the current configurations, summed over
 // the chains: out[m] = sum_w (|rho_m|^2, Re rho_m, Im rho_m), m < num_modes
 // (qmc_base/jastrow/vmc.py:304-351 evaluates them per step of one chain; an
@@ -1294,26 +1323,92 @@ extern "C" int qmc_vmc_ssf(qmc_vmc *v, int32_t num_modes, double *out)
     a.aux_prev = nullptr; a.aux_act = nullptr; a.partial = v->ssf_partial;
     a.maxw = v->W; a.step_idx = 0; a.pfw = 0; a.n = e->dm.n; a.K = M;
     a.pure = 0; a.scale = 4.0 / e->dm.L; a.scale2 = 0.0;
-    if (M <= 64) {
-        const size_t lds = (size_t)(BLOCK / 64) * SsfShape<8>::WAVE_DOUBLES *
-                           sizeof(double);
-        allow_lds(dmc_ssf_mfma_kernel<8>, lds);
-        hipLaunchKernelGGL(dmc_ssf_mfma_kernel<8>, dim3(EST_BLOCKS),
-                           dim3(BLOCK), lds, e->stream, a);
-    } else {
-        const size_t lds = (size_t)(BLOCK / 64) * SsfShape<16>::WAVE_DOUBLES *
-                           sizeof(double);
-        allow_lds(dmc_ssf_mfma_kernel<16>, lds);
-        hipLaunchKernelGGL(dmc_ssf_mfma_kernel<16>, dim3(EST_BLOCKS),
-                           dim3(BLOCK), lds, e->stream, a);
-    }
+    launch_ssf(e, a);
     hipLaunchKernelGGL(est_reduce_kernel, dim3((M * 3 + 31) / 32), dim3(256), 0,
                        e->stream, v->ssf_partial, EST_BLOCKS, M * 3, 1.0,
                        v->ssf_out);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, v->ssf_out, (size_t)M * 3 * sizeof(double),
-                           hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    return read_doubles(e, out, v->ssf_out, (size_t)M * 3);
+}
+
+// ---- batch estimators: what g1(s) and g2(r) share ------------------------
+// lane-group width of the kernels for n particles
+static int est_width(int n)
+{
+    return n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64;
+}
+
+// launch(std::integral_constant<int, G>, c0, nc) for the run-time width G over
+// nconf configurations, at most `xmax` to a launch (a grid's first dimension
+// holds 2^31 - 1 blocks)
+template <typename F>
+static int launch_width_chunks(int G, long long nconf, long long xmax, F launch)
+{
+    for (long long c0 = 0; c0 < nconf; c0 += xmax) {
+        const long long nc = std::min(xmax, nconf - c0);
+        switch (G) {
+        case 8: launch(std::integral_constant<int, 8>{}, c0, nc); break;
+        case 16: launch(std::integral_constant<int, 16>{}, c0, nc); break;
+        case 32: launch(std::integral_constant<int, 32>{}, c0, nc); break;
+        default: launch(std::integral_constant<int, 64>{}, c0, nc); break;
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+// sums[K][2] and wsum over nconf configurations, `tile` at a time:
+// fill(c0, nc) leaves rows[nc][K] of the tile from c0 on the stream and
+// obdm_reduce_kernel adds them up in tile order, into sums and wsum from the
+// second tile on.  (No configurations: one reduction of an empty tile, which
+// zeroes sums.)
+template <typename F>
+static int reduce_tiles(const qmc_engine *e, long long nconf, long long tile,
+                        const double *rows, const double *w, int K,
+                        double *sums, double *wsum, F fill)
+{
+    long long c0 = 0;
+    do {
+        const long long nc = std::min(tile, nconf - c0);
+        if (fill(c0, nc)) return 1;
+        hipLaunchKernelGGL(obdm_reduce_kernel, dim3(K + 1), dim3(256), 0,
+                           e->stream, rows, w ? w + c0 : nullptr, nc, K,
+                           c0 > 0 ? 1 : 0, sums, wsum);
+        HIP_TRY(hipGetLastError());
+        c0 += tile;
+    } while (c0 < nconf);
+    return 0;
+}
+
+// A per-configuration output of a host entry point: `bytes` per configuration
+// from the device tile `dev` to `host` (null: not asked for).
+struct HostOut {
+    void *host;
+    const void *dev;
+    size_t bytes;
+};
+
+// Host positions pos[nconf][n] through the device, `tile` configurations at a
+// time: upload to dpos, launch(nc), download the outputs, wait.
+template <typename F>
+static int run_host_tiles(const qmc_engine *e, long long nconf, long long tile,
+                          const double *pos, double *dpos,
+                          std::initializer_list<HostOut> outs, F launch)
+{
+    const size_t n = (size_t)e->dm.n;
+    for (long long c0 = 0; c0 < nconf; c0 += tile) {
+        const size_t nc = (size_t)std::min(tile, nconf - c0);
+        HIP_TRY(hipMemcpyAsync(dpos, pos + (size_t)c0 * n,
+                               nc * n * sizeof(double),
+                               hipMemcpyHostToDevice, e->stream));
+        if (launch((long long)nc)) return 1;
+        for (const HostOut &o : outs)
+            if (o.host)
+                HIP_TRY(hipMemcpyAsync((char *)o.host + (size_t)c0 * o.bytes,
+                                       o.dev, nc * o.bytes,
+                                       hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
     return 0;
 }
 
@@ -1344,9 +1439,7 @@ static int obdm_launch(qmc_engine *e, long long nconf, const double *pos_dev,
                        int32_t nshift, double *g1_dev, double *ith_dev)
 {
     if (nconf <= 0) return 0;
-    const int n = e->dm.n;
-    int G = 64;
-    if (n <= 8) G = 8; else if (n <= 16) G = 16; else if (n <= 32) G = 32;
+    const int n = e->dm.n, G = est_width(n);
     const int unit = (64 / G) * OBDM_U;       // shifts of one wavefront pass
     // shifts per wavefront: all of them once the batch alone fills the chip
     // (the unshifted rows are computed once per wavefront), fewer for a small
@@ -1358,24 +1451,16 @@ static int obdm_launch(qmc_engine *e, long long nconf, const double *pos_dev,
     chunk = std::max(chunk, (nshift + 65534) / 65535);
     const unsigned ny = (unsigned)((nshift + chunk - 1) / chunk);
     const size_t lds = (size_t)n * OBDM_LDS_PER_PARTICLE * sizeof(double);
-    // a grid's first dimension holds 2^31 - 1 blocks
-    const long long XMAX = 1ll << 30;
-    for (long long c0 = 0; c0 < nconf; c0 += XMAX) {
-        const long long nc = std::min(XMAX, nconf - c0);
+    return launch_width_chunks(G, nconf, 1ll << 30, [&](auto g, long long c0,
+                                                         long long nc) {
         ObdmArgs a{ pos_dev + (size_t)c0 * n, e->obdm_stab,
                     g1_dev + (size_t)c0 * nshift,
                     ith_dev ? ith_dev + (size_t)c0 * nshift * n : nullptr, nc,
                     (int)nshift, chunk };
-        const dim3 grid((unsigned)nc, ny);
-        switch (G) {
-        case 8: hipLaunchKernelGGL(obdm_kernel<8>, grid, dim3(64), lds, e->stream, e->dm_dev, a); break;
-        case 16: hipLaunchKernelGGL(obdm_kernel<16>, grid, dim3(64), lds, e->stream, e->dm_dev, a); break;
-        case 32: hipLaunchKernelGGL(obdm_kernel<32>, grid, dim3(64), lds, e->stream, e->dm_dev, a); break;
-        default: hipLaunchKernelGGL(obdm_kernel<64>, grid, dim3(64), lds, e->stream, e->dm_dev, a); break;
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+        hipLaunchKernelGGL(obdm_kernel<decltype(g)::value>,
+                           dim3((unsigned)nc, ny), dim3(64), lds, e->stream,
+                           e->dm_dev, a);
+    });
 }
 
 extern "C" int qmc_obdm_dev(qmc_engine *e, int64_t nconf, const double *pos,
@@ -1407,19 +1492,11 @@ extern "C" int qmc_obdm_reduce_dev(qmc_engine *e, int64_t nconf,
     if (obdm_make_shift_table(e, nshift, shifts) ||
         e->obdm_g1.reserve((size_t)tile * nshift))
         return 1;
-    long long c0 = 0;
-    do {
-        const long long nc = std::min(tile, (long long)nconf - c0);
-        if (obdm_launch(e, nc, pos + (size_t)c0 * n, nshift, e->obdm_g1,
-                        nullptr))
-            return 1;
-        hipLaunchKernelGGL(obdm_reduce_kernel, dim3(nshift + 1), dim3(256), 0,
-                           e->stream, e->obdm_g1, w ? w + c0 : nullptr, nc,
-                           (int)nshift, c0 > 0 ? 1 : 0, sums, wsum);
-        HIP_TRY(hipGetLastError());
-        c0 += tile;
-    } while (c0 < nconf);
-    return 0;
+    return reduce_tiles(e, nconf, tile, e->obdm_g1, w, nshift, sums, wsum,
+                        [&](long long c0, long long nc) {
+        return obdm_launch(e, nc, pos + (size_t)c0 * n, nshift, e->obdm_g1,
+                           nullptr);
+    });
 }
 
 static int obdm_check_host_shifts(const char *who, int32_t nshift,
@@ -1454,22 +1531,12 @@ extern "C" int qmc_obdm(qmc_engine *e, int64_t nconf, const double *pos,
     HIP_TRY(hipMemcpyAsync(dsh, shifts, M * sizeof(double),
                            hipMemcpyHostToDevice, e->stream));
     if (obdm_make_shift_table(e, nshift, dsh)) return 1;
-    for (long long c0 = 0; c0 < nconf; c0 += tile) {
-        const size_t nc = (size_t)std::min(tile, (long long)nconf - c0);
-        HIP_TRY(hipMemcpyAsync(dpos, pos + (size_t)c0 * n,
-                               nc * n * sizeof(double),
-                               hipMemcpyHostToDevice, e->stream));
-        if (obdm_launch(e, (long long)nc, dpos, nshift, dg1, dith)) return 1;
-        HIP_TRY(hipMemcpyAsync(g1 + (size_t)c0 * M, dg1,
-                               nc * M * sizeof(double),
-                               hipMemcpyDeviceToHost, e->stream));
-        if (ith)
-            HIP_TRY(hipMemcpyAsync(ith + (size_t)c0 * M * n, dith,
-                                   nc * M * n * sizeof(double),
-                                   hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    return 0;
+    return run_host_tiles(e, nconf, tile, pos, dpos,
+                          { { g1, dg1.get(), M * sizeof(double) },
+                            { ith, dith.get(), M * n * sizeof(double) } },
+                          [&](long long nc) {
+        return obdm_launch(e, nc, dpos, nshift, dg1, dith);
+    });
 }
 
 // g1 parts of the CURRENT configurations of the chains, summed over the
@@ -1489,11 +1556,7 @@ extern "C" int qmc_vmc_obdm(qmc_vmc *v, int32_t nshift, const double *shifts,
                            hipMemcpyHostToDevice, e->stream));
     int rc = qmc_obdm_reduce_dev(e, v->W, v->pos, nullptr, nshift, dsh,
                                  e->obdm_sums, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, e->obdm_sums, 2 * M * sizeof(double),
-                           hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return 0;
+    return rc ? rc : read_doubles(e, out, e->obdm_sums, 2 * M);
 }
 
 // ---- pair distribution g2(r) (csrc/qmc_pairdist.h) ----------------------
@@ -1520,29 +1583,20 @@ static int pair_dist_launch(qmc_engine *e, long long nconf,
 {
     if (nconf <= 0) return 0;
     const int n = e->dm.n;
-    int G = 64;
-    if (n <= 8) G = 8; else if (n <= 16) G = 16; else if (n <= 32) G = 32;
+    int G = est_width(n);
     const size_t per_conf = (size_t)n * sizeof(double) + (size_t)B * sizeof(unsigned);
     while (G < 64 && (64 / G) * per_conf > PD_LDS_BUDGET) G *= 2;
     const int gpw = 64 / G;
     const size_t lds = gpw * per_conf;
     const double L = e->dm.L, half = 0.5 * L;
-    // a grid's first dimension holds 2^31 - 1 blocks
-    const long long XMAX = (1ll << 30) * gpw;
-    for (long long c0 = 0; c0 < nconf; c0 += XMAX) {
-        const long long nc = std::min(XMAX, nconf - c0);
+    return launch_width_chunks(G, nconf, (1ll << 30) * gpw,
+                               [&](auto g, long long c0, long long nc) {
         PairDistArgs a{ pos_dev + (size_t)c0 * n, out + (size_t)c0 * B, nc, n,
                         (int)B, L, half, (double)B / half };
-        const dim3 grid((unsigned)((nc + gpw - 1) / gpw));
-        switch (G) {
-        case 8: hipLaunchKernelGGL((pair_dist_kernel<8, OutT>), grid, dim3(64), lds, e->stream, a); break;
-        case 16: hipLaunchKernelGGL((pair_dist_kernel<16, OutT>), grid, dim3(64), lds, e->stream, a); break;
-        case 32: hipLaunchKernelGGL((pair_dist_kernel<32, OutT>), grid, dim3(64), lds, e->stream, a); break;
-        default: hipLaunchKernelGGL((pair_dist_kernel<64, OutT>), grid, dim3(64), lds, e->stream, a); break;
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+        hipLaunchKernelGGL((pair_dist_kernel<decltype(g)::value, OutT>),
+                           dim3((unsigned)((nc + gpw - 1) / gpw)), dim3(64),
+                           lds, e->stream, a);
+    });
 }
 
 extern "C" int qmc_pair_dist_dev(qmc_engine *e, int64_t nconf,
@@ -1570,19 +1624,11 @@ extern "C" int qmc_pair_dist_reduce_dev(qmc_engine *e, int64_t nconf,
         std::max<long long>(nconf, 1),
         std::min(PD_TILE, PD_SCRATCH_ELEMS / num_bins));
     if (e->pd_hist.reserve((size_t)tile * num_bins)) return 1;
-    long long c0 = 0;
-    do {
-        const long long nc = std::min(tile, (long long)nconf - c0);
-        if (pair_dist_launch(e, nc, pos + (size_t)c0 * n, num_bins,
-                             e->pd_hist.get()))
-            return 1;
-        hipLaunchKernelGGL(obdm_reduce_kernel, dim3(num_bins + 1), dim3(256), 0,
-                           e->stream, e->pd_hist, w ? w + c0 : nullptr, nc,
-                           (int)num_bins, c0 > 0 ? 1 : 0, sums, wsum);
-        HIP_TRY(hipGetLastError());
-        c0 += tile;
-    } while (c0 < nconf);
-    return 0;
+    return reduce_tiles(e, nconf, tile, e->pd_hist, w, num_bins, sums, wsum,
+                        [&](long long c0, long long nc) {
+        return pair_dist_launch(e, nc, pos + (size_t)c0 * n, num_bins,
+                                e->pd_hist.get());
+    });
 }
 
 extern "C" int qmc_pair_dist(qmc_engine *e, int64_t nconf, const double *pos,
@@ -1598,19 +1644,11 @@ extern "C" int qmc_pair_dist(qmc_engine *e, int64_t nconf, const double *pos,
     DevBuf<double> dpos;
     DevBuf<uint32_t> dcnt;
     if (dpos.alloc((size_t)tile * n) || dcnt.alloc((size_t)tile * B)) return 1;
-    for (long long c0 = 0; c0 < nconf; c0 += tile) {
-        const size_t nc = (size_t)std::min(tile, (long long)nconf - c0);
-        HIP_TRY(hipMemcpyAsync(dpos, pos + (size_t)c0 * n,
-                               nc * n * sizeof(double),
-                               hipMemcpyHostToDevice, e->stream));
-        if (pair_dist_launch(e, (long long)nc, dpos, num_bins, dcnt.get()))
-            return 1;
-        HIP_TRY(hipMemcpyAsync(counts + (size_t)c0 * B, dcnt,
-                               nc * B * sizeof(uint32_t),
-                               hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    return 0;
+    return run_host_tiles(e, nconf, tile, pos, dpos,
+                          { { counts, dcnt.get(), B * sizeof(uint32_t) } },
+                          [&](long long nc) {
+        return pair_dist_launch(e, nc, dpos, num_bins, dcnt.get());
+    });
 }
 
 // Histogram sums of the CURRENT configurations of the chains: the resident
@@ -1626,11 +1664,7 @@ extern "C" int qmc_vmc_pair_dist(qmc_vmc *v, int32_t num_bins, double *out)
     if (e->pd_sums.reserve(2 * B)) return 1;
     int rc = qmc_pair_dist_reduce_dev(e, v->W, v->pos, nullptr, num_bins,
                                       e->pd_sums, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, e->pd_sums, 2 * B * sizeof(double),
-                           hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return 0;
+    return rc ? rc : read_doubles(e, out, e->pd_sums, 2 * B);
 }
 
 
@@ -1714,6 +1748,47 @@ extern "C" int qmc_vmc_run_block(qmc_vmc *v, int64_t nyield, double *sum_e,
 }
 
 // ----------------------------------------------------------------- DMC ----
+// What a setter asks of a slot; `aux`: keep per-walker rows.
+struct DmcEstSpec {
+    int K, pure;
+    long long pfw;
+    bool aux;
+};
+
+// One per-step estimator of a population: K modes or bins of C doubles each.
+struct DmcEstSlot {
+    int K = 0;                   // modes or bins; 0: off
+    int C = 1;                   // doubles per mode or bin
+    int pure = 0;
+    long long pfw = 1;           // forward-walking length
+    DevBuf<double> aux[2];       // [maxw][K][C] per-walker rows (null: none kept)
+    DevBuf<double> iter;         // [steps][K][C] per-step outputs, grown on demand
+    size_t row() const { return (size_t)K * C; }
+    bool on() const { return K > 0; }
+    void drop()
+    {
+        aux[0].release();
+        aux[1].release();
+        iter.release();
+        K = 0; pure = 0; pfw = 1;
+    }
+    // on (K > 0), with the rows of `maxw` walkers if asked for; a failure
+    // leaves it off
+    int set(const DmcEstSpec &a, size_t maxw)
+    {
+        drop();
+        if (a.K <= 0) return 0;
+        K = a.K; pure = a.pure; pfw = a.pfw;
+        for (int b = 0; b < 2 && a.aux; ++b)
+            if (aux[b].alloc(maxw * row())) {
+                drop();
+                return 1;
+            }
+        return 0;
+    }
+};
+enum { EST_SSF, EST_DENS, EST_PD, EST_SLOTS };
+
 struct qmc_dmc {
     qmc_engine *eng = nullptr;
     qmc_dmc_params p;
@@ -1744,42 +1819,48 @@ struct qmc_dmc {
                                        // device keeps their logarithms)
     bool sums_pending = false;   // E_t partials still to be summed (by finish)
     double global_target = 0.0;
-    // estimators (f1)
-    qmc_dmc_est_params est;
-    bool have_est = false;
-    DevBuf<double> ssf_aux[2];                   // [maxw][M][3]
-    DevBuf<double> dens_aux[2];                  // [maxw][B]
-    DevBuf<double> est_partial;                  // [EST_BLOCKS][max(3M, B)]
-    DevBuf<double> iter_ssf, iter_dens;          // per-step outputs, grown on demand
+    // estimators, in launch order: S(k) (3 doubles per mode) and the density,
+    // set together, and the pair distribution (qmc_pairdist.h), set on its own
+    DmcEstSlot est[EST_SLOTS];
+    DevBuf<double> est_partial;     // [EST_BLOCKS][widest row]
     long long est_block_steps = 0;  // steps of the estimator block in progress
     int est_last_act = 1;           // aux buffer the last estimator step wrote
-    // pair distribution estimator (qmc_pairdist.h: dmc_pair_dist_kernel),
-    // set on its own by qmc_dmc_set_pair_dist_estimator; pd_bins == 0: off
-    int pd_bins = 0, pd_pure = 0;
-    long long pd_pfw = 1;
-    DevBuf<double> pd_aux[2];                    // [maxw][pd_bins] (pure only)
-    DevBuf<double> iter_pd;                      // [steps][pd_bins]
-    bool any_est() const { return have_est || pd_bins > 0; }
+    qmc_dmc() { est[EST_SSF].C = 3; }
+    bool any_est() const
+    {
+        return std::any_of(est, est + EST_SLOTS,
+                           [](const DmcEstSlot &s) { return s.on(); });
+    }
 };
 
 // est_partial holds the block partial sums of one estimator at a time:
-// [EST_BLOCKS][max(3 M, B, B_g2)] over the estimators that are set.
+// [EST_BLOCKS][widest row of the estimators that are on].
 static int dmc_size_est_partial(qmc_dmc *d)
 {
     size_t kc = 0;
-    if (d->have_est)
-        kc = (size_t)std::max(d->est.num_modes * 3, d->est.num_bins);
-    kc = std::max(kc, (size_t)d->pd_bins);
+    for (const DmcEstSlot &s : d->est) kc = std::max(kc, s.row());
     d->est_partial.release();
     return kc ? d->est_partial.alloc(EST_BLOCKS * kc) : 0;
 }
 
-static void dmc_drop_pair_dist(qmc_dmc *d)
+// Replace the settings of `count` slots from `first` on; the other slots stay
+// as they are.  A failed allocation leaves these slots off and the others
+// with partial sums of their own size; if even those cannot be had, every
+// slot is off.  Nothing is ever on over a missing buffer.
+static int dmc_set_est_slots(qmc_dmc *d, int first, int count,
+                             const DmcEstSpec *spec)
 {
-    d->pd_aux[0].release();
-    d->pd_aux[1].release();
-    d->iter_pd.release();
-    d->pd_bins = 0; d->pd_pure = 0; d->pd_pfw = 1;
+    d->est_block_steps = 0;
+    d->est_partial.release();
+    for (int i = 0; i < count; ++i) d->est[first + i].drop();
+    bool ok = true;
+    for (int i = 0; i < count && ok; ++i)
+        ok = d->est[first + i].set(spec[i], (size_t)d->maxw) == 0;
+    if (ok && dmc_size_est_partial(d) == 0) return 0;
+    for (int i = 0; i < count; ++i) d->est[first + i].drop();
+    if (dmc_size_est_partial(d))
+        for (DmcEstSlot &s : d->est) s.drop();
+    return 1;            // (alloc has set the message)
 }
 
 static int dmc_reserve_series(qmc_dmc *d, long long nsteps)
@@ -2228,53 +2309,16 @@ extern "C" int qmc_dmc_set_estimators(qmc_dmc *d, const qmc_dmc_est_params *p)
         p->num_bins > EST_MAXK)
         return fail("qmc_dmc_set_estimators: num_modes / num_bins must be in "
                     "[0, 256]");
-    qmc_engine *e = d->eng;
-    HIP_TRY(hipSetDevice(e->device));
-    const auto drop = [d]() {
-        for (int k = 0; k < 2; ++k) {
-            d->ssf_aux[k].release();
-            d->dens_aux[k].release();
-        }
-        d->est_partial.release();
-    };
-    drop();
-    // the per-step output buffers are sized for the old mode / bin counts
-    d->iter_ssf.release();
-    d->iter_dens.release();
-    d->est_block_steps = 0;
+    HIP_TRY(hipSetDevice(d->eng->device));
     d->est_last_act = 1;
-    d->have_est = false;
-    d->est = *p;
-    const bool want = p->num_modes > 0 || p->num_bins > 0;
-    const size_t W = (size_t)d->maxw;
-    // estimators are on only once every buffer exists: a failed allocation
-    // leaves the population without estimators (and without half of their
-    // buffers), not with `have_est` set over null pointers
-    bool failed = false;
-    if (p->num_modes > 0)
-        for (int k = 0; k < 2 && !failed; ++k)
-            failed = d->ssf_aux[k].alloc(W * (size_t)p->num_modes * 3) != 0;
-    if (p->num_bins > 0)
-        for (int k = 0; k < 2 && !failed; ++k)
-            failed = d->dens_aux[k].alloc(W * (size_t)p->num_bins) != 0;
-    if (failed) {
-        drop();
-        d->est.num_modes = d->est.num_bins = 0;
-        // (the pair distribution estimator keeps its settings and gets the
-        // partial sums it needs back)
-        if (dmc_size_est_partial(d)) dmc_drop_pair_dist(d);
-        return 1;            // (alloc has set the message)
-    }
-    d->have_est = want;
-    if (dmc_size_est_partial(d)) {
-        // nothing can run without the partial sums: everything off
-        drop();
-        d->est.num_modes = d->est.num_bins = 0;
-        d->have_est = false;
-        dmc_drop_pair_dist(d);
-        return 1;
-    }
-    return 0;
+    // Per-walker rows, pure or mixed.  The density kernel accumulates in them
+    // in mixed mode as well.  The S(k) kernel does not touch them when mixed:
+    // they are allocated all the same, so that the memory footprint and the
+    // walker records of such a population stay what they were.
+    const DmcEstSpec spec[2] = {
+        { p->num_modes, p->ssf_pure, p->ssf_pfw, true },
+        { p->num_bins, p->dens_pure, p->dens_pfw, true } };
+    return dmc_set_est_slots(d, EST_SSF, 2, spec);
 }
 
 // The pair distribution estimator is set on its own: the S(k) / density
@@ -2289,53 +2333,26 @@ extern "C" int qmc_dmc_set_pair_dist_estimator(qmc_dmc *d, int32_t num_bins,
     if (num_bins > 0 && pure && pfw < 1)
         return fail("qmc_dmc_set_pair_dist_estimator: pfw must be >= 1");
     static_assert(PD_EST_MAXN >= 512, "every engine's boson_number fits");
-    qmc_engine *e = d->eng;
-    HIP_TRY(hipSetDevice(e->device));
-    dmc_drop_pair_dist(d);
-    d->est_block_steps = 0;
-    bool failed = false;
-    if (num_bins > 0 && pure)
-        for (int k = 0; k < 2 && !failed; ++k)
-            failed = d->pd_aux[k].alloc((size_t)d->maxw * (size_t)num_bins) != 0;
-    if (!failed) {
-        d->pd_bins = num_bins; d->pd_pure = pure ? 1 : 0;
-        d->pd_pfw = pure ? pfw : 1;
-        failed = dmc_size_est_partial(d) != 0;
-    }
-    if (failed) {
-        dmc_drop_pair_dist(d);
-        // (the other two get their partial sums back; if even that fails
-        // they are off as well)
-        if (dmc_size_est_partial(d)) {
-            for (int k = 0; k < 2; ++k) {
-                d->ssf_aux[k].release();
-                d->dens_aux[k].release();
-            }
-            d->est.num_modes = d->est.num_bins = 0;
-            d->have_est = false;
-        }
-        return 1;            // (alloc has set the message)
-    }
-    return 0;
+    HIP_TRY(hipSetDevice(d->eng->device));
+    // per-walker rows only when pure: the mixed kernel keeps none
+    const DmcEstSpec spec = { num_bins, pure ? 1 : 0, pure ? pfw : 1,
+                              pure != 0 };
+    return dmc_set_est_slots(d, EST_PD, 1, &spec);
 }
 
 extern "C" int qmc_dmc_read_pair_dist(qmc_dmc *d, int64_t nsteps,
                                       double *iter_out)
 {
     if (!d || !iter_out) return fail("qmc_dmc_read_pair_dist: null argument");
-    if (d->pd_bins <= 0)
+    const DmcEstSlot &s = d->est[EST_PD];
+    if (!s.on())
         return fail("qmc_dmc_read_pair_dist: the pair distribution estimator "
                     "is not set");
     if (nsteps <= 0 || nsteps > d->est_block_steps)
         return fail("qmc_dmc_read_pair_dist: nsteps outside the last "
                     "estimator block");
-    qmc_engine *e = d->eng;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpyAsync(iter_out, d->iter_pd,
-                           (size_t)nsteps * (size_t)d->pd_bins * 8,
-                           hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return 0;
+    HIP_TRY(hipSetDevice(d->eng->device));
+    return read_doubles(d->eng, iter_out, s.iter, (size_t)nsteps * s.row());
 }
 
 // Evaluate the estimators on the population yielded by the step that has just
@@ -2350,62 +2367,37 @@ static int dmc_enqueue_estimators(qmc_dmc *d, long long step_idx)
     a.ppos = d->pos[par]; a.ref = d->ref; a.ctl = d->ctl;
     a.maxw = d->maxw; a.step_idx = step_idx; a.n = e->dm.n;
     a.partial = d->est_partial;
-    a.scale2 = 0.0;
-    if (d->est.num_modes > 0) {
-        const int M = d->est.num_modes;
-        a.aux_prev = d->ssf_aux[prev]; a.aux_act = d->ssf_aux[act];
-        a.K = M; a.pure = d->est.ssf_pure; a.pfw = d->est.ssf_pfw;
-        a.scale = 4.0 / e->dm.L;
-        if (M <= 64) {
-            const size_t lds = (size_t)(BLOCK / 64) *
-                               SsfShape<8>::WAVE_DOUBLES * sizeof(double);
-            allow_lds(dmc_ssf_mfma_kernel<8>, lds);
-            hipLaunchKernelGGL(dmc_ssf_mfma_kernel<8>, dim3(EST_BLOCKS),
-                               dim3(BLOCK), lds, e->stream, a);
-        } else {
-            const size_t lds = (size_t)(BLOCK / 64) *
-                               SsfShape<16>::WAVE_DOUBLES * sizeof(double);
-            allow_lds(dmc_ssf_mfma_kernel<16>, lds);
-            hipLaunchKernelGGL(dmc_ssf_mfma_kernel<16>, dim3(EST_BLOCKS),
-                               dim3(BLOCK), lds, e->stream, a);
+    // (in slot order: they take turns at est_partial)
+    for (int k = 0; k < EST_SLOTS; ++k) {
+        const DmcEstSlot &s = d->est[k];
+        if (!s.on()) continue;
+        // (null where no per-walker rows are kept: the mixed g2)
+        a.aux_prev = s.aux[prev]; a.aux_act = s.aux[act];
+        a.K = s.K; a.pure = s.pure; a.pfw = s.pfw;
+        a.scale2 = 0.0;
+        switch (k) {
+        case EST_SSF:
+            a.scale = 4.0 / e->dm.L;
+            launch_ssf(e, a);
+            break;
+        case EST_DENS:
+            a.scale = e->dm.L / (double)s.K;      // bin size
+            hipLaunchKernelGGL(dmc_density_kernel, dim3(EST_BLOCKS),
+                               dim3(BLOCK), 0, e->stream, a);
+            break;
+        default:
+            a.scale = e->dm.L;
+            a.scale2 = (double)s.K / (0.5 * e->dm.L);   // as pair_dist_launch
+            hipLaunchKernelGGL(dmc_pair_dist_kernel, dim3(EST_BLOCKS),
+                               dim3(BLOCK), 0, e->stream, a);
         }
+        const int row = (int)s.row();
         double div = 1.0;
         if (a.pure) div = step_idx < a.pfw ? (double)(step_idx + 1)
                                            : (double)a.pfw;
-        hipLaunchKernelGGL(est_reduce_kernel, dim3((M * 3 + 31) / 32),
-                           dim3(256), 0, e->stream, d->est_partial, EST_BLOCKS,
-                           M * 3, div, d->iter_ssf + (size_t)step_idx * M * 3);
-    }
-    if (d->est.num_bins > 0) {
-        const int B = d->est.num_bins;
-        a.aux_prev = d->dens_aux[prev]; a.aux_act = d->dens_aux[act];
-        a.K = B; a.pure = d->est.dens_pure; a.pfw = d->est.dens_pfw;
-        a.scale = e->dm.L / (double)B;      // bin size
-        hipLaunchKernelGGL(dmc_density_kernel, dim3(EST_BLOCKS), dim3(BLOCK), 0,
-                           e->stream, a);
-        double div = 1.0;
-        if (a.pure) div = step_idx < a.pfw ? (double)(step_idx + 1)
-                                           : (double)a.pfw;
-        hipLaunchKernelGGL(est_reduce_kernel, dim3((B + 31) / 32), dim3(256),
-                           0, e->stream, d->est_partial, EST_BLOCKS, B, div,
-                           d->iter_dens + (size_t)step_idx * B);
-    }
-    if (d->pd_bins > 0) {
-        const int B = d->pd_bins;
-        // (mixed: no per-walker rows are kept)
-        a.aux_prev = d->pd_pure ? d->pd_aux[prev].get() : nullptr;
-        a.aux_act = d->pd_pure ? d->pd_aux[act].get() : nullptr;
-        a.K = B; a.pure = d->pd_pure; a.pfw = d->pd_pfw;
-        a.scale = e->dm.L;
-        a.scale2 = (double)B / (0.5 * e->dm.L);     // as pair_dist_launch
-        hipLaunchKernelGGL(dmc_pair_dist_kernel, dim3(EST_BLOCKS), dim3(BLOCK),
-                           0, e->stream, a);
-        double div = 1.0;
-        if (a.pure) div = step_idx < a.pfw ? (double)(step_idx + 1)
-                                           : (double)a.pfw;
-        hipLaunchKernelGGL(est_reduce_kernel, dim3((B + 31) / 32), dim3(256),
-                           0, e->stream, d->est_partial, EST_BLOCKS, B, div,
-                           d->iter_pd + (size_t)step_idx * B);
+        hipLaunchKernelGGL(est_reduce_kernel, dim3((row + 31) / 32), dim3(256),
+                           0, e->stream, d->est_partial, EST_BLOCKS, row, div,
+                           s.iter + (size_t)step_idx * row);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -2416,24 +2408,15 @@ static int dmc_enqueue_estimators(qmc_dmc *d, long long step_idx)
 static int dmc_est_begin_block(qmc_dmc *d, long long nsteps)
 {
     qmc_engine *e = d->eng;
-    const size_t M3 = (size_t)d->est.num_modes * 3, B = (size_t)d->est.num_bins;
-    const size_t W = (size_t)d->maxw;
-    const size_t need_s = (size_t)nsteps * (M3 ? M3 : 1);
-    const size_t need_d = (size_t)nsteps * (B ? B : 1);
-    if (d->iter_ssf.reserve(need_s) || d->iter_dens.reserve(need_d)) return 1;
-    HIP_TRY(hipMemsetAsync(d->iter_ssf, 0, need_s * 8, e->stream));
-    HIP_TRY(hipMemsetAsync(d->iter_dens, 0, need_d * 8, e->stream));
-    for (int k = 0; k < 2; ++k) {
-        if (M3) HIP_TRY(hipMemsetAsync(d->ssf_aux[k], 0, W * M3 * 8, e->stream));
-        if (B) HIP_TRY(hipMemsetAsync(d->dens_aux[k], 0, W * B * 8, e->stream));
-    }
-    if (d->pd_bins > 0) {
-        const size_t PB = (size_t)d->pd_bins, need_p = (size_t)nsteps * PB;
-        if (d->iter_pd.reserve(need_p)) return 1;
-        HIP_TRY(hipMemsetAsync(d->iter_pd, 0, need_p * 8, e->stream));
-        if (d->pd_pure)
-            for (int k = 0; k < 2; ++k)
-                HIP_TRY(hipMemsetAsync(d->pd_aux[k], 0, W * PB * 8, e->stream));
+    for (DmcEstSlot &s : d->est) {
+        if (!s.on()) continue;
+        const size_t need = (size_t)nsteps * s.row();
+        if (s.iter.reserve(need)) return 1;
+        HIP_TRY(hipMemsetAsync(s.iter, 0, need * 8, e->stream));
+        for (int k = 0; k < 2; ++k)
+            if (s.aux[k])
+                HIP_TRY(hipMemsetAsync(s.aux[k], 0,
+                                       (size_t)d->maxw * s.row() * 8, e->stream));
     }
     d->est_block_steps = nsteps;
     d->est_last_act = 1;
@@ -2459,7 +2442,6 @@ extern "C" int qmc_dmc_run_block_est(qmc_dmc *d, int64_t nsteps,
     HIP_TRY(hipSetDevice(e->device));
     if (dmc_reserve_series(d, nsteps)) return 1;
     if (dmc_est_begin_block(d, nsteps)) return 1;
-    const size_t M3 = (size_t)d->est.num_modes * 3, B = (size_t)d->est.num_bins;
     d->ser_len = 0;
     for (long long t = 0; t < nsteps; ++t) {
         int rc = dmc_enqueue_local(d, nullptr);
@@ -2472,12 +2454,12 @@ extern "C" int qmc_dmc_run_block_est(qmc_dmc *d, int64_t nsteps,
             if (rc) return rc;
         }
     }
-    if (iter_ssf && M3)
-        HIP_TRY(hipMemcpyAsync(iter_ssf, d->iter_ssf, (size_t)nsteps * M3 * 8,
-                               hipMemcpyDeviceToHost, e->stream));
-    if (iter_density && B)
-        HIP_TRY(hipMemcpyAsync(iter_density, d->iter_dens, (size_t)nsteps * B * 8,
-                               hipMemcpyDeviceToHost, e->stream));
+    double *const host[2] = { iter_ssf, iter_density };
+    for (int k = 0; k < 2; ++k)
+        if (host[k] && d->est[k].on())
+            HIP_TRY(hipMemcpyAsync(host[k], d->est[k].iter,
+                                   (size_t)nsteps * d->est[k].row() * 8,
+                                   hipMemcpyDeviceToHost, e->stream));
     return qmc_dmc_read_series(d, nsteps, energy, weight, num_walkers,
                                ref_energy, accum_energy);
 }
@@ -2513,9 +2495,9 @@ extern "C" int qmc_dmc_est_iter_dev(qmc_dmc *d, double **iter_ssf,
                                     double **iter_density)
 {
     if (!d) return fail("qmc_dmc_est_iter_dev: null argument");
-    if (iter_ssf) *iter_ssf = d->est.num_modes > 0 ? d->iter_ssf.get() : nullptr;
-    if (iter_density)
-        *iter_density = d->est.num_bins > 0 ? d->iter_dens.get() : nullptr;
+    // (a slot that is off holds no buffer)
+    if (iter_ssf) *iter_ssf = d->est[EST_SSF].iter.get();
+    if (iter_density) *iter_density = d->est[EST_DENS].iter.get();
     return 0;
 }
 
@@ -2657,15 +2639,14 @@ static WalkerRecArgs walker_rec_args(qmc_dmc *d, long long first,
     a.label = d->label[d->cur];
     a.energy = d->energy[d->cur]; a.weight = d->weight[d->cur];
     a.eslot = d->eslot;
-    // the rows the next estimator step reads as "previous"
-    a.ssf_aux = d->est.num_modes > 0 && d->have_est
-                    ? d->ssf_aux[d->est_last_act].get() : nullptr;
-    a.dens_aux = d->est.num_bins > 0 && d->have_est
-                     ? d->dens_aux[d->est_last_act].get() : nullptr;
+    // the rows the next estimator step reads as "previous" (null and no
+    // doubles for a slot that is off; the pair distribution's do not travel)
+    a.ssf_aux = d->est[EST_SSF].aux[d->est_last_act];
+    a.dens_aux = d->est[EST_DENS].aux[d->est_last_act];
     a.first = first; a.count = count;
     a.n = d->eng->dm.n;
-    a.m3 = a.ssf_aux ? d->est.num_modes * 3 : 0;
-    a.nb = a.dens_aux ? d->est.num_bins : 0;
+    a.m3 = (int)d->est[EST_SSF].row();
+    a.nb = (int)d->est[EST_DENS].row();
     return a;
 }
 

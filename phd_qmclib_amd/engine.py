@@ -77,6 +77,15 @@ def pair_distribution_norm(counts, boson_number, supercell_size):
     return counts * (L / (n * (n - 1) * delta))
 
 
+def _pos2d(pos, num_particles,
+           expected='pos must have shape (W, boson_number)'):
+    """pos as a contiguous fp64 [rows, num_particles] array."""
+    pos = np.ascontiguousarray(pos, dtype=np.float64)
+    if pos.ndim != 2 or pos.shape[1] != num_particles:
+        raise ValueError(expected)
+    return pos
+
+
 class DeviceBuffer:
     """A plain fp64 array in HBM (qmc_buffer_*): inputs / outputs of
     `ModelEngine.evaluate_dev` that stay resident across calls."""
@@ -278,9 +287,7 @@ class ModelEngine:
     def evaluate(self, pos) -> EvalResult:
         """log|psi|, local energy, per-particle energy and drift of every
         configuration in pos[W, N]."""
-        pos = np.ascontiguousarray(pos, dtype=np.float64)
-        if pos.ndim != 2 or pos.shape[1] != self.num_particles:
-            raise ValueError('pos must have shape (W, boson_number)')
+        pos = _pos2d(pos, self.num_particles)
         W, n = pos.shape
         wf, en = np.zeros(W), np.zeros(W)
         ith, dr = np.zeros((W, n)), np.zeros((W, n))
@@ -305,9 +312,7 @@ class ModelEngine:
         """One-body density matrix g1(s) of every configuration in pos[W, N]
         for every shift -> g1[W, nshift]; with ith=True also the per-particle
         terms -> (g1, ith[W, nshift, N])."""
-        pos = np.ascontiguousarray(pos, dtype=np.float64)
-        if pos.ndim != 2 or pos.shape[1] != self.num_particles:
-            raise ValueError('pos must have shape (W, boson_number)')
+        pos = _pos2d(pos, self.num_particles)
         sh = self._shifts(shifts)
         W, n = pos.shape
         g1 = np.zeros((W, sh.size))
@@ -333,31 +338,39 @@ class ModelEngine:
                                             w_ptr, int(nshift), shifts_ptr,
                                             sums_ptr, wsum_ptr))
 
-    def one_body_density_weighted(self, pos, weights, shifts):
-        """sum_c w_c g1_c(s) / sum_c w_c over the configurations pos[W, N]
-        (one upload of the positions, the weighted reduction on the device)
-        -> g1[nshift]."""
-        pos = np.ascontiguousarray(pos, dtype=np.float64)
+    def _weighted_mean(self, pos, weights, num_out, extra, reduce):
+        """sum_c w_c x_c / sum_c w_c of the `num_out` per-configuration values
+        x_c that `reduce(nconf, pos_ptr, w_ptr, *extra_ptrs, sums_ptr,
+        wsum_ptr)` sums on the device (one upload of the positions and of the
+        host arrays `extra`)."""
+        expected = 'pos[W, boson_number] and weights[W] expected'
+        pos = _pos2d(pos, self.num_particles, expected)
         w = np.ascontiguousarray(weights, dtype=np.float64)
-        sh = self._shifts(shifts)
-        if pos.ndim != 2 or pos.shape[1] != self.num_particles \
-                or w.shape != (pos.shape[0],):
-            raise ValueError('pos[W, boson_number] and weights[W] expected')
-        bufs = [DeviceBuffer(pos.shape, self.device).upload(pos),
-                DeviceBuffer(w.shape, self.device).upload(w),
-                DeviceBuffer(sh.shape, self.device).upload(sh),
-                DeviceBuffer((sh.size, 2), self.device),
-                DeviceBuffer((1,), self.device)]
+        if w.shape != (pos.shape[0],):
+            raise ValueError(expected)
+        bufs = [DeviceBuffer(x.shape, self.device).upload(x)
+                for x in (pos, w, *extra)]
+        bufs += [DeviceBuffer((num_out, 2), self.device),
+                 DeviceBuffer((1,), self.device)]
         try:
-            self.one_body_density_reduce_dev(pos.shape[0], bufs[0].ptr,
-                                             bufs[1].ptr, sh.size, bufs[2].ptr,
-                                             bufs[3].ptr, bufs[4].ptr)
+            reduce(pos.shape[0], *(b.ptr for b in bufs))
             self.sync()
-            sums, wsum = bufs[3].download(), bufs[4].download()
+            sums, wsum = bufs[-2].download(), bufs[-1].download()
         finally:
             for b in bufs:
                 b.close()
         return sums[:, 0] / wsum[0]
+
+    def one_body_density_weighted(self, pos, weights, shifts):
+        """sum_c w_c g1_c(s) / sum_c w_c over the configurations pos[W, N]
+        (one upload of the positions, the weighted reduction on the device)
+        -> g1[nshift]."""
+        sh = self._shifts(shifts)
+        return self._weighted_mean(
+            pos, weights, sh.size, [sh],
+            lambda nconf, pos_ptr, w_ptr, sh_ptr, sums_ptr, wsum_ptr:
+            self.one_body_density_reduce_dev(nconf, pos_ptr, w_ptr, sh.size,
+                                             sh_ptr, sums_ptr, wsum_ptr))
 
     @staticmethod
     def _num_bins(num_bins):
@@ -373,9 +386,7 @@ class ModelEngine:
         uniform bins of the minimum-image distance in [0, L/2]; every row adds
         up to N (N - 1) / 2.  `pair_distribution_norm` turns counts into
         g2."""
-        pos = np.ascontiguousarray(pos, dtype=np.float64)
-        if pos.ndim != 2 or pos.shape[1] != self.num_particles:
-            raise ValueError('pos must have shape (W, boson_number)')
+        pos = _pos2d(pos, self.num_particles)
         nb = self._num_bins(num_bins)
         counts = np.zeros((pos.shape[0], nb), dtype=np.uint32)
         check(self._lib.qmc_pair_dist(self._h, pos.shape[0], ptr(pos), nb,
@@ -401,26 +412,12 @@ class ModelEngine:
         """sum_c w_c H_c / sum_c w_c over the configurations pos[W, N] (one
         upload of the positions, the weighted reduction on the device)
         -> mean histogram[num_bins]."""
-        pos = np.ascontiguousarray(pos, dtype=np.float64)
-        w = np.ascontiguousarray(weights, dtype=np.float64)
         nb = self._num_bins(num_bins)
-        if pos.ndim != 2 or pos.shape[1] != self.num_particles \
-                or w.shape != (pos.shape[0],):
-            raise ValueError('pos[W, boson_number] and weights[W] expected')
-        bufs = [DeviceBuffer(pos.shape, self.device).upload(pos),
-                DeviceBuffer(w.shape, self.device).upload(w),
-                DeviceBuffer((nb, 2), self.device),
-                DeviceBuffer((1,), self.device)]
-        try:
-            self.pair_distribution_reduce_dev(pos.shape[0], bufs[0].ptr,
-                                              bufs[1].ptr, nb, bufs[2].ptr,
-                                              bufs[3].ptr)
-            self.sync()
-            sums, wsum = bufs[2].download(), bufs[3].download()
-        finally:
-            for b in bufs:
-                b.close()
-        return sums[:, 0] / wsum[0]
+        return self._weighted_mean(
+            pos, weights, nb, [],
+            lambda nconf, pos_ptr, w_ptr, sums_ptr, wsum_ptr:
+            self.pair_distribution_reduce_dev(nconf, pos_ptr, w_ptr, nb,
+                                              sums_ptr, wsum_ptr))
 
 
 class VmcEnsemble:
@@ -588,6 +585,7 @@ class DmcEnsemble:
         h = C.c_void_p()
         check(self._lib.qmc_dmc_create(engine._h, C.byref(p), C.byref(h)))
         self._h = h
+        self.pair_dist_bins = 0
 
     def close(self):
         if getattr(self, '_h', None):
@@ -602,9 +600,8 @@ class DmcEnsemble:
 
     def set_state(self, pos, ref_energy: t.Optional[float] = None):
         """build_state semantics: energies and drifts are computed here."""
-        pos = np.ascontiguousarray(pos, dtype=np.float64)
-        if pos.ndim != 2 or pos.shape[1] != self.num_particles:
-            raise ValueError('pos must have shape (nw, boson_number)')
+        pos = _pos2d(pos, self.num_particles,
+                     'pos must have shape (nw, boson_number)')
         check(self._lib.qmc_dmc_set_state(
             self._h, pos.shape[0], ptr(pos), int(ref_energy is not None),
             float(ref_energy if ref_energy is not None else 0.0)))
@@ -700,7 +697,7 @@ class DmcEnsemble:
         """Rows of the last estimator block -> iter_pair_dist[nsteps, B]:
         per time step the pair histograms summed over the walkers (pure: the
         forward-walking rows over min(step + 1, pfw))."""
-        out = np.zeros((int(nsteps), getattr(self, 'pair_dist_bins', 0)))
+        out = np.zeros((int(nsteps), self.pair_dist_bins))
         check(self._lib.qmc_dmc_read_pair_dist(self._h, int(nsteps), ptr(out)))
         return out
 

@@ -182,6 +182,61 @@ def test_independent_of_the_other_estimators(pure):
         assert np.array_equal(run[0].num_walkers, ref['num_walkers'])
 
 
+@pytest.mark.parametrize('second_pure', [False, True],
+                         ids=['wide_then_narrow', 'narrow_then_wide'])
+def test_resetting_a_live_ensemble_equals_a_fresh_one(second_pure):
+    """Estimators set again, to other sizes, on an ensemble that already has
+    some: ensemble R is set twice, ensemble F only to the second configuration;
+    same seed, same state, one estimator block each.  Every buffer of R was
+    dropped and sized anew, so its rows are F's byte for byte.  The density is
+    off in the narrow configuration (`dens is None` in R and in F); where the
+    second configuration is the wide one it has 12 bins, and the density rows
+    are compared like the others: equal byte for byte, none of them zero."""
+    from phd_qmclib_amd.engine import DmcEnsemble, ModelEngine
+    tag = 'many'
+    n, cut, B, nw0, maxw, T, pfw, seed = CASES[tag]
+    B2 = B // 4          # its bin edges are edges of the B bins as well
+    assert (n, nw0, maxw) == (16, 48, 64) and 0 < B2 < B
+    wide = (dict(num_modes=8, ssf_pure=True, ssf_pfw=pfw, num_bins=12),
+            dict(num_bins=B, pure=True, pfw=pfw))
+    narrow = (dict(num_modes=5, num_bins=0), dict(num_bins=B2, pure=False))
+    configs = [narrow, wide] if second_pure else [wide, narrow]
+    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
+    runs = []
+    for todo in (configs, configs[1:]):              # R, then F
+        d = DmcEnsemble(eng, TIME_STEP, maxw, nw0, 0.5, rng_seed=seed)
+        for est, g2 in todo:
+            d.set_estimators(**est)
+            d.set_pair_dist_estimator(**g2)
+        d.set_state(start_positions(tag))
+        ser, ssf, dens = d.run_block_est(T)
+        runs.append((ser, ssf, dens, d.read_pair_dist(T)))
+        d.close()
+    eng.close()
+    (ser_r, ssf_r, dens_r, g2_r), (ser_f, ssf_f, dens_f, g2_f) = runs
+    for x, y in zip(ser_r, ser_f):
+        assert x.tobytes() == y.tobytes()
+    assert ssf_r.tobytes() == ssf_f.tobytes()
+    assert g2_r.tobytes() == g2_f.tobytes()
+    assert ssf_r.shape == (T, 8 if second_pure else 5, 3)
+    assert g2_r.shape == (T, B if second_pure else B2)
+    assert ssf_r.reshape(T, -1).any(axis=1).all() and g2_r.any(axis=1).all()
+    if second_pure:
+        assert dens_r.tobytes() == dens_f.tobytes()
+        assert dens_r.shape == (T, 12, 1) and dens_r.any(axis=(1, 2)).all()
+    else:
+        assert dens_r is None and dens_f is None
+    # F is not the only witness: the restatement on the twin's states
+    ref = reference(tag)
+    assert np.array_equal(ser_r.energy, ref['energy'])
+    if second_pure:
+        want = ref['pure']
+    else:
+        want, _, amb = fw.forward_walk(ref['steps'], float(n), B2, pfw)
+        assert amb == []
+    assert np.array_equal(g2_r, want), np.argwhere(g2_r != want)[:8]
+
+
 def test_switching_off_and_errors():
     from phd_qmclib_amd.engine import ModelEngine
     from phd_qmclib_amd._lib import QmcError
