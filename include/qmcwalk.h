@@ -428,6 +428,21 @@ int qmc_dmc_est_iter_dev(qmc_dmc *d, double **iter_ssf, double **iter_density);
 int qmc_dmc_set_pair_dist_estimator(qmc_dmc *d, int32_t num_bins, int32_t pure,
                                     int64_t pfw);
 int qmc_dmc_read_pair_dist(qmc_dmc *d, int64_t nsteps, double *iter_out);
+/* Centre-of-mass diffusion as a fourth block estimator (an extension: the
+ * reference has none): the winding-number estimator of the superfluid
+ * fraction.  Per time step t of an estimator block two doubles,
+ * (sum_s Y_t(s), sum_s Y_t(s)^2) over the yielded walkers, where Y_t(s) is N
+ * times the unwrapped centre-of-mass displacement of walker s since the first
+ * yielded state of the block, carried through the cloning table (pure, unit
+ * weights); row 0 is zero.  rho_s / rho is the large-t limit of
+ * iter[t][1] / num_walkers[t] / (2 N t dt).  Needs |sum_i displacement_i| <
+ * L / 2 per time step.  on != 0 switches it on, 0 off.  Set on its own, as the
+ * pair distribution.  read_cm_diffusion copies the first nsteps rows of the
+ * last estimator block to the host, iter_out[nsteps][2] (synchronises); rows
+ * of a block run with eval_estimators == 0 are zero.  The per-walker rows are
+ * not part of the walker record: single-GPU only. */
+int qmc_dmc_set_cm_diffusion_estimator(qmc_dmc *d, int32_t on);
+int qmc_dmc_read_cm_diffusion(qmc_dmc *d, int64_t nsteps, double *iter_out);
 /* The yielded ("actual") State after the last step (qmc_base/dmc.py:773-780):
  * confs[maxw][2][N], energy/weight[maxw], mask[maxw], cloning_ref[maxw];
  * scalars[5] = energy, weight, ref_energy, accum_energy, num_walkers. */

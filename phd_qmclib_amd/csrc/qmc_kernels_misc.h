@@ -282,6 +282,8 @@ __global__ void __launch_bounds__(BLOCK) dmc_finish_kernel(FinishArgs a)
 // configuration of its parent, parents[ref[s]] (qmc_base/dmc.py:773-780).
 struct EstArgs {
     const double *ppos;       // parent positions [maxw][N]
+    const double *cpos = nullptr;   // child positions [maxw][N] (centre-of-mass
+                              // diffusion only: qmc_cmdiff.h)
     const long long *ref;     // cloning table
     const DmcCtl *ctl;
     const double *aux_prev;   // [maxw][K][C] per-walker parts one step ago
@@ -295,7 +297,8 @@ struct EstArgs {
     int pure;
     double scale;             // S(k): 4 / L (angle k_m z = (pi/2) * m * scale * z)
                               // density: bin size L / num_bins
-                              // g2(r): supercell size L
+                              // g2(r), centre-of-mass diffusion: supercell
+                              // size L
     double scale2;            // g2(r): 1 / delta = num_bins / (L / 2)
 };
 

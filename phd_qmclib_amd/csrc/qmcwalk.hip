@@ -11,6 +11,7 @@
 #include "qmc_kernels_misc.h"
 #include "qmc_obdm.h"
 #include "qmc_pairdist.h"
+#include "qmc_cmdiff.h"
 #include "../../include/qmcwalk.h"
 #include "qmc_probe.h"
 
@@ -1759,11 +1760,14 @@ struct DmcEstSpec {
 struct DmcEstSlot {
     int K = 0;                   // modes or bins; 0: off
     int C = 1;                   // doubles per mode or bin
+    int A = 0;                   // doubles per walker in the rows; 0: as the
+                                 // output, K * C
     int pure = 0;
     long long pfw = 1;           // forward-walking length
-    DevBuf<double> aux[2];       // [maxw][K][C] per-walker rows (null: none kept)
+    DevBuf<double> aux[2];       // [maxw][aux_row()] per-walker rows (null: none kept)
     DevBuf<double> iter;         // [steps][K][C] per-step outputs, grown on demand
     size_t row() const { return (size_t)K * C; }
+    size_t aux_row() const { return A ? (size_t)A : row(); }
     bool on() const { return K > 0; }
     void drop()
     {
@@ -1780,14 +1784,14 @@ struct DmcEstSlot {
         if (a.K <= 0) return 0;
         K = a.K; pure = a.pure; pfw = a.pfw;
         for (int b = 0; b < 2 && a.aux; ++b)
-            if (aux[b].alloc(maxw * row())) {
+            if (aux[b].alloc(maxw * aux_row())) {
                 drop();
                 return 1;
             }
         return 0;
     }
 };
-enum { EST_SSF, EST_DENS, EST_PD, EST_SLOTS };
+enum { EST_SSF, EST_DENS, EST_PD, EST_CM, EST_SLOTS };
 
 struct qmc_dmc {
     qmc_engine *eng = nullptr;
@@ -1820,12 +1824,19 @@ struct qmc_dmc {
     bool sums_pending = false;   // E_t partials still to be summed (by finish)
     double global_target = 0.0;
     // estimators, in launch order: S(k) (3 doubles per mode) and the density,
-    // set together, and the pair distribution (qmc_pairdist.h), set on its own
+    // set together, the pair distribution (qmc_pairdist.h) and the
+    // centre-of-mass diffusion (qmc_cmdiff.h: two sums per step, one double
+    // per walker), each set on its own
     DmcEstSlot est[EST_SLOTS];
     DevBuf<double> est_partial;     // [EST_BLOCKS][widest row]
     long long est_block_steps = 0;  // steps of the estimator block in progress
     int est_last_act = 1;           // aux buffer the last estimator step wrote
-    qmc_dmc() { est[EST_SSF].C = 3; }
+    qmc_dmc()
+    {
+        est[EST_SSF].C = 3;
+        est[EST_CM].C = 2;
+        est[EST_CM].A = 1;
+    }
     bool any_est() const
     {
         return std::any_of(est, est + EST_SLOTS,
@@ -2355,6 +2366,33 @@ extern "C" int qmc_dmc_read_pair_dist(qmc_dmc *d, int64_t nsteps,
     return read_doubles(d->eng, iter_out, s.iter, (size_t)nsteps * s.row());
 }
 
+// The centre-of-mass diffusion estimator (qmc_cmdiff.h) is set on its own as
+// well.  Its rows are one double per walker; begin_block zeroes them, which
+// moves the time origin to the start of the block.
+extern "C" int qmc_dmc_set_cm_diffusion_estimator(qmc_dmc *d, int32_t on)
+{
+    if (!d) return fail("qmc_dmc_set_cm_diffusion_estimator: null argument");
+    HIP_TRY(hipSetDevice(d->eng->device));
+    const DmcEstSpec spec = { on ? 1 : 0, 0, 1, true };
+    return dmc_set_est_slots(d, EST_CM, 1, &spec);
+}
+
+extern "C" int qmc_dmc_read_cm_diffusion(qmc_dmc *d, int64_t nsteps,
+                                         double *iter_out)
+{
+    if (!d || !iter_out)
+        return fail("qmc_dmc_read_cm_diffusion: null argument");
+    const DmcEstSlot &s = d->est[EST_CM];
+    if (!s.on())
+        return fail("qmc_dmc_read_cm_diffusion: the centre-of-mass diffusion "
+                    "estimator is not set");
+    if (nsteps <= 0 || nsteps > d->est_block_steps)
+        return fail("qmc_dmc_read_cm_diffusion: nsteps outside the last "
+                    "estimator block");
+    HIP_TRY(hipSetDevice(d->eng->device));
+    return read_doubles(d->eng, iter_out, s.iter, (size_t)nsteps * s.row());
+}
+
 // Evaluate the estimators on the population yielded by the step that has just
 // been finished (its parents are the buffer that is not `cur`).
 static int dmc_enqueue_estimators(qmc_dmc *d, long long step_idx)
@@ -2385,11 +2423,19 @@ static int dmc_enqueue_estimators(qmc_dmc *d, long long step_idx)
             hipLaunchKernelGGL(dmc_density_kernel, dim3(EST_BLOCKS),
                                dim3(BLOCK), 0, e->stream, a);
             break;
-        default:
+        case EST_PD:
             a.scale = e->dm.L;
             a.scale2 = (double)s.K / (0.5 * e->dm.L);   // as pair_dist_launch
             hipLaunchKernelGGL(dmc_pair_dist_kernel, dim3(EST_BLOCKS),
                                dim3(BLOCK), 0, e->stream, a);
+            break;
+        default:
+            // the children of the step sit in the buffer that is `cur` now
+            a.scale = e->dm.L;
+            a.cpos = d->pos[d->cur];
+            hipLaunchKernelGGL(dmc_cm_diffusion_kernel, dim3(EST_BLOCKS),
+                               dim3(BLOCK), 0, e->stream, a);
+            a.cpos = nullptr;
         }
         const int row = (int)s.row();
         double div = 1.0;
@@ -2416,7 +2462,8 @@ static int dmc_est_begin_block(qmc_dmc *d, long long nsteps)
         for (int k = 0; k < 2; ++k)
             if (s.aux[k])
                 HIP_TRY(hipMemsetAsync(s.aux[k], 0,
-                                       (size_t)d->maxw * s.row() * 8, e->stream));
+                                       (size_t)d->maxw * s.aux_row() * 8,
+                                       e->stream));
     }
     d->est_block_steps = nsteps;
     d->est_last_act = 1;

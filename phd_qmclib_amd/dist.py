@@ -170,6 +170,12 @@ class DistributedDmc:
                 'forward-walking rows are not part of the walker record that '
                 'the population rebalance moves between ranks; switch it off '
                 '(set_pair_dist_estimator(0)) for a distributed run')
+        if getattr(ensemble, 'cm_diffusion', False):
+            raise NotImplementedError(
+                'the centre-of-mass diffusion estimator is single-GPU only: '
+                'its per-walker rows are not part of the walker record that '
+                'the population rebalance moves between ranks; switch it off '
+                '(set_cm_diffusion_estimator(False)) for a distributed run')
         self.ens = ensemble
         self.n = int(num_particles)
         self.device = torch.device(device)

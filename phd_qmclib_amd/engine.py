@@ -77,6 +77,17 @@ def pair_distribution_norm(counts, boson_number, supercell_size):
     return counts * (L / (n * (n - 1) * delta))
 
 
+def superfluid_ratio(iter_cm, num_walkers, boson_number, time_step):
+    """The normalised centre-of-mass diffusion curve of one estimator block,
+    iter_cm[nts, 2] (`DmcEnsemble.read_cm_diffusion`) and num_walkers[nts]:
+    ratio[t] = iter_cm[t, 1] / num_walkers[t] / (2 N t dt) for t >= 1, which
+    tends to rho_s / rho at large lag -> (tau[1:], ratio[1:]), tau = t dt."""
+    iter_cm = np.asarray(iter_cm, dtype=np.float64)
+    nw = np.asarray(num_walkers, dtype=np.float64)
+    tau = np.arange(1, iter_cm.shape[0]) * float(time_step)
+    return tau, iter_cm[1:, 1] / nw[1:] / (2.0 * int(boson_number) * tau)
+
+
 def _pos2d(pos, num_particles,
            expected='pos must have shape (W, boson_number)'):
     """pos as a contiguous fp64 [rows, num_particles] array."""
@@ -586,6 +597,7 @@ class DmcEnsemble:
         check(self._lib.qmc_dmc_create(engine._h, C.byref(p), C.byref(h)))
         self._h = h
         self.pair_dist_bins = 0
+        self.cm_diffusion = False
 
     def close(self):
         if getattr(self, '_h', None):
@@ -699,6 +711,25 @@ class DmcEnsemble:
         forward-walking rows over min(step + 1, pfw))."""
         out = np.zeros((int(nsteps), self.pair_dist_bins))
         check(self._lib.qmc_dmc_read_pair_dist(self._h, int(nsteps), ptr(out)))
+        return out
+
+    def set_cm_diffusion_estimator(self, on=True):
+        """Enable (or disable) the centre-of-mass diffusion estimator of the
+        estimator blocks: the winding-number estimator of the superfluid
+        fraction (`superfluid_ratio`).  Independent of `set_estimators` and
+        `set_pair_dist_estimator`."""
+        check(self._lib.qmc_dmc_set_cm_diffusion_estimator(
+            self._h, int(bool(on))))
+        self.cm_diffusion = bool(on)
+
+    def read_cm_diffusion(self, nsteps: int) -> np.ndarray:
+        """Rows of the last estimator block -> iter_cm[nsteps, 2]: per time
+        step t the sums over the yielded walkers of Y and Y^2, Y being N
+        times the unwrapped centre-of-mass displacement of a walker since the
+        first yielded state of the block (row 0 is zero)."""
+        out = np.zeros((int(nsteps), 2))
+        check(self._lib.qmc_dmc_read_cm_diffusion(self._h, int(nsteps),
+                                                  ptr(out)))
         return out
 
     def read_series(self, nsteps: int) -> DmcSeries:

@@ -15,7 +15,8 @@ forward-walking) run on the device after every kept
 time step and reproduce the reference's semantics, per-block resets included.
 The pair distribution g2(r) is a third such estimator and an extension (the
 reference has none): its forward walking goes through the cloning table, as
-that of S(k).
+that of S(k).  The centre-of-mass diffusion (the winding-number estimator of
+the superfluid fraction) is a fourth, an extension as well.
 """
 import typing as t
 from math import pi, sqrt
@@ -30,7 +31,8 @@ from ..qmc_base import dmc as dmc_base
 from . import model
 
 __all__ = ['CFCSpec', 'DDFParams', 'DensityEstSpec', 'PairDistEstSpec',
-           'Sampling', 'SSFEstSpec', 'State', 'StateError']
+           'Sampling', 'SSFEstSpec', 'State', 'StateError',
+           'SuperfluidEstSpec']
 
 State = dmc_base.State
 
@@ -106,6 +108,13 @@ class PairDistEstSpec:
 
 
 @attr.s(auto_attribs=True, frozen=True)
+class SuperfluidEstSpec:
+    """Centre-of-mass diffusion as a block estimator, pure, with the start of
+    each block as its time origin: rho_s / rho is the large-lag limit of
+    `engine.superfluid_ratio`.  It has no parameters."""
+
+
+@attr.s(auto_attribs=True, frozen=True)
 class Sampling:
     """A class to realize a DMC sampling (mrbp_qmc/dmc.py:143-160)."""
 
@@ -120,6 +129,9 @@ class Sampling:
     jit_parallel: bool = True
     jit_fastmath: bool = False
     fix_stale_energy: bool = False
+    # (keyword only: the positional order of the others is what it was)
+    superfluid_est_spec: t.Optional[SuperfluidEstSpec] = attr.ib(
+        default=None, kw_only=True)
     pair_dist_est_spec: t.Optional[PairDistEstSpec] = None
 
     def __attrs_post_init__(self):
@@ -314,7 +326,11 @@ class Sampling:
         eng, ens = self._start(ini_state)
         dp, sp = self.density_params, self.ssf_params
         pd = self.pair_dist_est_spec
-        with_est = not (dp.assume_none and sp.assume_none) or pd is not None
+        sf = self.superfluid_est_spec
+        with_est = not (dp.assume_none and sp.assume_none) or \
+            pd is not None or sf is not None
+        if sf is not None:
+            ens.set_cm_diffusion_estimator(True)
         if pd is not None:
             ens.set_pair_dist_estimator(pd.num_bins, pd.as_pure_est,
                                         pd.pfw_num_time_steps)
@@ -327,7 +343,7 @@ class Sampling:
         block_idx = 0
         try:
             while True:
-                iter_ssf = iter_density = iter_pair_dist = None
+                iter_ssf = iter_density = iter_pair_dist = iter_cm = None
                 if with_est:
                     # estimators only once the burn-in blocks are over
                     # (qmc_base/dmc.py:916, 928)
@@ -335,6 +351,8 @@ class Sampling:
                         nts, block_idx >= burn_in_blocks)
                     if pd is not None:
                         iter_pair_dist = ens.read_pair_dist(nts)
+                    if sf is not None:
+                        iter_cm = ens.read_cm_diffusion(nts)
                 else:
                     ser = ens.run_block(nts)
                 props = dmc_base.PropsData(ser.energy, ser.weight,
@@ -342,7 +360,8 @@ class Sampling:
                                            ser.accum_energy)
                 last = self._to_state(ens.get_state())
                 yield dmc_base.SamplingBlock(props, iter_density, iter_ssf,
-                                             last, iter_pair_dist)
+                                             last, iter_cm_diffusion=iter_cm,
+                                             iter_pair_dist=iter_pair_dist)
                 block_idx += 1
         finally:
             ens.close()

@@ -14,7 +14,7 @@ from . import dmc, model
 from .vmc_exec import ModelSysConfSpec, _as_int, _opt
 
 __all__ = ['DensityEstSpec', 'ModelSysConfSpec', 'PairDistEstSpec', 'Proc',
-           'ProcInput', 'ProcResult', 'SSFEstSpec']
+           'ProcInput', 'ProcResult', 'SSFEstSpec', 'SuperfluidEstSpec']
 
 ProcInputError = proc_base.ProcInputError
 
@@ -41,6 +41,13 @@ class PairDistEstSpec:
     num_bins: int = attr.ib(converter=_as_int,
                             validator=attr.validators.instance_of(int))
     as_pure_est: bool = attr.ib(default=True, converter=bool)
+
+
+@attr.s(auto_attribs=True, frozen=True)
+class SuperfluidEstSpec:
+    """Centre-of-mass diffusion, the winding-number estimator of the
+    superfluid fraction (an extension; dmc.SuperfluidEstSpec).  It has no
+    parameters: a configuration enables it with an empty mapping."""
 
 
 @attr.s(auto_attribs=True)
@@ -96,6 +103,7 @@ class Proc:
     jit_fastmath: bool = attr.ib(default=False, converter=bool)
     verbose: bool = attr.ib(default=False, converter=bool)
     pair_dist_spec: t.Optional[t.Any] = None
+    superfluid_spec: t.Optional[t.Any] = None
 
     @classmethod
     def from_config(cls, config: t.Mapping):
@@ -127,8 +135,15 @@ class Proc:
             pd_cfg = dict(pd_cfg)
             pd_cfg.pop('pfw_num_time_steps', None)
             pair_dist = PairDistEstSpec(**pd_cfg)
+        sf_cfg = cfg.pop('superfluid_spec', None)
+        superfluid = None
+        if sf_cfg is not None and sf_cfg is not False:
+            # (no parameters: an empty mapping, or just `true`)
+            superfluid = SuperfluidEstSpec(
+                **({} if sf_cfg is True else dict(sf_cfg)))
         return cls(model_spec=model_spec, density_spec=dens, ssf_spec=ssf,
-                   pair_dist_spec=pair_dist, **cfg)
+                   pair_dist_spec=pair_dist, superfluid_spec=superfluid,
+                   **cfg)
 
     def as_config(self):
         return attr.asdict(self, filter=attr.filters.exclude(type(None)))
@@ -144,6 +159,10 @@ class Proc:
     @property
     def should_eval_pair_dist(self):
         return self.pair_dist_spec is not None
+
+    @property
+    def should_eval_superfluid(self):
+        return self.superfluid_spec is not None
 
     @functools.cached_property
     def sampling(self) -> dmc.Sampling:
@@ -165,7 +184,9 @@ class Proc:
                             self.max_num_walkers, self.target_num_walkers,
                             self.num_walkers_control_factor, self.rng_seed,
                             density_est_spec=dens, ssf_est_spec=ssf,
-                            pair_dist_est_spec=pair_dist)
+                            pair_dist_est_spec=pair_dist,
+                            superfluid_est_spec=dmc.SuperfluidEstSpec()
+                            if self.should_eval_superfluid else None)
 
     def build_result(self, state, data):
         return ProcResult(state, self, data)

@@ -92,6 +92,9 @@ class SamplingBlock(t.NamedTuple):
     iter_density: t.Optional[np.ndarray]
     iter_ssf: t.Optional[np.ndarray] = None
     last_state: t.Optional[State] = None
+    #: centre-of-mass diffusion sums per time step [nts, 2] (an extension:
+    #: the superfluid fraction).  The two extensions are given by keyword.
+    iter_cm_diffusion: t.Optional[np.ndarray] = None
     #: pair histograms per time step [nts, num_bins] (an extension: g2(r))
     iter_pair_dist: t.Optional[np.ndarray] = None
 

@@ -11,7 +11,8 @@ import numpy as np
 
 from ...stats import reblock
 
-__all__ = ['DensityBlocks', 'EnergyBlocks', 'NumWalkersBlocks',
+__all__ = ['CMDiffusionBlocks', 'DensityBlocks', 'EnergyBlocks',
+           'NumWalkersBlocks',
            'PairDistBlocks', 'PropBlocks',
            'SSFBlocks', 'SSFPartBlocks',
            'PropsDataBlocks', 'PropsDataSeries', 'SamplingData', 'UnWeightedPropBlocks',
@@ -217,6 +218,33 @@ class PairDistBlocks(SetPropBlocks):
 
 
 @attr.s(auto_attribs=True, frozen=True)
+class CMDiffusionBlocks(UnWeightedPropBlocks):
+    """Centre-of-mass diffusion curves in blocks (an extension: the reference
+    has no superfluid fraction): totals[num_blocks, nts] holds, per kept block
+    and time step t, <Y^2> = iter_cm_diffusion[t, 1] / num_walkers[t], Y being
+    N times the unwrapped centre-of-mass displacement since the start of the
+    block.  The yielded walkers have unit weight and every block restarts the
+    clock, so the blocks are averaged as they are, one column per lag."""
+    totals: np.ndarray
+
+    @property
+    def reblock(self):
+        return reblock.OTFSet.from_non_obj_data(self.totals)
+
+    def superfluid_fraction(self, model_spec, time_step):
+        """-> (tau[nts - 1], ratio[nts - 1], ratio_err[nts - 1]) for the
+        lags tau = t dt, t >= 1: the mean over the blocks of
+        <Y^2>(t) / (2 N t dt), which tends to rho_s / rho at large lag, and
+        its error from the reblocking over blocks."""
+        curves = np.asarray(self.totals)
+        tau = np.arange(1, curves.shape[-1]) * float(time_step)
+        norm = 2.0 * model_spec.boson_number * tau
+        # (lag 0 is zero in every block: it has no statistics)
+        rb = reblock.OTFSet.from_non_obj_data(curves[:, 1:])
+        return tau, rb.mean / norm, rb.mean_eff_error / norm
+
+
+@attr.s(auto_attribs=True, frozen=True)
 class SSFPartBlocks(SetPropBlocks):
     totals: np.ndarray
     weight_totals: np.ndarray
@@ -267,6 +295,8 @@ class PropsDataBlocks:
     num_walkers: NumWalkersBlocks
     density: t.Optional[t.Any] = None
     ss_factor: t.Optional[t.Any] = None
+    # (keyword only: the positional order of the others is what it was)
+    cm_diffusion: t.Optional[t.Any] = attr.ib(default=None, kw_only=True)
     pair_dist: t.Optional[t.Any] = None
 
 
@@ -278,6 +308,8 @@ class PropsDataSeries:
     ssf_blocks: t.Optional[np.ndarray] = None
     #: pair histograms per block and time step [num_blocks, nts, num_bins]
     pair_dist_blocks: t.Optional[np.ndarray] = None
+    #: centre-of-mass diffusion sums per block and time step [num_blocks, nts, 2]
+    cm_diffusion_blocks: t.Optional[np.ndarray] = None
 
     @property
     def props(self):
@@ -294,7 +326,7 @@ class SamplingData:
 # ---- HDF5 layout (qmc_exec/data/dmc.py:99-120, 192-211, 581-613, 683-735,
 # 770-793): <group>/totals [, weight_totals]; ss_factor/{fdk_sqr_abs,fdk_real,
 # fdk_imag}/...; blocks/{energy,weight,num_walkers[,density][,ss_factor]
-# [,pair_dist]} ----
+# [,pair_dist][,cm_diffusion]} ----
 def _export_weighted(self, group):
     group.create_dataset('totals', data=self.totals)
     group.create_dataset('weight_totals', data=self.weight_totals)
@@ -345,17 +377,22 @@ def _blocks_export(self, group):
         self.ss_factor.hdf5_export(group.require_group('ss_factor'))
     if self.pair_dist is not None:
         self.pair_dist.hdf5_export(group.require_group('pair_dist'))
+    if self.cm_diffusion is not None:
+        self.cm_diffusion.hdf5_export(group.require_group('cm_diffusion'))
 
 
 def _blocks_import(cls, group):
     dens, ssf = group.get('density'), group.get('ss_factor')
     pdist = group.get('pair_dist')
+    cmd = group.get('cm_diffusion')
     return cls(EnergyBlocks.from_hdf5_data(group.get('energy')),
                WeightBlocks.from_hdf5_data(group.get('weight')),
                NumWalkersBlocks.from_hdf5_data(group.get('num_walkers')),
                None if dens is None else DensityBlocks.from_hdf5_data(dens),
                None if ssf is None else SSFBlocks.from_hdf5_data(ssf),
-               None if pdist is None else PairDistBlocks.from_hdf5_data(pdist))
+               None if pdist is None else PairDistBlocks.from_hdf5_data(pdist),
+               cm_diffusion=None if cmd is None
+               else CMDiffusionBlocks.from_hdf5_data(cmd))
 
 
 PropsDataBlocks.hdf5_export = _blocks_export

@@ -72,7 +72,8 @@ def exec_vmc(proc, proc_input):
 
 def exec_dmc(proc, proc_input):
     """qmc_exec/dmc/proc.py:136-415: energy / weight / walkers series and the
-    density / S(k) / g2(r) estimators of the kept blocks."""
+    density / S(k) / g2(r) / centre-of-mass diffusion estimators of the kept
+    blocks."""
     from ..mrbp_qmc.dmc_exec import ProcInput
     num_blocks, nts = proc.num_blocks, proc.num_time_steps_block
     keep = proc.keep_iter_data
@@ -85,6 +86,7 @@ def exec_dmc(proc, proc_input):
                              'not valid')
     dens_spec, ssf_spec = proc.density_spec, proc.ssf_spec
     pd_spec = getattr(proc, 'pair_dist_spec', None)
+    sf_spec = getattr(proc, 'superfluid_spec', None)
     blocks_iter = proc.sampling.blocks(proc_input.state, nts, burn)
     block = None
     try:
@@ -108,9 +110,19 @@ def exec_dmc(proc, proc_input):
             npb = pd_spec.num_bins
             pdist = np.zeros((num_blocks, nts, npb) if keep
                              else (num_blocks, npb))
+        # centre-of-mass diffusion: the curve <Y^2>(t) of every block, and
+        # the sums themselves with keep_iter_data
+        cm_curves = cm_iter = None
+        if sf_spec is not None:
+            cm_curves = np.zeros((num_blocks, nts))
+            cm_iter = np.zeros((num_blocks, nts, 2)) if keep else None
         pure_fac = np.ones(num_blocks)
         for b, block in enumerate(islice(blocks_iter, num_blocks)):
             p = block.iter_props
+            if cm_curves is not None:
+                cm_curves[b] = block.iter_cm_diffusion[:, 1] / p.num_walkers
+                if keep:
+                    cm_iter[b] = block.iter_cm_diffusion
             if keep:
                 e[b], w[b], nw[b] = p.energy, p.weight, p.num_walkers
                 re[b], ae[b] = p.ref_energy, p.accum_energy
@@ -158,8 +170,11 @@ def exec_dmc(proc, proc_input):
         dmc_data.EnergyBlocks.from_data(props, reduce_data),
         dmc_data.WeightBlocks.from_data(props, reduce_data),
         dmc_data.NumWalkersBlocks.from_data(props, reduce_data),
-        dens_blocks, ssf_blocks, pd_blocks)
+        dens_blocks, ssf_blocks, pd_blocks,
+        cm_diffusion=None if cm_curves is None
+        else dmc_data.CMDiffusionBlocks(cm_curves))
     data = dmc_data.SamplingData(
         blocks,
-        dmc_data.PropsDataSeries(props, ssf, pdist) if keep else None)
+        dmc_data.PropsDataSeries(props, ssf, pdist, cm_iter) if keep
+        else None)
     return proc.build_result(last_state, data)

@@ -1,9 +1,11 @@
 """Cost of the DMC estimators next to the plain time step (development tool).
 usage: est_bench.py [--bosons N] [--walkers W] [--steps K] [--modes M] [--bins B]
-                    [--pair-bins P] [--repeats R] [--only plain,g2]
-(groups: plain, ssf, density, g2 = g2mixed + g2pure)
+                    [--pair-bins P] [--repeats R] [--relax S] [--only plain,g2]
+(groups: plain, ssf, density, g2 = g2mixed + g2pure, cm)
 Every line is the median over R timed blocks of K steps (after a warm-up
-block), with the shortest and the longest next to it."""
+block and, with --relax, S more untimed steps that bring the population from
+its random start to the stationary state), with the shortest and the longest
+next to it."""
 import argparse
 import os
 import sys
@@ -24,6 +26,7 @@ ap.add_argument('--modes', type=int, default=64)
 ap.add_argument('--bins', type=int, default=128)
 ap.add_argument('--pair-bins', type=int, default=64)
 ap.add_argument('--repeats', type=int, default=5)
+ap.add_argument('--relax', type=int, default=0)
 ap.add_argument('--only', default='plain,ssf,density,g2',
                 help='comma-separated groups to time')
 a = ap.parse_args()
@@ -35,18 +38,22 @@ pos = n * np.random.RandomState(1).random_sample((a.walkers, n))
 maxw = ((a.walkers * 512 // 480) + 255) // 256 * 256
 
 
-def timed(tag, pair=None, **est):
+def timed(tag, pair=None, cm=False, **est):
     d = DmcEnsemble(eng, 6.25e-4, maxw, a.walkers, 0.5, rng_seed=1)
     d.set_state(pos)
     if est:
         d.set_estimators(**est)
     if pair:
         d.set_pair_dist_estimator(**pair)
-    if est or pair:
+    if cm:
+        d.set_cm_diffusion_estimator()
+    if est or pair or cm:
         run = lambda k: d.run_block_est(k, True)
     else:
         run = lambda k: d.run_block(k)
     run(a.steps)
+    if a.relax:
+        run(a.relax)
     eng.sync()
     ts = []
     for _ in range(a.repeats):
@@ -76,5 +83,7 @@ if 'g2' in only or 'g2mixed' in only:
 if 'g2' in only or 'g2pure' in only:
     timed(f'g2 pure  B={a.pair_bins}',
           pair=dict(num_bins=a.pair_bins, pure=True, pfw=a.steps))
+if 'cm' in only:
+    timed('centre-of-mass diffusion', cm=True)
 if 'plain' in only:
     timed('plain (again)')
