@@ -234,8 +234,9 @@ class Sampling:
                 'jit_fastmath=True with jit_parallel=True runs the pair loop '
                 'in float (fp32) on the device: local energy ~1e-7 relative, '
                 'drift of a pair closer than ~1e-6 L loses its leading digits '
-                '(DESIGN.md section 4, "Reduced precision"); the DMC result '
-                'with this option is not pinned against the reference',
+                '(DESIGN.md section 4, "Reduced precision"); single steps '
+                'with this option are pinned against the reference and the '
+                'fp64 oracle at 2e-5, long DMC runs only statistically',
                 RuntimeWarning, stacklevel=3)
         eng = ModelEngine(self.model_spec.cfc_spec, device=device,
                           stream=stream, fast_math=self.fast_math_in_effect)

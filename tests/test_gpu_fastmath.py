@@ -9,7 +9,13 @@ What is pinned here, against the REFERENCE's golden vectors
     report is written to gpurun_out/fastmath_report.json and quoted in
     DESIGN.md;
   * at N = 64, on identical Philox streams, the shift of the block-averaged
-    VMC energy between the two precisions in units of its Monte-Carlo error.
+    VMC and DMC energies between the two precisions in units of their
+    Monte-Carlo error: long runs are pinned statistically only.
+
+`qmc_evaluate` takes the general pair sum.  The float pair loop INSIDE the
+stepping kernels -- the sorted rows at 33 <= N <= 128 -- is pinned by
+tests/test_gpu_fastmath_steps.py: single VMC / DMC steps against the
+reference's goldens and the fp64 oracle at the 2e-5 of this file.
 
 Near-contact configurations (two particles 1e-9 apart) are excluded from the
 float tolerance: sin(pi d / L) of such a pair cancels to nothing in float,
