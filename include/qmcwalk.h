@@ -443,6 +443,28 @@ int qmc_dmc_read_pair_dist(qmc_dmc *d, int64_t nsteps, double *iter_out);
  * not part of the walker record: single-GPU only. */
 int qmc_dmc_set_cm_diffusion_estimator(qmc_dmc *d, int32_t on);
 int qmc_dmc_read_cm_diffusion(qmc_dmc *d, int64_t nsteps, double *iter_out);
+/* Imaginary-time density correlations F(k, tau) = <rho_k(tau) rho_-k(0)> as a
+ * fifth block estimator (an extension: the reference has none).  num_modes K:
+ * k_m = 2 pi m / L, m = 0 .. K-1, the mode set of S(k); num_lags T; lag l is
+ * tau_l = l lag_stride dt.  Per time step t of an estimator block K (T + 2)
+ * doubles, [m][c]: the sums over the yielded walkers of their rows.  The first
+ * step of a block writes the origin of a row, columns T and T+1 = Re, Im
+ * rho_m, and column 0 = |rho_m|^2; step t = l lag_stride, l < T, writes column
+ * l = Re rho_m row[m][T] + Im rho_m row[m][T+1]; the rows travel through the
+ * cloning table (pure, unit weights).  iter[t][m][l] / num_walkers[t]
+ * estimates F(k_m, tau_l) with projection time (t - l lag_stride) dt behind
+ * the later end: pure in the limit of a long block, to be read at the last
+ * step of the block; columns T, T+1 over num_walkers[t] are the pure
+ * <rho_m>.  Columns not measured yet are zero.  Limits: 1 <= num_modes <= 64,
+ * 1 <= num_lags <= 64, lag_stride >= 1, num_modes (num_lags + 2) <= 1024;
+ * num_modes = 0 switches it off.  Set on its own, as the pair distribution.
+ * read_isf copies the first nsteps rows of the last estimator block to the
+ * host, iter_out[nsteps][K][T+2] (synchronises); rows of a block run with
+ * eval_estimators == 0 are zero.  The per-walker rows are not part of the
+ * walker record: single-GPU only. */
+int qmc_dmc_set_isf_estimator(qmc_dmc *d, int32_t num_modes, int32_t num_lags,
+                              int64_t lag_stride);
+int qmc_dmc_read_isf(qmc_dmc *d, int64_t nsteps, double *iter_out);
 /* The yielded ("actual") State after the last step (qmc_base/dmc.py:773-780):
  * confs[maxw][2][N], energy/weight[maxw], mask[maxw], cloning_ref[maxw];
  * scalars[5] = energy, weight, ref_energy, accum_energy, num_walkers. */

@@ -291,10 +291,14 @@ struct EstArgs {
     double *partial;          // [nblocks][K][C] block partial sums
     long long maxw;
     long long step_idx;       // index of the step inside the block
-    long long pfw;            // forward-walking length
+    long long pfw;            // forward-walking length (F(k, tau): lags T)
     int n;                    // particles
     int K;                    // modes or bins
     int pure;
+    int stride = 1;           // F(k, tau) only (qmc_isf.h): time steps per lag,
+                              // its number of lags travels in pfw.  (It sits
+                              // where the struct had padding: the kernel
+                              // arguments of the others are laid out as before.)
     double scale;             // S(k): 4 / L (angle k_m z = (pi/2) * m * scale * z)
                               // density: bin size L / num_bins
                               // g2(r), centre-of-mass diffusion: supercell

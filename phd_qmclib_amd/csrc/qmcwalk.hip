@@ -12,6 +12,7 @@
 #include "qmc_obdm.h"
 #include "qmc_pairdist.h"
 #include "qmc_cmdiff.h"
+#include "qmc_isf.h"
 #include "../../include/qmcwalk.h"
 #include "qmc_probe.h"
 
@@ -1754,6 +1755,7 @@ struct DmcEstSpec {
     int K, pure;
     long long pfw;
     bool aux;
+    int stride = 1;              // (F(k, tau) only)
 };
 
 // One per-step estimator of a population: K modes or bins of C doubles each.
@@ -1763,7 +1765,8 @@ struct DmcEstSlot {
     int A = 0;                   // doubles per walker in the rows; 0: as the
                                  // output, K * C
     int pure = 0;
-    long long pfw = 1;           // forward-walking length
+    long long pfw = 1;           // forward-walking length; F(k, tau): lags
+    int stride = 1;              // F(k, tau): time steps per lag
     DevBuf<double> aux[2];       // [maxw][aux_row()] per-walker rows (null: none kept)
     DevBuf<double> iter;         // [steps][K][C] per-step outputs, grown on demand
     size_t row() const { return (size_t)K * C; }
@@ -1774,7 +1777,7 @@ struct DmcEstSlot {
         aux[0].release();
         aux[1].release();
         iter.release();
-        K = 0; pure = 0; pfw = 1;
+        K = 0; pure = 0; pfw = 1; stride = 1;
     }
     // on (K > 0), with the rows of `maxw` walkers if asked for; a failure
     // leaves it off
@@ -1782,7 +1785,7 @@ struct DmcEstSlot {
     {
         drop();
         if (a.K <= 0) return 0;
-        K = a.K; pure = a.pure; pfw = a.pfw;
+        K = a.K; pure = a.pure; pfw = a.pfw; stride = a.stride;
         for (int b = 0; b < 2 && a.aux; ++b)
             if (aux[b].alloc(maxw * aux_row())) {
                 drop();
@@ -1791,7 +1794,7 @@ struct DmcEstSlot {
         return 0;
     }
 };
-enum { EST_SSF, EST_DENS, EST_PD, EST_CM, EST_SLOTS };
+enum { EST_SSF, EST_DENS, EST_PD, EST_CM, EST_ISF, EST_SLOTS };
 
 struct qmc_dmc {
     qmc_engine *eng = nullptr;
@@ -1826,7 +1829,9 @@ struct qmc_dmc {
     // estimators, in launch order: S(k) (3 doubles per mode) and the density,
     // set together, the pair distribution (qmc_pairdist.h) and the
     // centre-of-mass diffusion (qmc_cmdiff.h: two sums per step, one double
-    // per walker), each set on its own
+    // per walker) and the imaginary-time density correlations (qmc_isf.h:
+    // K modes of C = lags + 2 doubles, C set with the slot), each set on its
+    // own
     DmcEstSlot est[EST_SLOTS];
     DevBuf<double> est_partial;     // [EST_BLOCKS][widest row]
     long long est_block_steps = 0;  // steps of the estimator block in progress
@@ -2393,6 +2398,49 @@ extern "C" int qmc_dmc_read_cm_diffusion(qmc_dmc *d, int64_t nsteps,
     return read_doubles(d->eng, iter_out, s.iter, (size_t)nsteps * s.row());
 }
 
+// The imaginary-time density correlations F(k, tau) (qmc_isf.h) are set on
+// their own as well.  A walker's row is what a step puts out, K modes of
+// C = num_lags + 2 doubles; the first step of a block writes the origin, so
+// begin_block moves it.  K (T + 2) <= ISF_MAXROW keeps a row within 16 indices
+// per lane (8 KB per walker and buffer).
+extern "C" int qmc_dmc_set_isf_estimator(qmc_dmc *d, int32_t num_modes,
+                                         int32_t num_lags, int64_t lag_stride)
+{
+    if (!d) return fail("qmc_dmc_set_isf_estimator: null argument");
+    if (num_modes < 0 || num_modes > 64)
+        return fail("qmc_dmc_set_isf_estimator: num_modes must be in [0, 64]");
+    if (num_modes > 0) {
+        if (num_lags < 1 || num_lags > 64)
+            return fail("qmc_dmc_set_isf_estimator: num_lags must be in "
+                        "[1, 64]");
+        if (lag_stride < 1 || lag_stride > INT32_MAX)
+            return fail("qmc_dmc_set_isf_estimator: lag_stride must be in "
+                        "[1, 2^31 - 1]");
+        if (num_modes * (num_lags + 2) > ISF_MAXROW)
+            return fail("qmc_dmc_set_isf_estimator: num_modes * (num_lags + 2) "
+                        "must not exceed 1024");
+    }
+    HIP_TRY(hipSetDevice(d->eng->device));
+    const DmcEstSpec spec = { num_modes, 0, num_modes > 0 ? num_lags : 1, true,
+                              num_modes > 0 ? (int)lag_stride : 1 };
+    // (off: the slot is dropped and C does not matter)
+    d->est[EST_ISF].C = num_modes > 0 ? num_lags + 2 : 1;
+    return dmc_set_est_slots(d, EST_ISF, 1, &spec);
+}
+
+extern "C" int qmc_dmc_read_isf(qmc_dmc *d, int64_t nsteps, double *iter_out)
+{
+    if (!d || !iter_out) return fail("qmc_dmc_read_isf: null argument");
+    const DmcEstSlot &s = d->est[EST_ISF];
+    if (!s.on())
+        return fail("qmc_dmc_read_isf: the F(k, tau) estimator is not set");
+    if (nsteps <= 0 || nsteps > d->est_block_steps)
+        return fail("qmc_dmc_read_isf: nsteps outside the last estimator "
+                    "block");
+    HIP_TRY(hipSetDevice(d->eng->device));
+    return read_doubles(d->eng, iter_out, s.iter, (size_t)nsteps * s.row());
+}
+
 // Evaluate the estimators on the population yielded by the step that has just
 // been finished (its parents are the buffer that is not `cur`).
 static int dmc_enqueue_estimators(qmc_dmc *d, long long step_idx)
@@ -2429,13 +2477,20 @@ static int dmc_enqueue_estimators(qmc_dmc *d, long long step_idx)
             hipLaunchKernelGGL(dmc_pair_dist_kernel, dim3(EST_BLOCKS),
                                dim3(BLOCK), 0, e->stream, a);
             break;
-        default:
+        case EST_CM:
             // the children of the step sit in the buffer that is `cur` now
             a.scale = e->dm.L;
             a.cpos = d->pos[d->cur];
             hipLaunchKernelGGL(dmc_cm_diffusion_kernel, dim3(EST_BLOCKS),
                                dim3(BLOCK), 0, e->stream, a);
             a.cpos = nullptr;
+            break;
+        default:
+            a.scale = 4.0 / e->dm.L;              // as S(k)
+            a.stride = s.stride;
+            hipLaunchKernelGGL(dmc_isf_kernel, dim3(EST_BLOCKS), dim3(BLOCK),
+                               0, e->stream, a);
+            a.stride = 1;
         }
         const int row = (int)s.row();
         double div = 1.0;

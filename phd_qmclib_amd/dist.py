@@ -176,6 +176,12 @@ class DistributedDmc:
                 'its per-walker rows are not part of the walker record that '
                 'the population rebalance moves between ranks; switch it off '
                 '(set_cm_diffusion_estimator(False)) for a distributed run')
+        if getattr(ensemble, 'isf_shape', None):
+            raise NotImplementedError(
+                'the F(k, tau) estimator is single-GPU only: '
+                'its per-walker rows are not part of the walker record that '
+                'the population rebalance moves between ranks; switch it off '
+                '(set_isf_estimator(0)) for a distributed run')
         self.ens = ensemble
         self.n = int(num_particles)
         self.device = torch.device(device)

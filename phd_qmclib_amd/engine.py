@@ -88,6 +88,30 @@ def superfluid_ratio(iter_cm, num_walkers, boson_number, time_step):
     return tau, iter_cm[1:, 1] / nw[1:] / (2.0 * int(boson_number) * tau)
 
 
+def intermediate_scattering(iter_isf, num_walkers, boson_number, time_step,
+                            lag_stride):
+    """The imaginary-time density correlations of one estimator block,
+    iter_isf[nts, K, T + 2] (`DmcEnsemble.read_isf`) and num_walkers[nts], read
+    at the last step of the block, where the projection behind every lag is
+    longest -> (tau[T], F[T, K] / N, rho_mean[K] complex):
+    tau[l] = l lag_stride dt, F[l, m] / N = iter_isf[-1, m, l] /
+    num_walkers[-1] / N (it is S(k_m) at lag 0 and decays as
+    sum_n |<n|rho_k|0>|^2 exp(-(E_n - E_0) tau)), rho_mean[m] the pure
+    <rho_m> of columns T, T + 1.  The estimate is pure in the limit of a long
+    block: lag l has projection time (nts - 1 - l lag_stride) dt behind its
+    later end, and lags close to the end of the block are mixed there.  Lags
+    the block did not reach (l lag_stride >= nts) are zero.  The connected
+    function, which matters at the reciprocal vectors of the lattice, is
+    F[l, m] - |rho_mean[m]|^2 (before the division by N)."""
+    iter_isf = np.asarray(iter_isf, dtype=np.float64)
+    nw = float(np.asarray(num_walkers)[-1])
+    num_lags = iter_isf.shape[-1] - 2
+    last = iter_isf[-1] / nw
+    tau = np.arange(num_lags) * (int(lag_stride) * float(time_step))
+    rho_mean = last[:, num_lags] + 1j * last[:, num_lags + 1]
+    return tau, last[:, :num_lags].T / int(boson_number), rho_mean
+
+
 def _pos2d(pos, num_particles,
            expected='pos must have shape (W, boson_number)'):
     """pos as a contiguous fp64 [rows, num_particles] array."""
@@ -598,6 +622,7 @@ class DmcEnsemble:
         self._h = h
         self.pair_dist_bins = 0
         self.cm_diffusion = False
+        self.isf_shape = None
 
     def close(self):
         if getattr(self, '_h', None):
@@ -730,6 +755,32 @@ class DmcEnsemble:
         out = np.zeros((int(nsteps), 2))
         check(self._lib.qmc_dmc_read_cm_diffusion(self._h, int(nsteps),
                                                   ptr(out)))
+        return out
+
+    def set_isf_estimator(self, num_modes, num_lags=1, lag_stride=1):
+        """Enable the imaginary-time density correlations F(k, tau) of the
+        estimator blocks (`intermediate_scattering`): num_modes momenta
+        k_m = 2 pi m / L (the mode set of S(k)), num_lags lags tau_l =
+        l lag_stride dt; num_modes = 0 disables them.  1 <= num_modes <= 64,
+        1 <= num_lags <= 64, num_modes (num_lags + 2) <= 1024.  Independent of
+        the other estimators."""
+        check(self._lib.qmc_dmc_set_isf_estimator(
+            self._h, int(num_modes), int(num_lags), int(lag_stride)))
+        self.isf_shape = (int(num_modes), int(num_lags) + 2) \
+            if int(num_modes) > 0 else None
+
+    def read_isf(self, nsteps: int) -> np.ndarray:
+        """Rows of the last estimator block -> iter_isf[nsteps, K, T + 2]: per
+        time step t and mode m the sums over the yielded walkers of
+        rho_m(t) rho_m(0)^* (real part) in column l once step l lag_stride has
+        run (zero before), and of Re, Im rho_m(0) in columns T, T + 1; the
+        rows travel through the cloning table, so the earlier end is weighted
+        by its descendants (pure in the limit of a long block; read the last
+        step)."""
+        if self.isf_shape is None:
+            raise QmcError('read_isf: the F(k, tau) estimator is not set')
+        out = np.zeros((int(nsteps),) + self.isf_shape)
+        check(self._lib.qmc_dmc_read_isf(self._h, int(nsteps), ptr(out)))
         return out
 
     def read_series(self, nsteps: int) -> DmcSeries:

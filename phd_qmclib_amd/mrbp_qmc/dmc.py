@@ -16,7 +16,9 @@ time step and reproduce the reference's semantics, per-block resets included.
 The pair distribution g2(r) is a third such estimator and an extension (the
 reference has none): its forward walking goes through the cloning table, as
 that of S(k).  The centre-of-mass diffusion (the winding-number estimator of
-the superfluid fraction) is a fourth, an extension as well.
+the superfluid fraction) is a fourth, an extension as well, and the
+imaginary-time density correlations F(k, tau), whose decay gives the
+excitation spectrum, are a fifth.
 """
 import typing as t
 from math import pi, sqrt
@@ -30,7 +32,8 @@ from ..engine import (DmcEnsemble, ModelEngine, pair_distribution_bins,
 from ..qmc_base import dmc as dmc_base
 from . import model
 
-__all__ = ['CFCSpec', 'DDFParams', 'DensityEstSpec', 'PairDistEstSpec',
+__all__ = ['CFCSpec', 'DDFParams', 'DensityEstSpec', 'ISFEstSpec',
+           'PairDistEstSpec',
            'Sampling', 'SSFEstSpec', 'State', 'StateError',
            'SuperfluidEstSpec']
 
@@ -115,6 +118,21 @@ class SuperfluidEstSpec:
 
 
 @attr.s(auto_attribs=True, frozen=True)
+class ISFEstSpec:
+    """Imaginary-time density correlations F(k, tau) = <rho_k(tau) rho_-k(0)>
+    as a block estimator: `num_modes` momenta k_m = 2 pi m / L (1..64, the
+    mode set of `SSFEstSpec`), `num_lags` lags (1..64) tau_l =
+    l lag_stride dt, num_modes (num_lags + 2) <= 1024.  The start of each
+    block is the time origin and the rows travel through the cloning table:
+    the estimate is pure in the limit of a long block and is read at the last
+    step of the block (`engine.intermediate_scattering`); lags close to the
+    end of the block are mixed at their later end."""
+    num_modes: int
+    num_lags: int
+    lag_stride: int = 1
+
+
+@attr.s(auto_attribs=True, frozen=True)
 class Sampling:
     """A class to realize a DMC sampling (mrbp_qmc/dmc.py:143-160)."""
 
@@ -132,6 +150,7 @@ class Sampling:
     # (keyword only: the positional order of the others is what it was)
     superfluid_est_spec: t.Optional[SuperfluidEstSpec] = attr.ib(
         default=None, kw_only=True)
+    isf_est_spec: t.Optional[ISFEstSpec] = attr.ib(default=None, kw_only=True)
     pair_dist_est_spec: t.Optional[PairDistEstSpec] = None
 
     def __attrs_post_init__(self):
@@ -181,6 +200,14 @@ class Sampling:
                             'specified')
         return pair_distribution_bins(self.model_spec.supercell_size,
                                       self.pair_dist_est_spec.num_bins)
+
+    @property
+    def isf_momenta(self) -> np.ndarray:
+        """Momenta k_m of the F(k, tau) estimator."""
+        if self.isf_est_spec is None:
+            raise TypeError('the F(k, tau) spec has not been specified')
+        return (np.arange(self.isf_est_spec.num_modes) * 2 * pi /
+                self.model_spec.supercell_size)
 
     @property
     def cfc_spec(self) -> CFCSpec:
@@ -328,8 +355,11 @@ class Sampling:
         dp, sp = self.density_params, self.ssf_params
         pd = self.pair_dist_est_spec
         sf = self.superfluid_est_spec
+        isf = self.isf_est_spec
         with_est = not (dp.assume_none and sp.assume_none) or \
-            pd is not None or sf is not None
+            pd is not None or sf is not None or isf is not None
+        if isf is not None:
+            ens.set_isf_estimator(isf.num_modes, isf.num_lags, isf.lag_stride)
         if sf is not None:
             ens.set_cm_diffusion_estimator(True)
         if pd is not None:
@@ -345,6 +375,7 @@ class Sampling:
         try:
             while True:
                 iter_ssf = iter_density = iter_pair_dist = iter_cm = None
+                iter_isf = None
                 if with_est:
                     # estimators only once the burn-in blocks are over
                     # (qmc_base/dmc.py:916, 928)
@@ -354,6 +385,8 @@ class Sampling:
                         iter_pair_dist = ens.read_pair_dist(nts)
                     if sf is not None:
                         iter_cm = ens.read_cm_diffusion(nts)
+                    if isf is not None:
+                        iter_isf = ens.read_isf(nts)
                 else:
                     ser = ens.run_block(nts)
                 props = dmc_base.PropsData(ser.energy, ser.weight,
@@ -362,6 +395,7 @@ class Sampling:
                 last = self._to_state(ens.get_state())
                 yield dmc_base.SamplingBlock(props, iter_density, iter_ssf,
                                              last, iter_cm_diffusion=iter_cm,
+                                             iter_isf=iter_isf,
                                              iter_pair_dist=iter_pair_dist)
                 block_idx += 1
         finally:

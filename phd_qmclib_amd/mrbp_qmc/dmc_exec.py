@@ -13,7 +13,8 @@ from ..qmc_exec import proc as proc_base
 from . import dmc, model
 from .vmc_exec import ModelSysConfSpec, _as_int, _opt
 
-__all__ = ['DensityEstSpec', 'ModelSysConfSpec', 'PairDistEstSpec', 'Proc',
+__all__ = ['DensityEstSpec', 'ISFEstSpec', 'ModelSysConfSpec',
+           'PairDistEstSpec', 'Proc',
            'ProcInput', 'ProcResult', 'SSFEstSpec', 'SuperfluidEstSpec']
 
 ProcInputError = proc_base.ProcInputError
@@ -48,6 +49,16 @@ class SuperfluidEstSpec:
     """Centre-of-mass diffusion, the winding-number estimator of the
     superfluid fraction (an extension; dmc.SuperfluidEstSpec).  It has no
     parameters: a configuration enables it with an empty mapping."""
+
+
+@attr.s(auto_attribs=True, frozen=True)
+class ISFEstSpec:
+    """Imaginary-time density correlations F(k, tau) (an extension;
+    dmc.ISFEstSpec): num_modes momenta, num_lags lags of lag_stride time
+    steps each."""
+    num_modes: int = attr.ib(converter=_as_int)
+    num_lags: int = attr.ib(converter=_as_int)
+    lag_stride: int = attr.ib(default=1, converter=_as_int)
 
 
 @attr.s(auto_attribs=True)
@@ -104,6 +115,7 @@ class Proc:
     verbose: bool = attr.ib(default=False, converter=bool)
     pair_dist_spec: t.Optional[t.Any] = None
     superfluid_spec: t.Optional[t.Any] = None
+    isf_spec: t.Optional[t.Any] = None
 
     @classmethod
     def from_config(cls, config: t.Mapping):
@@ -141,9 +153,11 @@ class Proc:
             # (no parameters: an empty mapping, or just `true`)
             superfluid = SuperfluidEstSpec(
                 **({} if sf_cfg is True else dict(sf_cfg)))
+        isf_cfg = cfg.pop('isf_spec', None)
+        isf = ISFEstSpec(**isf_cfg) if isf_cfg is not None else None
         return cls(model_spec=model_spec, density_spec=dens, ssf_spec=ssf,
                    pair_dist_spec=pair_dist, superfluid_spec=superfluid,
-                   **cfg)
+                   isf_spec=isf, **cfg)
 
     def as_config(self):
         return attr.asdict(self, filter=attr.filters.exclude(type(None)))
@@ -164,12 +178,20 @@ class Proc:
     def should_eval_superfluid(self):
         return self.superfluid_spec is not None
 
+    @property
+    def should_eval_isf(self):
+        return self.isf_spec is not None
+
     @functools.cached_property
     def sampling(self) -> dmc.Sampling:
         """dmc_exec/proc.py:336-371: the forward walking of the pure
         estimators spans one block."""
         pfw = self.num_time_steps_block
-        dens = ssf = pair_dist = None
+        dens = ssf = pair_dist = isf = None
+        if self.should_eval_isf:
+            isf = dmc.ISFEstSpec(self.isf_spec.num_modes,
+                                 self.isf_spec.num_lags,
+                                 self.isf_spec.lag_stride)
         if self.should_eval_pair_dist:
             pair_dist = dmc.PairDistEstSpec(self.pair_dist_spec.num_bins,
                                             self.pair_dist_spec.as_pure_est,
@@ -184,7 +206,7 @@ class Proc:
                             self.max_num_walkers, self.target_num_walkers,
                             self.num_walkers_control_factor, self.rng_seed,
                             density_est_spec=dens, ssf_est_spec=ssf,
-                            pair_dist_est_spec=pair_dist,
+                            pair_dist_est_spec=pair_dist, isf_est_spec=isf,
                             superfluid_est_spec=dmc.SuperfluidEstSpec()
                             if self.should_eval_superfluid else None)
 

@@ -95,6 +95,9 @@ class SamplingBlock(t.NamedTuple):
     #: centre-of-mass diffusion sums per time step [nts, 2] (an extension:
     #: the superfluid fraction).  The two extensions are given by keyword.
     iter_cm_diffusion: t.Optional[np.ndarray] = None
+    #: F(k, tau) row sums per time step [nts, num_modes, num_lags + 2] (an
+    #: extension: the imaginary-time density correlations), by keyword too
+    iter_isf: t.Optional[np.ndarray] = None
     #: pair histograms per time step [nts, num_bins] (an extension: g2(r))
     iter_pair_dist: t.Optional[np.ndarray] = None
 

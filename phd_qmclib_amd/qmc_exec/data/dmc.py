@@ -12,7 +12,7 @@ import numpy as np
 from ...stats import reblock
 
 __all__ = ['CMDiffusionBlocks', 'DensityBlocks', 'EnergyBlocks',
-           'NumWalkersBlocks',
+           'ISFBlocks', 'NumWalkersBlocks',
            'PairDistBlocks', 'PropBlocks',
            'SSFBlocks', 'SSFPartBlocks',
            'PropsDataBlocks', 'PropsDataSeries', 'SamplingData', 'UnWeightedPropBlocks',
@@ -245,6 +245,45 @@ class CMDiffusionBlocks(UnWeightedPropBlocks):
 
 
 @attr.s(auto_attribs=True, frozen=True)
+class ISFBlocks(UnWeightedPropBlocks):
+    """Imaginary-time density correlations in blocks (an extension: the
+    reference has none): totals[num_blocks, K, T + 2] holds, per kept block,
+    the row of the last time step of the block over its num_walkers,
+    iter_isf[nts - 1] / num_walkers[nts - 1]: columns l < T are
+    F(k_m, tau_l), columns T, T + 1 the pure Re, Im <rho_m>.  The yielded
+    walkers have unit weight and every block resets the origin, so the blocks
+    are averaged as they are, one column per (mode, lag).  The estimate is
+    pure in the limit of a long block: lag l has (nts - 1 - l lag_stride) dt
+    of projection behind its later end, and lags close to the end of the block
+    are mixed there."""
+    totals: np.ndarray
+
+    @property
+    def reblock(self):
+        rows = np.asarray(self.totals)
+        return reblock.OTFSet.from_non_obj_data(rows.reshape(len(rows), -1))
+
+    def scattering_function(self, model_spec, time_step, lag_stride=1):
+        """-> (tau[T], F[T, K] / N, F_err[T, K] / N, F_conn[T, K] / N): the
+        lags tau_l = l lag_stride dt, per mode the mean over the blocks of
+        F(k_m, tau_l) with its error from the reblocking over blocks, and the
+        connected function F - |<rho_m>|^2 from the means of columns T, T + 1
+        (it matters at the reciprocal vectors of the lattice); all per
+        particle, so that lag 0 is S(k_m)."""
+        rows = np.asarray(self.totals)
+        num_lags = rows.shape[-1] - 2
+        n = model_spec.boson_number
+        tau = np.arange(num_lags) * (int(lag_stride) * float(time_step))
+        rb = self.reblock
+        mean = rb.mean.reshape(rows.shape[1:])
+        err = rb.mean_eff_error.reshape(rows.shape[1:])
+        rho_sqr = mean[:, num_lags] ** 2 + mean[:, num_lags + 1] ** 2
+        f = mean[:, :num_lags]
+        return (tau, f.T / n, err[:, :num_lags].T / n,
+                (f - rho_sqr[:, np.newaxis]).T / n)
+
+
+@attr.s(auto_attribs=True, frozen=True)
 class SSFPartBlocks(SetPropBlocks):
     totals: np.ndarray
     weight_totals: np.ndarray
@@ -297,6 +336,7 @@ class PropsDataBlocks:
     ss_factor: t.Optional[t.Any] = None
     # (keyword only: the positional order of the others is what it was)
     cm_diffusion: t.Optional[t.Any] = attr.ib(default=None, kw_only=True)
+    isf: t.Optional[t.Any] = attr.ib(default=None, kw_only=True)
     pair_dist: t.Optional[t.Any] = None
 
 
@@ -310,6 +350,8 @@ class PropsDataSeries:
     pair_dist_blocks: t.Optional[np.ndarray] = None
     #: centre-of-mass diffusion sums per block and time step [num_blocks, nts, 2]
     cm_diffusion_blocks: t.Optional[np.ndarray] = None
+    #: F(k, tau) row sums per block and time step [num_blocks, nts, K, T + 2]
+    isf_blocks: t.Optional[np.ndarray] = None
 
     @property
     def props(self):
@@ -326,7 +368,7 @@ class SamplingData:
 # ---- HDF5 layout (qmc_exec/data/dmc.py:99-120, 192-211, 581-613, 683-735,
 # 770-793): <group>/totals [, weight_totals]; ss_factor/{fdk_sqr_abs,fdk_real,
 # fdk_imag}/...; blocks/{energy,weight,num_walkers[,density][,ss_factor]
-# [,pair_dist][,cm_diffusion]} ----
+# [,pair_dist][,cm_diffusion][,isf]} ----
 def _export_weighted(self, group):
     group.create_dataset('totals', data=self.totals)
     group.create_dataset('weight_totals', data=self.weight_totals)
@@ -379,12 +421,15 @@ def _blocks_export(self, group):
         self.pair_dist.hdf5_export(group.require_group('pair_dist'))
     if self.cm_diffusion is not None:
         self.cm_diffusion.hdf5_export(group.require_group('cm_diffusion'))
+    if self.isf is not None:
+        self.isf.hdf5_export(group.require_group('isf'))
 
 
 def _blocks_import(cls, group):
     dens, ssf = group.get('density'), group.get('ss_factor')
     pdist = group.get('pair_dist')
     cmd = group.get('cm_diffusion')
+    isf = group.get('isf')
     return cls(EnergyBlocks.from_hdf5_data(group.get('energy')),
                WeightBlocks.from_hdf5_data(group.get('weight')),
                NumWalkersBlocks.from_hdf5_data(group.get('num_walkers')),
@@ -392,7 +437,8 @@ def _blocks_import(cls, group):
                None if ssf is None else SSFBlocks.from_hdf5_data(ssf),
                None if pdist is None else PairDistBlocks.from_hdf5_data(pdist),
                cm_diffusion=None if cmd is None
-               else CMDiffusionBlocks.from_hdf5_data(cmd))
+               else CMDiffusionBlocks.from_hdf5_data(cmd),
+               isf=None if isf is None else ISFBlocks.from_hdf5_data(isf))
 
 
 PropsDataBlocks.hdf5_export = _blocks_export

@@ -72,8 +72,8 @@ def exec_vmc(proc, proc_input):
 
 def exec_dmc(proc, proc_input):
     """qmc_exec/dmc/proc.py:136-415: energy / weight / walkers series and the
-    density / S(k) / g2(r) / centre-of-mass diffusion estimators of the kept
-    blocks."""
+    density / S(k) / g2(r) / centre-of-mass diffusion / F(k, tau) estimators
+    of the kept blocks."""
     from ..mrbp_qmc.dmc_exec import ProcInput
     num_blocks, nts = proc.num_blocks, proc.num_time_steps_block
     keep = proc.keep_iter_data
@@ -87,6 +87,7 @@ def exec_dmc(proc, proc_input):
     dens_spec, ssf_spec = proc.density_spec, proc.ssf_spec
     pd_spec = getattr(proc, 'pair_dist_spec', None)
     sf_spec = getattr(proc, 'superfluid_spec', None)
+    isf_spec = getattr(proc, 'isf_spec', None)
     blocks_iter = proc.sampling.blocks(proc_input.state, nts, burn)
     block = None
     try:
@@ -116,6 +117,13 @@ def exec_dmc(proc, proc_input):
         if sf_spec is not None:
             cm_curves = np.zeros((num_blocks, nts))
             cm_iter = np.zeros((num_blocks, nts, 2)) if keep else None
+        # F(k, tau): the last step's row of every block over its walkers, and
+        # the row sums of every step with keep_iter_data
+        isf_rows = isf_iter = None
+        if isf_spec is not None:
+            kc = (isf_spec.num_modes, isf_spec.num_lags + 2)
+            isf_rows = np.zeros((num_blocks,) + kc)
+            isf_iter = np.zeros((num_blocks, nts) + kc) if keep else None
         pure_fac = np.ones(num_blocks)
         for b, block in enumerate(islice(blocks_iter, num_blocks)):
             p = block.iter_props
@@ -123,6 +131,10 @@ def exec_dmc(proc, proc_input):
                 cm_curves[b] = block.iter_cm_diffusion[:, 1] / p.num_walkers
                 if keep:
                     cm_iter[b] = block.iter_cm_diffusion
+            if isf_rows is not None:
+                isf_rows[b] = block.iter_isf[nts - 1] / p.num_walkers[nts - 1]
+                if keep:
+                    isf_iter[b] = block.iter_isf
             if keep:
                 e[b], w[b], nw[b] = p.energy, p.weight, p.num_walkers
                 re[b], ae[b] = p.ref_energy, p.accum_energy
@@ -172,9 +184,10 @@ def exec_dmc(proc, proc_input):
         dmc_data.NumWalkersBlocks.from_data(props, reduce_data),
         dens_blocks, ssf_blocks, pd_blocks,
         cm_diffusion=None if cm_curves is None
-        else dmc_data.CMDiffusionBlocks(cm_curves))
+        else dmc_data.CMDiffusionBlocks(cm_curves),
+        isf=None if isf_rows is None else dmc_data.ISFBlocks(isf_rows))
     data = dmc_data.SamplingData(
         blocks,
-        dmc_data.PropsDataSeries(props, ssf, pdist, cm_iter) if keep
+        dmc_data.PropsDataSeries(props, ssf, pdist, cm_iter, isf_iter) if keep
         else None)
     return proc.build_result(last_state, data)

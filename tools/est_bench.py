@@ -1,7 +1,8 @@
 """Cost of the DMC estimators next to the plain time step (development tool).
 usage: est_bench.py [--bosons N] [--walkers W] [--steps K] [--modes M] [--bins B]
-                    [--pair-bins P] [--repeats R] [--relax S] [--only plain,g2]
-(groups: plain, ssf, density, g2 = g2mixed + g2pure, cm)
+                    [--pair-bins P] [--repeats R] [--relax S] [--isf K,T,q]
+                    [--only plain,g2]
+(groups: plain, ssf, density, g2 = g2mixed + g2pure, cm, isf)
 Every line is the median over R timed blocks of K steps (after a warm-up
 block and, with --relax, S more untimed steps that bring the population from
 its random start to the stationary state), with the shortest and the longest
@@ -27,6 +28,8 @@ ap.add_argument('--bins', type=int, default=128)
 ap.add_argument('--pair-bins', type=int, default=64)
 ap.add_argument('--repeats', type=int, default=5)
 ap.add_argument('--relax', type=int, default=0)
+ap.add_argument('--isf', default='16,16,8',
+                help='modes, lags, lag stride of the F(k, tau) estimator')
 ap.add_argument('--only', default='plain,ssf,density,g2',
                 help='comma-separated groups to time')
 a = ap.parse_args()
@@ -38,7 +41,7 @@ pos = n * np.random.RandomState(1).random_sample((a.walkers, n))
 maxw = ((a.walkers * 512 // 480) + 255) // 256 * 256
 
 
-def timed(tag, pair=None, cm=False, **est):
+def timed(tag, pair=None, cm=False, isf=None, **est):
     d = DmcEnsemble(eng, 6.25e-4, maxw, a.walkers, 0.5, rng_seed=1)
     d.set_state(pos)
     if est:
@@ -47,7 +50,9 @@ def timed(tag, pair=None, cm=False, **est):
         d.set_pair_dist_estimator(**pair)
     if cm:
         d.set_cm_diffusion_estimator()
-    if est or pair or cm:
+    if isf:
+        d.set_isf_estimator(*isf)
+    if est or pair or cm or isf:
         run = lambda k: d.run_block_est(k, True)
     else:
         run = lambda k: d.run_block(k)
@@ -85,5 +90,7 @@ if 'g2' in only or 'g2pure' in only:
           pair=dict(num_bins=a.pair_bins, pure=True, pfw=a.steps))
 if 'cm' in only:
     timed('centre-of-mass diffusion', cm=True)
+if 'isf' in only:
+    timed(f'F(k, tau) K,T,q={a.isf}', isf=[int(v) for v in a.isf.split(',')])
 if 'plain' in only:
     timed('plain (again)')
