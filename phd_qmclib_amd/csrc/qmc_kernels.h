@@ -91,35 +91,28 @@ __device__ __forceinline__ double qmc_lane_f64(double v, int k)
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
-// The fused VMC yields (vmc_step_kernel, VmcFused): where particles 0 and 1
-// sit -- lane | slot << 6 -- so that the accept words are two readlanes.  The
-// labels move only with an accepted move; one ballot each, then.  (n = 1:
-// particle 0 gives both words, as in vmc_step_kernel.)
-template <int P>
-__device__ __forceinline__ void vmc_accept_lanes(const int (&lab)[P], int n,
-                                                 int &src0, int &src1)
+// The fused VMC yields (vmc_step_kernel, VmcFused): the accept thresholds of 64
+// yields at once, one yield per lane.  The accept draw of a step is made of the
+// second words of the move blocks of particles 0 and 1, and a block's counter
+// is (chain, step, particle index): it needs neither the labels nor the row,
+// so lane l draws both blocks of step `step0 + l` itself and takes the
+// logarithm there -- 64 logarithms for the price of one, and the yield reads
+// its threshold h = log(u) / 2 with two readlanes.  u = 0 (accept whatever the
+// ratio is) is kept as a NaN.  The Metropolis test adds h to log|psi|; the
+// per-yield kernels form 0.5 log(u) + log|psi| in one fused multiply-add: the
+// product by 0.5 is exact, so both round the same sum once.  (n = 1: particle
+// 0 gives both words, as in vmc_step_kernel.)
+__device__ __forceinline__ double vmc_accept_thresholds(uint64_t seed,
+                                                        uint32_t slot,
+                                                        uint32_t step0, int lane,
+                                                        int n)
 {
-    src0 = 0;
-    src1 = 0;
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const unsigned long long b0 = __ballot(lab[p] == 0);
-        const unsigned long long b1 = __ballot(lab[p] == 1);
-        if (b0) src0 = ((int)__ffsll((long long)b0) - 1) | (p << 6);
-        if (b1) src1 = ((int)__ffsll((long long)b1) - 1) | (p << 6);
-    }
-    if (n == 1) src1 = src0;
-}
-template <int P>
-__device__ __forceinline__ unsigned int vmc_read_slot(const uint32_t (&wd)[P],
-                                                      int src)
-{
-    unsigned int r = 0u;
-#pragma unroll
-    for (int p = 0; p < P; ++p)
-        if ((src >> 6) == p)
-            r = (unsigned)__builtin_amdgcn_readlane((int)wd[p], src & 63);
-    return r;
+    uint32_t m0, m1, hi, lo;
+    vmc_move_block(seed, slot, step0 + (uint32_t)lane, 0u, m0, hi);
+    vmc_move_block(seed, slot, step0 + (uint32_t)lane, n == 1 ? 0u : 1u, m1, lo);
+    const double ua = u53(hi, lo);
+    const double h = 0.5 * log_pos(ua);
+    return ua <= 0.0 ? __builtin_nan("") : h;
 }
 
 // Minimum waves per SIMD asked of the register allocator for the N <= 64
@@ -402,7 +395,8 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
     constexpr bool FUSED = STEADY && VmcFused<G, P, ZC>::ON;
     double zc[P];
     int labc[P];
-    int src0 = 0, src1 = 0;   // lanes of particles 0 and 1 (FUSED)
+    // FUSED: lane l holds log(u) / 2 of the accept draw of yield (s & ~63) + l
+    [[maybe_unused]] double thr = 0.0;
     if constexpr (FUSED) {
 #pragma unroll
         for (int p = 0; p < P; ++p) {
@@ -410,7 +404,6 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
             zc[p] = (i < n) ? a.pos[wr * n + i] : 0.0;
             labc[p] = (i < n) ? (int)a.label[wr * n + i] : i;
         }
-        vmc_accept_lanes<P>(labc, n, src0, src1);
     }
     bool any_acc = false;     // FUSED: some yield of the launch accepted
     const unsigned int nst = FUSED ? a.nsteps : 1u;
@@ -424,6 +417,11 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
     // derived again on every trip instead of being hoisted out of the loop and
     // held in registers across it)
     const int gl = FUSED ? qmc_opaque(gl_top) : gl_top;
+    if constexpr (FUSED) {
+        // (a block longer than 64 yields refills every 64 trips)
+        if ((s & 63u) == 0u)
+            thr = vmc_accept_thresholds(a.seed, slot, step, gl, n);
+    }
     QMC_SECTION("load+philox+wrap");
     double zn[P];
     int labn[P];              // original particle index held by each lane
@@ -433,10 +431,8 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
     unsigned int aw0 = 0u, aw1 = 0u;
     bool has0 = false, has1 = false;
     bool outside = false;     // forced yield: a particle given outside [0, L)
-    [[maybe_unused]] uint32_t wacc[P];   // FUSED: every slot's second word
 #pragma unroll
     for (int p = 0; p < P; ++p) {
-        wacc[p] = 0u;
         int i = lane_particle<G, P, PAD>(m, gl, p);
         double zp;
         if constexpr (FUSED) {
@@ -462,9 +458,7 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
                 uint32_t w0, w1;
                 vmc_move_block(a.seed, slot, step, li, w0, w1);
                 d = vmc_move_unit(w0) * a.move_spread;
-                if constexpr (FUSED) {
-                    wacc[p] = w1;
-                } else {
+                if constexpr (!FUSED) {
                     if (li == 0u) { aw0 = w1; has0 = true; }
                     if (li == 1u || n == 1) { aw1 = w1; has1 = true; }
                 }
@@ -478,12 +472,6 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
         // it until the first accepted move.
         zn[p] = wrap_box(zp + d, m.L);
         if (forced) outside = outside || zn[p] != zp;
-    }
-    if constexpr (FUSED) {
-        // the accept words straight from the lanes that hold particles 0 and
-        // 1 (known since the last accepted move: no ballots)
-        aw0 = vmc_read_slot<P>(wacc, src0);
-        aw1 = vmc_read_slot<P>(wacc, src1);
     }
     QMC_SECTION("resort");
     // (one odd-even pass every RESORT_EVERY steps keeps the lanes sorted
@@ -561,7 +549,7 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
     }
     QMC_SECTION("metropolis+store");
     if (FUSED) {
-        ua = u53(aw0, aw1);
+        // (the draw of this yield is in `thr`)
     } else if (!forced) {
         if (!LEAN && a.tape) {
             ua = a.tape[(wr * a.tape_steps + a.tape_idx) * (n + 1) + n];
@@ -603,8 +591,9 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
         // lane 0's log|psi| -- the lane whose decision the per-yield kernel
         // takes -- as a scalar: the test and its branch are scalar
         const double w0 = qmc_uniform_f64(wf_new);
-        acc = ua <= 0.0 || w0 > wf_cur;
-        if (!acc) acc = w0 > 0.5 * log_pos(ua) + wf_cur;
+        const double h = qmc_lane_f64(thr, (int)(s & 63u));
+        acc = h != h || w0 > wf_cur;
+        if (!acc) acc = w0 > h + wf_cur;
         acc = __builtin_amdgcn_readfirstlane((int)acc) != 0;
     } else {
         acc = forced || ua <= 0.0 || wf_new > wf_cur;
@@ -644,7 +633,6 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
                 zc[p] = zn[p];
                 labc[p] = labn[p];
             }
-            vmc_accept_lanes<P>(labc, n, src0, src1);
             any_acc = true;
         } else {
 #pragma unroll
