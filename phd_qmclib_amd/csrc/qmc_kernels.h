@@ -470,7 +470,16 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
         // the image inside the box (and the one-body factor the position as
         // given, below).  The stored configuration stays as the caller gave
         // it until the first accepted move.
-        zn[p] = wrap_box(zp + d, m.L);
+        // (the sum as the reference forms it, from the rounded product: where
+        // d is always the product -- STEADY, no padding -- the compiler fused
+        // the two into an fma and the production block left the series
+        // kernels' positions by an ulp)
+        double zs;
+        {
+#pragma clang fp contract(off)
+            zs = zp + d;
+        }
+        zn[p] = wrap_box(zs, m.L);
         if (forced) outside = outside || zn[p] != zp;
     }
     QMC_SECTION("resort");

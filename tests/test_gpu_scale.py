@@ -281,11 +281,27 @@ def test_large_shapes_trajectories_vs_oracle(oracle, n):
 @pytest.mark.parametrize('n', [37, 48, 64, 66, 100, 101, 128, 300, 512])
 def test_long_trajectories_across_the_box_boundary(oracle, n):
     """Lane order is kept ascending with the place where positions wrap from L
-    to 0 anchored at the end of the row (`anchor_seam`, `anchor_seam_rows`):
-    whenever a particle crosses the box boundary the whole row moves by one
-    slot.  Long chains with wide moves cross it many times; positions (handed
-    back in particle order through the labels), log|psi| and the carried energy
-    must still be the oracle's on the same Philox streams."""
+    to 0 anchored at the end of the row: whenever a particle crosses the box
+    boundary the whole row moves by one slot.  Long chains with wide moves
+    cross it many times; positions (handed back in particle order through the
+    labels), log|psi| and the carried energy must still be the oracle's on the
+    same Philox streams.
+
+    Which code keeps the order at this cutoff (L / 4, pairs classified from
+    the sines), by size:
+      37, 48, 64    (64, 1): `sort_lanes64` -- odd-even passes until the lanes
+                    ascend, `anchor_seam` as its first move when the inversion
+                    sits at an end of the row -- then the sorted-row pair sum;
+      66, 100, 128  (64, 2): `sort_rows128`, with `anchor_seam_rows<2>` in the
+                    same role;
+      101           (64, 2), odd N: no sorted rows exist, nothing reorders the
+                    row and the general pair sum takes it in any order;
+      300, 512      (64, 8): the `anchor_seam_rows` + `resort_linear_rows`
+                    branch of `vmc_step_kernel` itself.
+    The `anchor_seam` + `resort_linear<64>` branch of the stepping kernels and
+    their `anchor_seam_rows` branch at (64, 2) are compiled only for models
+    that classify pairs from the positions (cutoff above 0.45 L): they are
+    pinned by tests/test_gpu_zclass_steps.py."""
     from phd_qmclib_amd.engine import ModelEngine, VmcEnsemble
     from ._traj import explain_flips
     spec = box(n)
