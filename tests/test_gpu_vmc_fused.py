@@ -4,7 +4,10 @@ LEAN blocks of several yields against the series kernel of the same stream
 (one launch per yield) and against blocks of one yield each, right after
 set_state and later; positions, labels (through the positions handed back in
 particle order), log|psi|, carried energy, block sums and accept counts; the
-general-path counter; and a DMC ensemble built from a fused block."""
+general-path counter; and a DMC ensemble built from a fused block.  The move
+spread here is exactly 0.125 (a quarter of the well width), at which the
+product vmc_move_unit * move_spread is exact; the spreads at which it rounds
+are in tests/test_gpu_generic_steps.py."""
 from math import pi
 
 import numpy as np

@@ -5,7 +5,10 @@ against the series kernel of the same stream, which draws and tests yield by
 yield -- bit for bit: positions, log|psi|, carried energy, the three block sums
 and the general-path counter.  Blocks long enough to refill the thresholds,
 chains that leave and re-enter the sorted-row path inside a launch, models
-whose pair sums or one-body factor take other branches, and the padded shape."""
+whose pair sums or one-body factor take other branches, and the padded shape.
+The move spread here is exactly 0.125 (a quarter of the well width), at which
+the product vmc_move_unit * move_spread is exact; the spreads at which it
+rounds are in tests/test_gpu_generic_steps.py."""
 from math import pi
 
 import numpy as np

@@ -45,6 +45,10 @@ fused z + d into an fma (fixed in `vmc_step_kernel`; invisible at the
 move_spread 0.125 of the rest of the suite, where the product is exact).  The
 last test pins the same kernels of the sine classifier at N = 16, 32.
 
+The start rows, the oracle's chains and populations and the once-per-walker
+condition of the sorted rows are shared with tests/test_gpu_generic_steps.py
+(the sine classifier on generic models): tests/_steps.py.
+
 Every precondition (classifier-edge distances, box crossings, branching
 margins) is asserted from the oracle / numpy before the device is compared.
 Every test prints its worst deviation as a fraction of its tolerance (`-s`);
@@ -55,14 +59,16 @@ from math import pi
 import numpy as np
 import pytest
 
+from ._steps import (DMC_DT, DMC_KAPPA, DMC_MAXW, DMC_STEPS, DMC_W, EDGE_EPS,
+                     VMC_SPREAD, VMC_W, VMC_YIELDS, dmc_start,
+                     oracle_dmc_run, oracle_vmc_chains, report, six_rows,
+                     start_rows, takes_sorted_rows)
 from ._traj import explain_flips
 from .test_gpu_parity import close, worst
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 2e-11                    # the suite's double-path tolerance
-STREAM_DMC_BRANCH = 2           # oracle/qmc_oracle.h: ORC_STREAM_DMC_BRANCH
-EDGE_EPS = 1e-6                 # straddling partners: this far from an edge, of L
 EDGE_MIN = 1e-9                 # no pair closer to an edge of the classifier, of L
 
 SIZES = (9, 16, 24, 32, 37, 64, 66, 101, 128, 130, 256, 300, 512)
@@ -96,9 +102,6 @@ DMC_SEEDS = dict({cid: 1 for cid in IDS}, **{
     'box128-c0.47': 2, 'box300-c0.47': 3, 'box512-c0.47': 3,
     'box128-c0.4501': 2, 'box300-c0.4501': 3,
     'box128-c0.4999': 2, 'box300-c0.4999': 3, 'box300-c0.5': 3})
-
-VMC_W, VMC_YIELDS, VMC_SPREAD = 6, 24, 0.6
-DMC_W, DMC_MAXW, DMC_DT, DMC_KAPPA, DMC_STEPS = 12, 16, 5e-4, 0.5, 8
 
 
 def make_spec(golden_params, kind, n, L, cutoff):
@@ -155,60 +158,6 @@ def models(oracle, golden_params):
 # configurations
 # ---------------------------------------------------------------------------
 
-def jittered_lattice(rng, n, L):
-    """A lattice of spacing L / n, every particle displaced by up to 0.3
-    spacings: particles spread like an equilibrated walker."""
-    return (np.arange(n) + 0.5 + 0.6 * (rng.random_sample(n) - 0.5)) * (L / n)
-
-
-def straddling_row(rng, n, L, rm):
-    """A uniform random row in which chosen particles have partners EDGE_EPS L
-    on either side of every edge of the classifier.  Particle 0 at 0.0211 L
-    with partners at z0 + s, s = rm -+ eps, (L - rm) -+ eps, L / 2 -+ eps:
-    the device sees |z_a - z_b| = s, on the ring the partners at (L - rm) -+
-    eps are the ones rm +- eps away on the other side of the particle.  Where
-    the row has room (N >= 14) a second particle at 0.9637 L has the mirrored
-    partners z1 - s, so both signs of z_a - z_b meet every edge."""
-    eps = EDGE_EPS * L
-    seps = [s + e for s in (rm, L - rm, 0.5 * L) for e in (-eps, eps)]
-    row = L * rng.random_sample(n)
-    z0, z1 = 0.0211 * L, 0.9637 * L
-    row[:7] = [z0] + [z0 + s for s in seps]
-    if n >= 14:
-        row[7:14] = [z1] + [z1 - s for s in seps]
-    assert np.all((row >= 0.0) & (row < L))
-    return row
-
-
-def six_rows(n, L, rm, seed):
-    """The rows of part 1: two uniform random rows, one sorted row, one
-    jittered lattice, permuted, one row with four particles within 1e-3 of 0
-    and of L (on a jittered lattice), one row with pairs straddling the
-    classifier's edges.  At rm = L / 2 exactly the edges coincide (the
-    straddling partners would sit on top of each other): five rows."""
-    rng = np.random.RandomState(seed)
-    rows = [L * rng.random_sample(n), L * rng.random_sample(n),
-            np.sort(L * rng.random_sample(n)),
-            rng.permutation(jittered_lattice(rng, n, L))]
-    seam = jittered_lattice(rng, n, L)
-    u = 1e-3 * (0.05 + 0.95 * rng.random_sample(4))
-    seam[:2], seam[-2:] = u[:2], L - u[2:]
-    rows.append(seam)
-    if rm != 0.5 * L:
-        rows.append(straddling_row(rng, n, L, rm))
-    return np.array(rows)
-
-
-def start_rows(n, L, rm, seed):
-    """Six start rows of the trajectories: the rows of part 1 (at rm = L / 2
-    a third uniform random row takes the place of the straddling one)."""
-    rows = six_rows(n, L, rm, seed)
-    if len(rows) < 6:
-        rng = np.random.RandomState(seed + 1)
-        rows = np.concatenate([rows, L * rng.random_sample((1, n))])
-    return rows
-
-
 def edge_distance(pos, L, rm):
     """The smallest distance of any |z_a - z_b| of any row from the edges rm
     and L - rm of the position classifier, and the number of pairs closer
@@ -244,13 +193,6 @@ def deviation(got, ref, scale):
     ref2 = ref.reshape(ref.shape[0], -1)
     got2 = np.asarray(got, dtype=np.float64).reshape(ref2.shape)
     return float((np.abs(got2 - ref2).max(1) / scale).max())
-
-
-def report(part, cid, figures):
-    """One line per test: worst deviations as fractions of their tolerance."""
-    print(f'zclass {part} {cid}: ' + ', '.join(
-        f'{k} {v:.1e}' if isinstance(v, float) else f'{k} {v}'
-        for k, v in figures.items()))
 
 
 def vmc_first_yield(eng, pos, series):
@@ -365,29 +307,6 @@ def test_single_evaluations_vs_oracle(models, oracle, case):
 # 2. VMC real steps
 # ---------------------------------------------------------------------------
 
-def oracle_vmc_chains(oracle, m, pos0, spread, seed, nyield):
-    """The oracle's chains, yield by yield -> (move_stat, energy, log|psi|
-    [nyield, W], final positions mod L [W, N], crossings of the box boundary
-    counted as in test_long_trajectories_across_the_box_boundary)."""
-    W, n = pos0.shape
-    L = float(m.supercell_size)
-    st_o = np.zeros((nyield, W), dtype=bool)
-    en_o, wf_o = np.zeros((nyield, W)), np.zeros((nyield, W))
-    pos_o = np.zeros((W, n))
-    crossings = 0
-    for c in range(W):
-        ch = oracle.VmcChain(m, pos0[c], spread, seed=seed, chain=c)
-        prev = np.mod(pos0[c], L)
-        for t in range(nyield):
-            wf, en, st, _ = ch.run(1)
-            st_o[t, c], en_o[t, c], wf_o[t, c] = bool(st[0]), en[0], wf[0]
-            cur = np.mod(ch.pos, L)
-            crossings += int((np.abs(cur - prev) > 0.5 * L).sum())
-            prev = cur
-        pos_o[c] = np.mod(ch.pos, L)
-    return st_o, en_o, wf_o, pos_o, crossings
-
-
 @pytest.mark.parametrize('case', CASES, ids=IDS)
 def test_vmc_real_steps_follow_the_oracle(models, oracle, case):
     """6 chains, 24 yields with move_spread 0.6 from the rows of part 1:
@@ -440,51 +359,6 @@ def test_vmc_real_steps_follow_the_oracle(models, oracle, case):
 # 3. DMC real steps
 # ---------------------------------------------------------------------------
 
-def dmc_start(n, L, rm, seed):
-    """12 walkers: the six start rows twice; in two walkers of the second
-    half two particles sit within 5e-3 of 0 and of L (sqrt(2 dt) = 0.03: they
-    cross the seam)."""
-    pos = np.tile(start_rows(n, L, rm, seed), (2, 1))
-    pos[6, :2] = [2e-3, L - 1.5e-3]
-    pos[7, :2] = [L - 3e-3, 4e-3]
-    return pos
-
-
-def oracle_prev_weights(orc):
-    """The weights the oracle's next branching step reads."""
-    maxw = orc.cfg.max_num_walkers
-    w = np.ctypeslib.as_array(orc.st.prev_weight, shape=(maxw,))
-    return w[:orc.st.prev_num_walkers].copy()
-
-
-def oracle_dmc_run(oracle, m, pos0, seed):
-    """The oracle's population over DMC_STEPS steps -> (orc, yields, smallest
-    distance of a branching w + u from an integer, particles that crossed the
-    box boundary).  Asserts that the clone counts rebuilt from the weights
-    and the Philox draws ARE the oracle's populations, below the cap."""
-    L = float(m.supercell_size)
-    orc = oracle.DmcEnsemble(m, pos0, DMC_DT, DMC_MAXW, DMC_W, DMC_KAPPA,
-                             seed=seed)
-    ys, margin, crossed = [], 1.0, 0
-    prev = np.mod(pos0, L)
-    for t in range(DMC_STEPS):
-        w = oracle_prev_weights(orc)
-        u = np.array([oracle.philox_uniform2(seed, s, t, 0,
-                                             STREAM_DMC_BRANCH)[0]
-                      for s in range(len(w))])
-        x = w + u
-        margin = min(margin, float(np.abs(x - np.round(x)).min()))
-        y = orc.step()
-        nw = int(y.num_walkers)
-        assert int(np.floor(x).sum()) == nw < DMC_MAXW, t
-        cur = np.mod(orc.confs[:nw, 0], L)
-        crossed += int((np.abs(cur - prev[orc.cloning_ref[:nw]]) >
-                        0.5 * L).sum())
-        prev = cur
-        ys.append((nw, float(y.energy), float(y.ref_energy)))
-    return orc, ys, margin, crossed
-
-
 @pytest.mark.parametrize('case', CASES, ids=IDS)
 def test_dmc_real_steps_follow_the_oracle(models, oracle, case):
     """12 walkers (max 16), time_step 5e-4, 8 steps: population exact and
@@ -532,23 +406,6 @@ def test_dmc_real_steps_follow_the_oracle(models, oracle, case):
 # ---------------------------------------------------------------------------
 # 4. either side of the switch
 # ---------------------------------------------------------------------------
-
-def takes_sorted_rows(row, n, L, rm):
-    """The once-per-walker condition of the sorted-row pair sums
-    (`far_partner_ok64`, `far_partner_ok128`): on the ascending row the
-    partner of the last rotation step (32 lanes away) is closer than L - rm
-    for every lane.  A row that fails it is evaluated by the general pair sum
-    inside the same kernel, and counted."""
-    z = np.sort(row)
-    gl = np.arange(64)
-    if n == 64:
-        d = z - z[gl ^ 32]
-    else:
-        assert n == 128
-        d = z[2 * gl + 1] - z[2 * (gl ^ 32)]
-    d[:32] += L
-    return bool(np.all(d < L - rm))
-
 
 @pytest.mark.parametrize('n', [64, 128])
 def test_either_side_of_the_switch(oracle, golden_params, n):
