@@ -64,10 +64,5 @@ __global__ void __launch_bounds__(BLOCK) dmc_cm_diffusion_kernel(EstArgs a)
         red[wave][0] = sum_y;
         red[wave][1] = sum_y2;
     }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        double t = 0.0;
-        for (int w = 0; w < NWAVE; ++w) t += red[w][threadIdx.x];
-        a.partial[(size_t)blockIdx.x * 2 + threadIdx.x] = t;
-    }
+    est_block_sum(&red[0][0], 2, 2, a.partial);
 }

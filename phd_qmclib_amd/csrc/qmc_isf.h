@@ -30,31 +30,29 @@
 //
 // One wavefront per walker slot, grid-striding over the live slots.  At a step
 // that measures (t = 0, or t = l q with l < T; uniform over the launch) the
-// wavefront forms rho_m of its walker as the S(k) kernel does for up to 64
-// modes: m = 8 a + b, exp(i m t_i) = F_a(i) E_b(i), the two factor tables of a
-// chunk of 32 particles in LDS (ssf_fill_table<8>: one sincos_halfpi and seven
-// rotations per particle and table) and one v_mfma_f64_16x16x4_f64 per four
-// particles for the 16 x 16 tile (Re | Im of F) x (Re | Im of E); any N, in
-// chunks.  Lane m then holds rho_m and hands it to the others through LDS.
-// At any other step no rho is formed.  Lanes take the row indices
-// lane + 64 j for the coalesced copy aux_prev[par] -> aux_act[s], replace the
-// measured column on the way and keep per-lane running sums; the wavefronts of
-// a block add up in index order into partial[block][K C], est_reduce_kernel
-// sums the blocks.  fp64 whatever fast_math says; no atomics.
+// wavefront forms rho_m of its walker with the routine of the S(k) kernel for
+// up to 64 modes (qmc_kernels_misc.h: rho_modes8, the factor tables, the
+// matrix-core tile and its lane map are described there); any N.  Lane m then
+// holds rho_m and hands it to the others through LDS.  At any other step no
+// rho is formed.  Lanes take the row indices lane + 64 j for the coalesced
+// copy aux_prev[par] -> aux_act[s], replace the measured column on the way and
+// keep per-lane running sums; est_block_sum adds up the wavefronts of a block
+// into partial[block][K C], est_reduce_kernel sums the blocks.  fp64 whatever
+// fast_math says; no atomics.
 static constexpr int ISF_MAXROW = 1024;          // K (T + 2) at most
 static constexpr int ISF_NJ = ISF_MAXROW / 64;   // row indices per lane
 
 __global__ void __launch_bounds__(BLOCK) dmc_isf_kernel(EstArgs a)
 {
     using S = SsfShape<8>;
-    constexpr int NWAVE = BLOCK / 64, CH = S::CH, RS = S::RS;
+    constexpr int NWAVE = BLOCK / 64;
     static_assert(NWAVE * S::WAVE_DOUBLES >= NWAVE * ISF_MAXROW,
                   "the block reduction reuses the tables' LDS");
     __shared__ double smem[NWAVE * S::WAVE_DOUBLES];
     __shared__ double rho[NWAVE][2][64];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     double *X = smem + (size_t)wave * S::WAVE_DOUBLES;   // F_a (rows of D)
-    double *Y = X + S::ROWS * RS;                        // E_b (columns of D)
+    double *Y = X + S::ROWS * S::RS;                     // E_b (columns of D)
     const int n = a.n;
     const int T = (int)a.pfw, C = T + 2, A = a.K * C;
     const long long t = a.step_idx;
@@ -64,7 +62,6 @@ __global__ void __launch_bounds__(BLOCK) dmc_isf_kernel(EstArgs a)
     const int col = first ? 0 : (int)lag;       // the column measured now
     const long long nw = a.ctl->nw;
     const long long wstride = (long long)gridDim.x * NWAVE;
-    const int quad = lane >> 4, idx = lane & 15;
     // what this lane does to row index lane + 64 j at a measuring step:
     // 4 m + kind, kind 0 copy, 1 the measured column, 2 / 3 the origin (t = 0)
     int sel[ISF_NJ];
@@ -86,42 +83,10 @@ __global__ void __launch_bounds__(BLOCK) dmc_isf_kernel(EstArgs a)
          s += wstride) {
         const long long par = a.ref[s];
         if (measure) {
-            v4d D = {0, 0, 0, 0};
-            for (int c0 = 0; c0 < n; c0 += CH) {
-                {
-                    // lanes 0..31 build E of particle `lane`, lanes 32..63
-                    // build F of particle `lane - 32`
-                    const int pl = lane & 31;
-                    const int i = c0 + pl;
-                    const bool valid = i < n;
-                    const double u = a.scale * (valid ? a.ppos[par * n + i] : 0.0);
-                    ssf_fill_table<8>(lane < 32 ? Y : X, pl,
-                                      lane < 32 ? u : 8.0 * u, valid);
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                const int left = n - c0;
-                const int ngroups = (left >= CH ? CH : left + 3) / 4;
-                for (int g = 0; g < ngroups; ++g) {
-                    const int pc = 4 * g + quad;        // particle of this k
-                    const double xa = X[idx * RS + pc];
-                    const double yb = Y[idx * RS + pc];
-                    D = __builtin_amdgcn_mfma_f64_16x16x4f64(xa, yb, D, 0, 0, 0);
-                }
-                __builtin_amdgcn_wave_barrier();    // tables are rewritten next
-            }
-            // the tile holds the four quadrants RR | RI / IR | II; element
-            // (row, col) sits in lane (col, row & 3), register row >> 2
-            double *Dl = X;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Dl[(quad + 4 * r) * 16 + idx] = D[r];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const int fa = lane >> 3, eb = lane & 7;    // mode `lane`
-            rho[wave][0][lane] = Dl[fa * 16 + eb] - Dl[(8 + fa) * 16 + 8 + eb];
-            rho[wave][1][lane] = Dl[fa * 16 + 8 + eb] + Dl[(8 + fa) * 16 + eb];
+            double re, im;                  // rho of mode `lane`
+            rho_modes8(a.ppos + par * n, n, a.scale, X, Y, lane, re, im);
+            rho[wave][0][lane] = re;
+            rho[wave][1][lane] = im;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -146,19 +111,12 @@ __global__ void __launch_bounds__(BLOCK) dmc_isf_kernel(EstArgs a)
                 acc[j] += v;
             }
         }
-        __builtin_amdgcn_wave_barrier();    // rho and the tables are rewritten
+        __builtin_amdgcn_wave_barrier();    // rho is rewritten next
     }
-    // fixed-order block reduction: waves 0..3 (the tables' LDS is reused),
-    // then the reduce kernel sums the blocks in index order
-    __syncthreads();
+    __syncthreads();                       // the tables' LDS is reused
     double *red = smem;                    // [NWAVE][ISF_MAXROW]
 #pragma unroll
     for (int j = 0; j < ISF_NJ; ++j)
         red[wave * ISF_MAXROW + lane + 64 * j] = acc[j];
-    __syncthreads();
-    for (int i = threadIdx.x; i < A; i += BLOCK) {
-        double r = 0.0;
-        for (int w = 0; w < NWAVE; ++w) r += red[w * ISF_MAXROW + i];
-        a.partial[(size_t)blockIdx.x * A + i] = r;
-    }
+    est_block_sum(red, ISF_MAXROW, A, a.partial);
 }

@@ -304,11 +304,38 @@ struct EstArgs {
                               // g2(r), centre-of-mass diffusion: supercell
                               // size L
     double scale2;            // g2(r): 1 / delta = num_bins / (L / 2)
+    // Forward walking (S(k), density, g2(r)): a pure estimator adds the
+    // current step to the rows while step_idx < pfw and only transports them
+    // afterwards; its per-step sum is over min(step_idx + 1, pfw) steps.
+    __host__ __device__ bool counts_now() const
+    {
+        return !pure || step_idx < pfw;
+    }
+    double divisor() const      // (of the host's reduction launch)
+    {
+        return pure ? (double)(counts_now() ? step_idx + 1 : pfw) : 1.0;
+    }
 };
 
 static constexpr int EST_BLOCKS = 1024;
 static constexpr int EST_MAXK = 256;        // modes / bins supported per call
 static constexpr int EST_CH = EST_MAXK / 64;
+
+// The end of every estimator kernel: red[wave][stride] holds the running sums
+// of the block's wavefronts; they add up in index order into
+// partial[block][width], then est_reduce_kernel sums the blocks in index order.
+// (A kernel that reuses other LDS for `red` has its own barrier in front of
+// the reuse.)
+__device__ __forceinline__ void est_block_sum(const double *red, int stride,
+                                              int width, double *partial)
+{
+    __syncthreads();
+    for (int i = threadIdx.x; i < width; i += BLOCK) {
+        double t = 0.0;
+        for (int w = 0; w < BLOCK / 64; ++w) t += red[w * stride + i];
+        partial[(size_t)blockIdx.x * width + i] = t;
+    }
+}
 
 // Static structure factor parts of every yielded walker:
 // rho_m = sum_i exp(i k_m z_i), k_m = 2 pi m / L, parts (|rho_m|^2, Re, Im);
@@ -358,6 +385,59 @@ __device__ __forceinline__ void ssf_fill_table(double *T, int col, double u,
     }
 }
 
+// rho_m = sum_{i < n} exp(i (pi/2) m scale row[i]) for the 64 modes m = 8 a + b
+// of the packed tiling (KD = 8), formed by one wavefront with its tables X
+// (F_a) and Y (E_b); lane m gets rho_m in (re, im).  Chunks of 32 particles:
+// lanes 0..31 build E of particle `lane`, lanes 32..63 build F of particle
+// `lane - 32`, then one MFMA per four particles adds to the 16 x 16 tile
+// (Re | Im of F) x (Re | Im of E).  The tile holds the four quadrants
+// RR | RI / IR | II; element (row, col) sits in lane (col, row & 3), register
+// row >> 2 (f64 MFMA C/D map: col = lane & 15, row = (lane >> 4) + 4 reg).  It
+// goes through the LDS of X to hand lane m = 8 fa + eb its four entries.  The
+// tables belong to the wavefront alone, so wave-level fences order them; the
+// wave barriers at the ends keep a table from being rewritten while read.
+__device__ __forceinline__ void rho_modes8(const double *row, int n,
+                                           double scale, double *X, double *Y,
+                                           int lane, double &re, double &im)
+{
+    using S = SsfShape<8>;
+    constexpr int CH = S::CH, RS = S::RS;
+    const int quad = lane >> 4, idx = lane & 15;
+    v4d D = {0, 0, 0, 0};
+    for (int c0 = 0; c0 < n; c0 += CH) {
+        {
+            const int pl = lane & 31;
+            const int i = c0 + pl;
+            const bool valid = i < n;
+            const double u = scale * (valid ? row[i] : 0.0);
+            ssf_fill_table<8>(lane < 32 ? Y : X, pl, lane < 32 ? u : 8.0 * u,
+                              valid);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const int left = n - c0;
+        const int ngroups = (left >= CH ? CH : left + 3) / 4;
+        for (int g = 0; g < ngroups; ++g) {
+            const int col = 4 * g + quad;           // particle of this k
+            const double xa = X[idx * RS + col];
+            const double yb = Y[idx * RS + col];
+            D = __builtin_amdgcn_mfma_f64_16x16x4f64(xa, yb, D, 0, 0, 0);
+        }
+        __builtin_amdgcn_wave_barrier();    // tables are rewritten next
+    }
+    double *Dl = X;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Dl[(quad + 4 * r) * 16 + idx] = D[r];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int fa = lane >> 3, eb = lane & 7;
+    re = Dl[fa * 16 + eb] - Dl[(8 + fa) * 16 + 8 + eb];
+    im = Dl[fa * 16 + 8 + eb] + Dl[(8 + fa) * 16 + eb];
+    __builtin_amdgcn_wave_barrier();        // X is rewritten next
+}
+
 template <int KD>
 __global__ void __launch_bounds__(BLOCK) dmc_ssf_mfma_kernel(EstArgs a)
 {
@@ -380,14 +460,18 @@ __global__ void __launch_bounds__(BLOCK) dmc_ssf_mfma_kernel(EstArgs a)
     double acc[NM][3];
 #pragma unroll
     for (int r = 0; r < NM; ++r) acc[r][0] = acc[r][1] = acc[r][2] = 0.0;
-    const bool accumulate = !a.pure || a.step_idx < a.pfw;
+    const bool accumulate = a.counts_now();
     for (long long s = (long long)blockIdx.x * (BLOCK / 64) + wave; s < nw;
          s += wstride) {
         const long long par = a.ref ? a.ref[s] : s;
         double re[NM], im[NM];
 #pragma unroll
         for (int r = 0; r < NM; ++r) re[r] = im[r] = 0.0;
-        if (accumulate) {
+        if constexpr (KD == 8) {
+            if (accumulate)
+                rho_modes8(a.ppos + par * a.n, a.n, a.scale, X, Y, lane, re[0],
+                           im[0]);
+        } else if (accumulate) {
             v4d Drr = {0, 0, 0, 0}, Dri = {0, 0, 0, 0}, Dir = {0, 0, 0, 0},
                 Dii = {0, 0, 0, 0};
             for (int c0 = 0; c0 < a.n; c0 += CH) {
@@ -408,45 +492,23 @@ __global__ void __launch_bounds__(BLOCK) dmc_ssf_mfma_kernel(EstArgs a)
                 const int ngroups = (left >= CH ? CH : left + 3) / 4;
                 for (int g = 0; g < ngroups; ++g) {
                     const int col = 4 * g + quad;       // particle of this k
-                    if (KD == 8) {
-                        const double xa = X[idx * RS + col];
-                        const double yb = Y[idx * RS + col];
-                        Drr = __builtin_amdgcn_mfma_f64_16x16x4f64(xa, yb, Drr,
-                                                                   0, 0, 0);
-                    } else {
-                        const double xr = X[idx * RS + col];
-                        const double xi = X[(KD + idx) * RS + col];
-                        const double yr = Y[idx * RS + col];
-                        const double yi = Y[(KD + idx) * RS + col];
-                        Drr = __builtin_amdgcn_mfma_f64_16x16x4f64(xr, yr, Drr, 0, 0, 0);
-                        Dri = __builtin_amdgcn_mfma_f64_16x16x4f64(xr, yi, Dri, 0, 0, 0);
-                        Dir = __builtin_amdgcn_mfma_f64_16x16x4f64(xi, yr, Dir, 0, 0, 0);
-                        Dii = __builtin_amdgcn_mfma_f64_16x16x4f64(xi, yi, Dii, 0, 0, 0);
-                    }
+                    const double xr = X[idx * RS + col];
+                    const double xi = X[(KD + idx) * RS + col];
+                    const double yr = Y[idx * RS + col];
+                    const double yi = Y[(KD + idx) * RS + col];
+                    Drr = __builtin_amdgcn_mfma_f64_16x16x4f64(xr, yr, Drr, 0, 0, 0);
+                    Dri = __builtin_amdgcn_mfma_f64_16x16x4f64(xr, yi, Dri, 0, 0, 0);
+                    Dir = __builtin_amdgcn_mfma_f64_16x16x4f64(xi, yr, Dir, 0, 0, 0);
+                    Dii = __builtin_amdgcn_mfma_f64_16x16x4f64(xi, yi, Dii, 0, 0, 0);
                 }
                 __builtin_amdgcn_wave_barrier();    // tables are rewritten next
             }
-            if (KD == 8) {
-                // one tile holds the four quadrants RR | RI / IR | II; element
-                // (row, col) sits in lane (col, row & 3), register row >> 2
-                // (f64 MFMA C/D map: col = lane & 15, row = (lane >> 4) + 4 reg)
-                double *Dl = X;
+            // (four tiles, f64 MFMA C/D map as in rho_modes8: register r of
+            // this lane is the mode mo[r])
 #pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    Dl[(quad + 4 * r) * 16 + idx] = Drr[r];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                const int fa = lane >> 3, eb = lane & 7;
-                re[0] = Dl[fa * 16 + eb] - Dl[(8 + fa) * 16 + 8 + eb];
-                im[0] = Dl[fa * 16 + 8 + eb] + Dl[(8 + fa) * 16 + eb];
-                __builtin_amdgcn_wave_barrier();
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    re[r] = Drr[r] - Dii[r];
-                    im[r] = Dri[r] + Dir[r];
-                }
+            for (int r = 0; r < 4; ++r) {
+                re[r] = Drr[r] - Dii[r];
+                im[r] = Dri[r] + Dir[r];
             }
         }
 #pragma unroll
@@ -467,9 +529,7 @@ __global__ void __launch_bounds__(BLOCK) dmc_ssf_mfma_kernel(EstArgs a)
             acc[r][0] += v0; acc[r][1] += v1; acc[r][2] += v2;
         }
     }
-    // fixed-order block reduction: waves 0..3 (the tables' LDS is reused),
-    // then the reduce kernel sums the blocks in index order
-    __syncthreads();
+    __syncthreads();                       // the tables' LDS is reused
     double *red = smem;                    // [BLOCK/64][K][3]
 #pragma unroll
     for (int r = 0; r < NM; ++r)
@@ -477,12 +537,7 @@ __global__ void __launch_bounds__(BLOCK) dmc_ssf_mfma_kernel(EstArgs a)
             double *q = red + ((size_t)wave * a.K + mo[r]) * 3;
             q[0] = acc[r][0]; q[1] = acc[r][1]; q[2] = acc[r][2];
         }
-    __syncthreads();
-    for (int i = threadIdx.x; i < a.K * 3; i += BLOCK) {
-        double t = 0.0;
-        for (int w = 0; w < BLOCK / 64; ++w) t += red[(size_t)w * a.K * 3 + i];
-        a.partial[(size_t)blockIdx.x * a.K * 3 + i] = t;
-    }
+    est_block_sum(red, a.K * 3, a.K * 3, a.partial);
 }
 
 // Density histogram of every slot, lane = bin.  Reproduces the reference:
@@ -500,7 +555,7 @@ __global__ void __launch_bounds__(BLOCK) dmc_density_kernel(EstArgs a)
     double acc[EST_CH];
 #pragma unroll
     for (int c = 0; c < EST_CH; ++c) acc[c] = 0.0;
-    const bool count_now = !a.pure || a.step_idx < a.pfw;
+    const bool count_now = a.counts_now();
     for (long long s = (long long)blockIdx.x * (BLOCK / 64) + wave; s < a.maxw;
          s += wstride) {
         const bool live = s < nw;
@@ -534,12 +589,7 @@ __global__ void __launch_bounds__(BLOCK) dmc_density_kernel(EstArgs a)
     }
 #pragma unroll
     for (int c = 0; c < EST_CH; ++c) red[wave][c * 64 + lane] = acc[c];
-    __syncthreads();
-    for (int b = threadIdx.x; b < a.K; b += BLOCK) {
-        double t = 0.0;
-        for (int w = 0; w < BLOCK / 64; ++w) t += red[w][b];
-        a.partial[(size_t)blockIdx.x * a.K + b] = t;
-    }
+    est_block_sum(&red[0][0], EST_MAXK, a.K, a.partial);
 }
 
 // iter[step][k][c] = (sum over blocks) / divisor.  Fixed summation order:

@@ -166,7 +166,7 @@ __global__ void __launch_bounds__(BLOCK) dmc_pair_dist_kernel(EstArgs a)
     double acc[EST_CH];
 #pragma unroll
     for (int c = 0; c < EST_CH; ++c) acc[c] = 0.0;
-    const bool count_now = !a.pure || a.step_idx < a.pfw;
+    const bool count_now = a.counts_now();
     const int npass = (n + 63) / 64;
     const int kfull = (n - 1) / 2;              // offsets every particle takes
     for (long long s = (long long)blockIdx.x * NWAVE + wave; s < nw;
@@ -219,16 +219,9 @@ __global__ void __launch_bounds__(BLOCK) dmc_pair_dist_kernel(EstArgs a)
         }
         __builtin_amdgcn_wave_barrier();    // z and h are rewritten next
     }
-    // fixed-order block reduction (the position rows are free now), then
-    // est_reduce_kernel sums the blocks in index order
-    __syncthreads();
+    __syncthreads();                            // the position rows are free now
     double *red = &zs[0][0];                    // [NWAVE][EST_MAXK]
 #pragma unroll
     for (int c = 0; c < EST_CH; ++c) red[wave * EST_MAXK + c * 64 + lane] = acc[c];
-    __syncthreads();
-    for (int b = threadIdx.x; b < B; b += BLOCK) {
-        double t = 0.0;
-        for (int w = 0; w < NWAVE; ++w) t += red[w * EST_MAXK + b];
-        a.partial[(size_t)blockIdx.x * B + b] = t;
-    }
+    est_block_sum(red, EST_MAXK, B, a.partial);
 }

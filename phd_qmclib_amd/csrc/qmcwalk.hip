@@ -1750,11 +1750,13 @@ extern "C" int qmc_vmc_run_block(qmc_vmc *v, int64_t nyield, double *sum_e,
 }
 
 // ----------------------------------------------------------------- DMC ----
-// What a setter asks of a slot; `aux`: keep per-walker rows.
+// What a setter asks of a slot: K modes or bins (0: off) of C doubles each;
+// `aux`: keep per-walker rows, of A doubles (0: as the output, K * C).
 struct DmcEstSpec {
-    int K, pure;
+    int K, C, pure;
     long long pfw;
     bool aux;
+    int A = 0;
     int stride = 1;              // (F(k, tau) only)
 };
 
@@ -1777,7 +1779,7 @@ struct DmcEstSlot {
         aux[0].release();
         aux[1].release();
         iter.release();
-        K = 0; pure = 0; pfw = 1; stride = 1;
+        K = 0; C = 1; A = 0; pure = 0; pfw = 1; stride = 1;
     }
     // on (K > 0), with the rows of `maxw` walkers if asked for; a failure
     // leaves it off
@@ -1785,7 +1787,8 @@ struct DmcEstSlot {
     {
         drop();
         if (a.K <= 0) return 0;
-        K = a.K; pure = a.pure; pfw = a.pfw; stride = a.stride;
+        K = a.K; C = a.C; A = a.A; pure = a.pure; pfw = a.pfw;
+        stride = a.stride;
         for (int b = 0; b < 2 && a.aux; ++b)
             if (aux[b].alloc(maxw * aux_row())) {
                 drop();
@@ -1830,18 +1833,11 @@ struct qmc_dmc {
     // set together, the pair distribution (qmc_pairdist.h) and the
     // centre-of-mass diffusion (qmc_cmdiff.h: two sums per step, one double
     // per walker) and the imaginary-time density correlations (qmc_isf.h:
-    // K modes of C = lags + 2 doubles, C set with the slot), each set on its
-    // own
+    // K modes of lags + 2 doubles), each set on its own
     DmcEstSlot est[EST_SLOTS];
     DevBuf<double> est_partial;     // [EST_BLOCKS][widest row]
     long long est_block_steps = 0;  // steps of the estimator block in progress
     int est_last_act = 1;           // aux buffer the last estimator step wrote
-    qmc_dmc()
-    {
-        est[EST_SSF].C = 3;
-        est[EST_CM].C = 2;
-        est[EST_CM].A = 1;
-    }
     bool any_est() const
     {
         return std::any_of(est, est + EST_SLOTS,
@@ -2332,8 +2328,8 @@ extern "C" int qmc_dmc_set_estimators(qmc_dmc *d, const qmc_dmc_est_params *p)
     // they are allocated all the same, so that the memory footprint and the
     // walker records of such a population stay what they were.
     const DmcEstSpec spec[2] = {
-        { p->num_modes, p->ssf_pure, p->ssf_pfw, true },
-        { p->num_bins, p->dens_pure, p->dens_pfw, true } };
+        { p->num_modes, 3, p->ssf_pure, p->ssf_pfw, true },
+        { p->num_bins, 1, p->dens_pure, p->dens_pfw, true } };
     return dmc_set_est_slots(d, EST_SSF, 2, spec);
 }
 
@@ -2351,24 +2347,33 @@ extern "C" int qmc_dmc_set_pair_dist_estimator(qmc_dmc *d, int32_t num_bins,
     static_assert(PD_EST_MAXN >= 512, "every engine's boson_number fits");
     HIP_TRY(hipSetDevice(d->eng->device));
     // per-walker rows only when pure: the mixed kernel keeps none
-    const DmcEstSpec spec = { num_bins, pure ? 1 : 0, pure ? pfw : 1,
+    const DmcEstSpec spec = { num_bins, 1, pure ? 1 : 0, pure ? pfw : 1,
                               pure != 0 };
     return dmc_set_est_slots(d, EST_PD, 1, &spec);
+}
+
+// The first `nsteps` rows of slot `k` in the last estimator block: what the
+// read entry points of the slots that are set on their own share.
+static int dmc_read_est_rows(qmc_dmc *d, int k, int64_t nsteps,
+                             double *iter_out, const char *entry,
+                             const char *estimator)
+{
+    const std::string who = std::string(entry) + ": ";
+    if (!d || !iter_out) return fail(who + "null argument");
+    const DmcEstSlot &s = d->est[k];
+    if (!s.on())
+        return fail(who + "the " + estimator + " estimator is not set");
+    if (nsteps <= 0 || nsteps > d->est_block_steps)
+        return fail(who + "nsteps outside the last estimator block");
+    HIP_TRY(hipSetDevice(d->eng->device));
+    return read_doubles(d->eng, iter_out, s.iter, (size_t)nsteps * s.row());
 }
 
 extern "C" int qmc_dmc_read_pair_dist(qmc_dmc *d, int64_t nsteps,
                                       double *iter_out)
 {
-    if (!d || !iter_out) return fail("qmc_dmc_read_pair_dist: null argument");
-    const DmcEstSlot &s = d->est[EST_PD];
-    if (!s.on())
-        return fail("qmc_dmc_read_pair_dist: the pair distribution estimator "
-                    "is not set");
-    if (nsteps <= 0 || nsteps > d->est_block_steps)
-        return fail("qmc_dmc_read_pair_dist: nsteps outside the last "
-                    "estimator block");
-    HIP_TRY(hipSetDevice(d->eng->device));
-    return read_doubles(d->eng, iter_out, s.iter, (size_t)nsteps * s.row());
+    return dmc_read_est_rows(d, EST_PD, nsteps, iter_out,
+                             "qmc_dmc_read_pair_dist", "pair distribution");
 }
 
 // The centre-of-mass diffusion estimator (qmc_cmdiff.h) is set on its own as
@@ -2378,24 +2383,16 @@ extern "C" int qmc_dmc_set_cm_diffusion_estimator(qmc_dmc *d, int32_t on)
 {
     if (!d) return fail("qmc_dmc_set_cm_diffusion_estimator: null argument");
     HIP_TRY(hipSetDevice(d->eng->device));
-    const DmcEstSpec spec = { on ? 1 : 0, 0, 1, true };
+    const DmcEstSpec spec = { on ? 1 : 0, 2, 0, 1, true, 1 };
     return dmc_set_est_slots(d, EST_CM, 1, &spec);
 }
 
 extern "C" int qmc_dmc_read_cm_diffusion(qmc_dmc *d, int64_t nsteps,
                                          double *iter_out)
 {
-    if (!d || !iter_out)
-        return fail("qmc_dmc_read_cm_diffusion: null argument");
-    const DmcEstSlot &s = d->est[EST_CM];
-    if (!s.on())
-        return fail("qmc_dmc_read_cm_diffusion: the centre-of-mass diffusion "
-                    "estimator is not set");
-    if (nsteps <= 0 || nsteps > d->est_block_steps)
-        return fail("qmc_dmc_read_cm_diffusion: nsteps outside the last "
-                    "estimator block");
-    HIP_TRY(hipSetDevice(d->eng->device));
-    return read_doubles(d->eng, iter_out, s.iter, (size_t)nsteps * s.row());
+    return dmc_read_est_rows(d, EST_CM, nsteps, iter_out,
+                             "qmc_dmc_read_cm_diffusion",
+                             "centre-of-mass diffusion");
 }
 
 // The imaginary-time density correlations F(k, tau) (qmc_isf.h) are set on
@@ -2421,24 +2418,17 @@ extern "C" int qmc_dmc_set_isf_estimator(qmc_dmc *d, int32_t num_modes,
                         "must not exceed 1024");
     }
     HIP_TRY(hipSetDevice(d->eng->device));
-    const DmcEstSpec spec = { num_modes, 0, num_modes > 0 ? num_lags : 1, true,
-                              num_modes > 0 ? (int)lag_stride : 1 };
-    // (off: the slot is dropped and C does not matter)
-    d->est[EST_ISF].C = num_modes > 0 ? num_lags + 2 : 1;
+    const bool on = num_modes > 0;  // (off: the unchecked rest is not read)
+    const DmcEstSpec spec = { num_modes, on ? num_lags + 2 : 1, 0,
+                              on ? num_lags : 1, true, 0,
+                              on ? (int)lag_stride : 1 };
     return dmc_set_est_slots(d, EST_ISF, 1, &spec);
 }
 
 extern "C" int qmc_dmc_read_isf(qmc_dmc *d, int64_t nsteps, double *iter_out)
 {
-    if (!d || !iter_out) return fail("qmc_dmc_read_isf: null argument");
-    const DmcEstSlot &s = d->est[EST_ISF];
-    if (!s.on())
-        return fail("qmc_dmc_read_isf: the F(k, tau) estimator is not set");
-    if (nsteps <= 0 || nsteps > d->est_block_steps)
-        return fail("qmc_dmc_read_isf: nsteps outside the last estimator "
-                    "block");
-    HIP_TRY(hipSetDevice(d->eng->device));
-    return read_doubles(d->eng, iter_out, s.iter, (size_t)nsteps * s.row());
+    return dmc_read_est_rows(d, EST_ISF, nsteps, iter_out, "qmc_dmc_read_isf",
+                             "F(k, tau)");
 }
 
 // Evaluate the estimators on the population yielded by the step that has just
@@ -2493,12 +2483,9 @@ static int dmc_enqueue_estimators(qmc_dmc *d, long long step_idx)
             a.stride = 1;
         }
         const int row = (int)s.row();
-        double div = 1.0;
-        if (a.pure) div = step_idx < a.pfw ? (double)(step_idx + 1)
-                                           : (double)a.pfw;
         hipLaunchKernelGGL(est_reduce_kernel, dim3((row + 31) / 32), dim3(256),
-                           0, e->stream, d->est_partial, EST_BLOCKS, row, div,
-                           s.iter + (size_t)step_idx * row);
+                           0, e->stream, d->est_partial, EST_BLOCKS, row,
+                           a.divisor(), s.iter + (size_t)step_idx * row);
     }
     HIP_TRY(hipGetLastError());
     return 0;

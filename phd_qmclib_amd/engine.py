@@ -620,6 +620,7 @@ class DmcEnsemble:
         h = C.c_void_p()
         check(self._lib.qmc_dmc_create(engine._h, C.byref(p), C.byref(h)))
         self._h = h
+        self.num_modes = self.num_bins = 0
         self.pair_dist_bins = 0
         self.cm_diffusion = False
         self.isf_shape = None
@@ -684,6 +685,19 @@ class DmcEnsemble:
                                          g.size, ptr(u_off, _i64p),
                                          ptr(g_off, _i64p), u_off.size))
 
+    @staticmethod
+    def _series(nsteps):
+        """-> (DmcSeries of zeros, the pointers to its five arrays)."""
+        e, w, r, a = (np.zeros(nsteps) for _ in range(4))
+        nw = np.zeros(nsteps, dtype=np.uint64)
+        return (DmcSeries(e, w, nw, r, a),
+                (ptr(e), ptr(w), ptr(nw, _u64p), ptr(r), ptr(a)))
+
+    def _read_rows(self, fn, nsteps, row_shape):
+        out = np.zeros((int(nsteps),) + tuple(row_shape))
+        check(fn(self._h, int(nsteps), ptr(out)))
+        return out
+
     def run_block(self, nsteps: int, read: bool = True):
         """`nsteps` time steps; -> DmcSeries (or None when read=False: the
         series stay on the device until `read_series`)."""
@@ -691,12 +705,9 @@ class DmcEnsemble:
             check(self._lib.qmc_dmc_run_block(self._h, int(nsteps), None, None,
                                               None, None, None))
             return None
-        e, w = np.zeros(nsteps), np.zeros(nsteps)
-        nw = np.zeros(nsteps, dtype=np.uint64)
-        r, a = np.zeros(nsteps), np.zeros(nsteps)
-        check(self._lib.qmc_dmc_run_block(self._h, int(nsteps), ptr(e), ptr(w),
-                                          ptr(nw, _u64p), ptr(r), ptr(a)))
-        return DmcSeries(e, w, nw, r, a)
+        ser, ptrs = self._series(nsteps)
+        check(self._lib.qmc_dmc_run_block(self._h, int(nsteps), *ptrs))
+        return ser
 
     def set_estimators(self, num_modes=0, ssf_pure=False, ssf_pfw=1,
                        num_bins=0, dens_pure=False, dens_pfw=1):
@@ -709,16 +720,13 @@ class DmcEnsemble:
     def run_block_est(self, nsteps: int, eval_estimators: bool = True):
         """-> (DmcSeries, iter_ssf[nsteps, M, 3] or None,
         iter_density[nsteps, B, 1] or None)."""
-        M, B = getattr(self, 'num_modes', 0), getattr(self, 'num_bins', 0)
-        e, w = np.zeros(nsteps), np.zeros(nsteps)
-        nw = np.zeros(nsteps, dtype=np.uint64)
-        r, a = np.zeros(nsteps), np.zeros(nsteps)
-        ssf = np.zeros((nsteps, M, 3)) if M else None
-        dens = np.zeros((nsteps, B, 1)) if B else None
+        ser, ptrs = self._series(nsteps)
+        ssf = np.zeros((nsteps, self.num_modes, 3)) if self.num_modes else None
+        dens = np.zeros((nsteps, self.num_bins, 1)) if self.num_bins else None
         check(self._lib.qmc_dmc_run_block_est(
-            self._h, int(nsteps), int(bool(eval_estimators)), ptr(e), ptr(w),
-            ptr(nw, _u64p), ptr(r), ptr(a), ptr(ssf), ptr(dens)))
-        return DmcSeries(e, w, nw, r, a), ssf, dens
+            self._h, int(nsteps), int(bool(eval_estimators)), *ptrs, ptr(ssf),
+            ptr(dens)))
+        return ser, ssf, dens
 
     def set_pair_dist_estimator(self, num_bins, pure=False, pfw=1):
         """Enable the pair distribution estimator g2(r) of the estimator
@@ -734,9 +742,8 @@ class DmcEnsemble:
         """Rows of the last estimator block -> iter_pair_dist[nsteps, B]:
         per time step the pair histograms summed over the walkers (pure: the
         forward-walking rows over min(step + 1, pfw))."""
-        out = np.zeros((int(nsteps), self.pair_dist_bins))
-        check(self._lib.qmc_dmc_read_pair_dist(self._h, int(nsteps), ptr(out)))
-        return out
+        return self._read_rows(self._lib.qmc_dmc_read_pair_dist, nsteps,
+                               (self.pair_dist_bins,))
 
     def set_cm_diffusion_estimator(self, on=True):
         """Enable (or disable) the centre-of-mass diffusion estimator of the
@@ -752,10 +759,8 @@ class DmcEnsemble:
         step t the sums over the yielded walkers of Y and Y^2, Y being N
         times the unwrapped centre-of-mass displacement of a walker since the
         first yielded state of the block (row 0 is zero)."""
-        out = np.zeros((int(nsteps), 2))
-        check(self._lib.qmc_dmc_read_cm_diffusion(self._h, int(nsteps),
-                                                  ptr(out)))
-        return out
+        return self._read_rows(self._lib.qmc_dmc_read_cm_diffusion, nsteps,
+                               (2,))
 
     def set_isf_estimator(self, num_modes, num_lags=1, lag_stride=1):
         """Enable the imaginary-time density correlations F(k, tau) of the
@@ -779,18 +784,13 @@ class DmcEnsemble:
         step)."""
         if self.isf_shape is None:
             raise QmcError('read_isf: the F(k, tau) estimator is not set')
-        out = np.zeros((int(nsteps),) + self.isf_shape)
-        check(self._lib.qmc_dmc_read_isf(self._h, int(nsteps), ptr(out)))
-        return out
+        return self._read_rows(self._lib.qmc_dmc_read_isf, nsteps,
+                               self.isf_shape)
 
     def read_series(self, nsteps: int) -> DmcSeries:
-        e, w = np.zeros(nsteps), np.zeros(nsteps)
-        nw = np.zeros(nsteps, dtype=np.uint64)
-        r, a = np.zeros(nsteps), np.zeros(nsteps)
-        check(self._lib.qmc_dmc_read_series(self._h, int(nsteps), ptr(e),
-                                            ptr(w), ptr(nw, _u64p), ptr(r),
-                                            ptr(a)))
-        return DmcSeries(e, w, nw, r, a)
+        ser, ptrs = self._series(nsteps)
+        check(self._lib.qmc_dmc_read_series(self._h, int(nsteps), *ptrs))
+        return ser
 
     def get_state(self) -> DmcState:
         W, n = self.max_num_walkers, self.num_particles

@@ -74,13 +74,17 @@ def box(n, cut=0.25, depth=5 * pi ** 2, gint=2):
 # shapes of test_gpu_superfluid_est.py.  An odd N below a wavefront; N = 16;
 # N = 64 with more walkers than one pass of a block's wavefronts; N = 100, two
 # chunks of 32 particles and a ragged third plus a tail; a population that
-# starts at its cap.
+# starts at its cap; more live walkers than the launch has wavefronts (N = 37:
+# two chunks, the second ragged), so that every wavefront goes round its slot
+# loop again and rewrites its tables, its rho rows and its running sums.
+WAVEFRONTS = 4096               # of an estimator launch: 1024 blocks of 4
 SHAPES = {
     'odd':      (5, 0.25, 40, 64, 8, 1100),
     'mid':      (16, 0.25, 48, 64, 6, 13),
     'wave':     (64, 0.25, 300, 512, 10, 14),
     'two_pass': (100, 0.1, 64, 96, 6, 15),
     'cap':      (16, 0.25, 64, 64, 8, 1600),
+    'second_trip': (37, 0.25, 4500, 5120, 4, 1700),
 }
 KTQ = (8, 4, 2)
 # case: (shape, K, T, q).  Beyond the five shapes: the row limit K (T + 2) =
@@ -191,6 +195,8 @@ def test_rows_equal_the_restatement(case):
     assert len(set(ref['num_walkers']) | {nw0}) > 1
     if shape == 'cap':
         assert nw0 == maxw
+    if shape == 'second_trip':
+        assert maxw >= 5120 and (ref['num_walkers'] > WAVEFRONTS).all()
     for confs, _, nw in ref['steps']:
         assert confs[:nw].min() >= 0.0 and confs[:nw].max() <= n
     ser, _, _, _, _, rows = run_block_b(shape, (K, T, q))

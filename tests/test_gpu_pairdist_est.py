@@ -37,7 +37,11 @@ def box(n, cut=0.25):
 # an odd N with fewer bins than lanes; a single bin; more than 64 bins (the
 # lane = bin chunks); N = 64, one particle per lane, with pfw inside the block
 # (both divisors); N = 100, two passes over the own particles, at the largest
-# bin count; a population that starts at the cap.
+# bin count; a population that starts at the cap; more live walkers than the
+# launch has wavefronts (N = 37, bins in two lane chunks, pfw inside the block),
+# so that every wavefront goes round its slot loop again and rewrites its
+# positions and its histogram.
+WAVEFRONTS = 4096               # of an estimator launch: 1024 blocks of 4
 CASES = {
     'odd':      (5, 0.25, 7, 40, 64, 8, 3, 1100),
     'one_bin':  (16, 0.25, 1, 48, 64, 6, 3, 12),
@@ -45,6 +49,7 @@ CASES = {
     'wave':     (64, 0.25, 64, 300, 512, 10, 4, 14),
     'two_pass': (100, 0.1, 256, 64, 96, 6, 3, 15),
     'cap':      (16, 0.25, 16, 64, 64, 8, 3, 1600),
+    'second_trip': (37, 0.25, 70, 4500, 5120, 4, 2, 1700),
 }
 
 
@@ -126,6 +131,8 @@ def test_rows_equal_the_forward_walking(tag, pure):
     assert len(set(ref['num_walkers']) | {nw0}) > 1
     if tag == 'cap':
         assert nw0 == maxw
+    if tag == 'second_trip':
+        assert maxw >= 5120 and (ref['num_walkers'] > WAVEFRONTS).all()
     if pure:
         assert 1 < pfw < T          # both divisors, min(t + 1, pfw)
     ser, _, _, rows = run_block_b(tag, pure)

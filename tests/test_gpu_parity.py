@@ -415,13 +415,20 @@ def test_trajectories_at_other_cutoffs(oracle, cutoff):
     eng.close()
 
 
-@pytest.mark.parametrize('n,modes', [(16, 100), (16, 256), (37, 64), (70, 64),
-                                     (70, 130), (9, 3)])
-def test_ssf_matrix_core_kernel_vs_numpy(n, modes):
+# (an estimator launch has 4096 wavefronts, one per walker slot: the rows with
+# W = 4500 send every wavefront round its slot loop a second time)
+@pytest.mark.parametrize('n,modes,W,maxw', [
+    (16, 100, 300, 384), (16, 256, 300, 384), (37, 64, 300, 384),
+    (70, 64, 300, 384), (70, 130, 300, 384), (9, 3, 300, 384),
+    (37, 16, 4500, 5120), (16, 100, 4500, 5120)],
+    ids=['16-100', '16-256', '37-64', '70-64', '70-130', '9-3',
+         '37-16-4500', '16-100-4500'])
+def test_ssf_matrix_core_kernel_vs_numpy(n, modes, W, maxw):
     """S(k) parts of one time step against a direct numpy evaluation on the
     yielded walkers: both tilings of the MFMA kernel (<= 64 modes: one packed
     tile; <= 256: four tiles), particle counts that are not multiples of the
-    MFMA K = 4 nor of the 64-particle chunk."""
+    MFMA K = 4 nor of the 64-particle chunk, and for each tiling a population
+    above the wavefronts of a launch."""
     from math import pi
     from phd_qmclib_amd import mrbp_qmc
     from phd_qmclib_amd.engine import DmcEnsemble, ModelEngine
@@ -430,11 +437,12 @@ def test_ssf_matrix_core_kernel_vs_numpy(n, modes):
                          supercell_size=n, tbf_contact_cutoff=0.25 * n)
     eng = ModelEngine(spec.cfc_spec)
     rng = np.random.RandomState(n + modes)
-    W = 300
-    ens = DmcEnsemble(eng, 1e-3, 384, W, 0.5, rng_seed=5)
+    ens = DmcEnsemble(eng, 1e-3, maxw, W, 0.5, rng_seed=5)
     ens.set_state(n * rng.random_sample((W, n)))
     ens.set_estimators(num_modes=modes)
     ser, ssf, _ = ens.run_block_est(2, True)
+    if W > 4096:
+        assert maxw >= 5120 and (ser.num_walkers > 4096).all()
     st = ens.get_state()
     nw = st.num_walkers
     assert nw == int(ser.num_walkers[-1])
@@ -450,11 +458,15 @@ def test_ssf_matrix_core_kernel_vs_numpy(n, modes):
     eng.close()
 
 
-@pytest.mark.parametrize('n,bins', [(16, 256), (70, 200), (300, 33), (9, 5)])
-def test_density_kernel_vs_numpy(n, bins):
+@pytest.mark.parametrize('n,bins,W,maxw', [
+    (16, 256, 200, 256), (70, 200, 200, 256), (300, 33, 200, 256),
+    (9, 5, 200, 256), (70, 200, 4500, 5120)],
+    ids=['16-256', '70-200', '300-33', '9-5', '70-200-4500'])
+def test_density_kernel_vs_numpy(n, bins, W, maxw):
     """Density histogram of the first estimator step against numpy on the
     yielded walkers, for bin counts above the 64 lanes of a wavefront and
-    particle counts above one chunk."""
+    particle counts above one chunk, and for a population above the
+    wavefronts of a launch."""
     from math import pi
     from phd_qmclib_amd import mrbp_qmc
     from phd_qmclib_amd.engine import DmcEnsemble, ModelEngine
@@ -463,11 +475,12 @@ def test_density_kernel_vs_numpy(n, bins):
                          supercell_size=n, tbf_contact_cutoff=0.25 * n)
     eng = ModelEngine(spec.cfc_spec)
     rng = np.random.RandomState(n * bins)
-    W = 200
-    ens = DmcEnsemble(eng, 1e-3, 256, W, 0.5, rng_seed=2)
+    ens = DmcEnsemble(eng, 1e-3, maxw, W, 0.5, rng_seed=2)
     ens.set_state(n * rng.random_sample((W, n)))
     ens.set_estimators(num_bins=bins)
     ser, _, dens = ens.run_block_est(1, True)
+    if W > 4096:
+        assert maxw >= 5120 and (ser.num_walkers > 4096).all()
     st = ens.get_state()
     nw = st.num_walkers
     z = st.confs[:nw, 0, :]

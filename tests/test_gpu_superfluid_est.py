@@ -51,13 +51,16 @@ def box(n, cut=0.25, depth=5 * pi ** 2, gint=2):
 # shapes of test_gpu_pairdist_est.py.  An odd N below a wavefront; N = 16; N =
 # 64, one index per lane, with more walkers than one pass of a block's
 # wavefronts; N = 100, two passes over the indices; a population that starts
-# at its cap.
+# at its cap; more live walkers than the launch has wavefronts, so that every
+# wavefront goes round its slot loop again.
+WAVEFRONTS = 4096               # of an estimator launch: 1024 blocks of 4
 CASES = {
     'odd':      (5, 0.25, 40, 64, 8, 1100),
     'mid':      (16, 0.25, 48, 64, 6, 13),
     'wave':     (64, 0.25, 300, 512, 10, 14),
     'two_pass': (100, 0.1, 64, 96, 6, 15),
     'cap':      (16, 0.25, 64, 64, 8, 1600),
+    'second_trip': (37, 0.25, 4500, 5120, 4, 1700),
 }
 EST = dict(num_modes=8, ssf_pure=True, ssf_pfw=3, num_bins=12, dens_pure=False)
 G2 = dict(num_bins=20, pure=True, pfw=3)
@@ -139,6 +142,8 @@ def test_rows_equal_the_restatement(tag):
     assert ref['max_d'] < L / 4
     if tag == 'cap':
         assert nw0 == maxw
+    if tag == 'second_trip':
+        assert maxw >= 5120 and (ref['num_walkers'] > WAVEFRONTS).all()
     ser, _, _, _, rows = run_block_b(tag)
     assert np.array_equal(ser.num_walkers, ref['num_walkers'])
     assert np.array_equal(ser.energy, ref['energy'])
