@@ -465,6 +465,26 @@ int qmc_dmc_read_cm_diffusion(qmc_dmc *d, int64_t nsteps, double *iter_out);
 int qmc_dmc_set_isf_estimator(qmc_dmc *d, int32_t num_modes, int32_t num_lags,
                               int64_t lag_stride);
 int qmc_dmc_read_isf(qmc_dmc *d, int64_t nsteps, double *iter_out);
+/* One-body density matrix g1(s) as a sixth block estimator, last in launch
+ * order: the mixed estimator (g1 is non-local, forward walking does not
+ * apply).  Per evaluated time step t of an estimator block nshift doubles,
+ * iter[t][k] = sum over the yielded walkers, unweighted, of the g1 of the
+ * walker's configuration at shifts[k] (host, as qmc_obdm takes them: any
+ * finite value), computed by the code of qmc_obdm, fp64 whatever fast_math
+ * says; a zero shift gives exactly num_walkers[t].  The estimator costs
+ * nshift N (N - 1) shifted pair factors per walker, so it is evaluated only at
+ * the steps with t % eval_stride == 0 (the first step of a block always); the
+ * rows of the other steps are zero.  Limits: 0 <= nshift <= 256 (0 switches it
+ * off; shifts and eval_stride are not read then), 1 <= eval_stride <=
+ * 2^31 - 1.  The ensemble keeps a shift table of its own: qmc_obdm* calls on
+ * the engine do not disturb it.  Set on its own, as the pair distribution.
+ * read_obdm copies the first nsteps rows of the last estimator block to the
+ * host, iter_out[nsteps][nshift] (synchronises); rows of a block run with
+ * eval_estimators == 0 are zero.  The rows of several ranks are not summed:
+ * single-GPU only. */
+int qmc_dmc_set_obdm_estimator(qmc_dmc *d, int32_t nshift,
+                               const double *shifts, int64_t eval_stride);
+int qmc_dmc_read_obdm(qmc_dmc *d, int64_t nsteps, double *iter_out);
 /* The yielded ("actual") State after the last step (qmc_base/dmc.py:773-780):
  * confs[maxw][2][N], energy/weight[maxw], mask[maxw], cloning_ref[maxw];
  * scalars[5] = energy, weight, ref_energy, accum_energy, num_walkers. */

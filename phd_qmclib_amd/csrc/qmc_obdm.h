@@ -60,6 +60,7 @@
 #pragma once
 
 #include "qmc_device.h"
+#include "qmc_kernels_misc.h"
 
 static constexpr int OBDM_U = 2;        // shifts carried by a lane
 static constexpr int OBDM_FOLD = 32;    // partners between exponent folds
@@ -108,8 +109,24 @@ __device__ __forceinline__ double obdm_log_f1(const DevModel &m, double z)
         one_body_tab<true, false>(m, z, ldz, lf, barrier);
         return lf;
     }
-    double ldz, kp, f1, xoff;
-    one_body(m, z, ldz, kp, f1, xoff);
+    // The factor of `one_body` (qmc_device.h) without its derivatives, with
+    // the two offsets inside the cell written as the fused operations the
+    // batch kernel has always been compiled to: left to the compiler, a
+    // kernel with a loop around this code gets the products 0.5 z_a, 0.5 z_b
+    // hoisted out of it and rounded on their own, and the same configuration
+    // would give other bits in obdm_kernel and in dmc_obdm_kernel.
+    const double z_cell = z - floor(z);
+    double f1, xoff;
+    if (m.z_a < z_cell) {
+        const double x = m.kp1 * fma(0.5, m.z_b, z_cell - 1.0);
+        f1 = 0.5 * (exp_bounded(2.0 * x) + 1.0);
+        xoff = x;
+    } else {
+        double sh, ch;
+        sincos_kernel(m.k1_half * fma(-0.5, m.z_a, z_cell), sh, ch);
+        f1 = m.cf * ((ch - sh) * (ch + sh));
+        xoff = 0.0;
+    }
     return log_pos(f1) - xoff;
 }
 
@@ -193,24 +210,32 @@ __device__ __forceinline__ double obdm_row_log(const DevModel &m,
     return v + logf1;
 }
 
-// G: lanes of a shift group (8, 16, 32, 64; N <= G below 64).
-template <int G>
-__global__ void __launch_bounds__(64)
-obdm_kernel(const DevModel *__restrict__ mp, ObdmArgs a)
-{
-    const DevModel &m = *mp;
-    extern __shared__ double smem[];
-    const int n = m.n;
-    double *tab = smem;              // [n][4]
-    double *zraw = smem + 4 * n;     // positions as given
-    double *zbox = smem + 5 * n;     // their images in [0, L)
-    double *den = smem + 6 * n;      // log of the unshifted row
-    const long long c = blockIdx.x;
-    const int lane = threadIdx.x;
-    const double *row = a.pos + c * n;
-    const bool pairs = !m.is_ideal, onebody = !m.is_free;
-    const int npass = (n + 63) / 64;
+// ---- the stages of one configuration, run by one wavefront ---------------
+// obdm_kernel (a batch of configurations) and dmc_obdm_kernel (the walkers of
+// a DMC step) call the same three stages, so a configuration's g1 carries the
+// same bits from both.  The stages share the configuration's LDS region; the
+// caller orders them (stage 2 reads what stage 1 wrote, stage 3 what both
+// wrote): a block barrier where the block is the wavefront, wave-level fences
+// where the region belongs to one wavefront of a larger block.  Every lane of
+// the wavefront runs every stage: indices are clamped and stores masked.
+struct ObdmLds {
+    double *tab;       // [n][4] angle tables
+    double *zraw;      // positions as given
+    double *zbox;      // their images in [0, L)
+    double *den;       // log of the unshifted row
+    __device__ ObdmLds(double *base, int n)
+        : tab(base), zraw(base + 4 * n), zbox(base + 5 * n), den(base + 6 * n)
+    {
+    }
+};
 
+// Stage 1: the tables of the configuration `row`.
+__device__ __forceinline__ void obdm_fill_tables(const DevModel &m,
+                                                 const double *__restrict__ row,
+                                                 const ObdmLds &l, int lane)
+{
+    const int n = m.n;
+    const int npass = (n + 63) / 64;
     for (int p = 0; p < npass; ++p) {
         const int i = lane + 64 * p;
         const double z1 = (i < n) ? row[i] : 0.0;
@@ -219,14 +244,21 @@ obdm_kernel(const DevModel *__restrict__ mp, ObdmArgs a)
         sincos_halfpi(z * m.two_over_L, t.s, t.c);
         sincos_halfpi(z * m.k2_2pi, t.su, t.cu);
         if (i < n) {
-            tab[4 * i] = t.s; tab[4 * i + 1] = t.c;
-            tab[4 * i + 2] = t.su; tab[4 * i + 3] = t.cu;
-            zraw[i] = z1; zbox[i] = z;
+            l.tab[4 * i] = t.s; l.tab[4 * i + 1] = t.c;
+            l.tab[4 * i + 2] = t.su; l.tab[4 * i + 3] = t.cu;
+            l.zraw[i] = z1; l.zbox[i] = z;
         }
     }
-    __syncthreads();
+}
 
-    // the unshifted rows, once per configuration
+// Stage 2: the unshifted rows, once per configuration.
+__device__ __forceinline__ void obdm_unshifted_rows(const DevModel &m,
+                                                    const ObdmLds &l, int lane)
+{
+    const int n = m.n;
+    const double *tab = l.tab;
+    const bool pairs = !m.is_ideal, onebody = !m.is_free;
+    const int npass = (n + 63) / 64;
     for (int p = 0; p < npass; ++p) {
         const int i = lane + 64 * p;
         const int ic = min(i, n - 1);
@@ -237,16 +269,29 @@ obdm_kernel(const DevModel *__restrict__ mp, ObdmArgs a)
         ObdmRow r[1];
         r[0].PL = 0.5; r[0].PS = 0.5; r[0].eL = 1; r[0].eS = 1; r[0].cnt = 0;
         if (pairs) obdm_rows<1>(m, tab, n, own, self, r);
-        const double lf = onebody ? obdm_log_f1(m, zraw[ic]) : 0.0;
+        const double lf = onebody ? obdm_log_f1(m, l.zraw[ic]) : 0.0;
         const double v = obdm_row_log(m, r[0], lf);
-        if (i < n) den[i] = v;
+        if (i < n) l.den[i] = v;
     }
-    __syncthreads();
+}
 
+// Stage 3: the shifts [k0, k1) of the table `stab` (nshift rows).  Groups of
+// G lanes take one shift each and every lane carries OBDM_U of them;
+// out.ith(k, i, v) gets the ratio of particle i at shift k from its lane,
+// out.g1(k, v) the mean over the particles from the leader of the group.
+template <int G, typename Out>
+__device__ __forceinline__ void obdm_shift_loop(const DevModel &m,
+                                                const ObdmLds &l, int lane,
+                                                const double *__restrict__ stab,
+                                                int nshift, int k0, int k1,
+                                                Out out)
+{
+    const int n = m.n;
+    const double *tab = l.tab, *zraw = l.zraw, *zbox = l.zbox, *den = l.den;
+    const bool pairs = !m.is_ideal, onebody = !m.is_free;
+    const int npass = (n + 63) / 64;
     constexpr int GPW = 64 / G;                 // shift groups of a wavefront
     const int grp = lane / G, gl = lane % G;
-    const int k0 = blockIdx.y * a.chunk;
-    const int k1 = min(a.nshift, k0 + a.chunk);
     const double inv_guard = 700.0;             // domain of exp_bounded
     for (int kb = k0; kb < k1; kb += GPW * OBDM_U) {
         int ks[OBDM_U];
@@ -255,7 +300,7 @@ obdm_kernel(const DevModel *__restrict__ mp, ObdmArgs a)
         for (int u = 0; u < OBDM_U; ++u) {
             ks[u] = kb + GPW * u + grp;
             const double *srow =
-                a.stab + (size_t)min(ks[u], a.nshift - 1) * OBDM_SROW;
+                stab + (size_t)min(ks[u], nshift - 1) * OBDM_SROW;
 #pragma unroll
             for (int q = 0; q < OBDM_SROW - 2; ++q) sh[u][q] = srow[q];
         }
@@ -308,8 +353,7 @@ obdm_kernel(const DevModel *__restrict__ mp, ObdmArgs a)
                 const bool ok = (i < n) & (ks[u] < k1);
                 if (ok) {
                     acc[u] += v;
-                    if (a.ith)
-                        a.ith[((size_t)c * a.nshift + ks[u]) * n + i] = v;
+                    out.ith(ks[u], i, v);
                 }
             }
         }
@@ -320,10 +364,116 @@ obdm_kernel(const DevModel *__restrict__ mp, ObdmArgs a)
 #pragma unroll
             for (int off = G / 2; off >= 1; off >>= 1)
                 t += __shfl_xor(t, off, 64);
-            if (gl == 0 && ks[u] < k1)
-                a.g1[(size_t)c * a.nshift + ks[u]] = t / (double)n;
+            if (gl == 0 && ks[u] < k1) out.g1(ks[u], t / (double)n);
         }
     }
+}
+
+// G: lanes of a shift group (8, 16, 32, 64; N <= G below 64).
+template <int G>
+__global__ void __launch_bounds__(64)
+obdm_kernel(const DevModel *__restrict__ mp, ObdmArgs a)
+{
+    const DevModel &m = *mp;
+    extern __shared__ double smem[];
+    const int n = m.n;
+    const ObdmLds l(smem, n);
+    const long long c = blockIdx.x;
+    const int lane = threadIdx.x;
+
+    obdm_fill_tables(m, a.pos + c * n, l, lane);
+    __syncthreads();
+    obdm_unshifted_rows(m, l, lane);
+    __syncthreads();
+
+    const int k0 = blockIdx.y * a.chunk;
+    const int k1 = min(a.nshift, k0 + a.chunk);
+    struct Out {
+        double *g1v, *ithv;
+        int n;
+        __device__ __forceinline__ void ith(int k, int i, double v) const
+        {
+            if (ithv) ithv[(size_t)k * n + i] = v;
+        }
+        __device__ __forceinline__ void g1(int k, double v) const { g1v[k] = v; }
+    };
+    const Out out{ a.g1 + (size_t)c * a.nshift,
+                   a.ith ? a.ith + (size_t)c * a.nshift * n : nullptr, n };
+    obdm_shift_loop<G>(m, l, lane, a.stab, a.nshift, k0, k1, out);
+}
+
+// ---- g1(s) as a DMC block estimator --------------------------------------
+// The mixed g1 of the yielded walkers of a time step, in the frame of the
+// other DMC estimators (qmc_kernels_misc.h: EstArgs, est_reduce_kernel).
+// Walker s carries the configuration of its parent, ppos[ref[s]]:
+//
+//   iter[t][k] = sum_{s < nw_t} g1_s(shift_k)        (a.K shifts, divisor 1)
+//
+// Mixed only (g1 is non-local: forward walking does not apply), the walkers
+// unweighted as in the mixed g2, no per-walker rows.
+//
+// One wavefront per walker slot, grid-striding over the live slots.  Per walker
+// it runs the three stages above on an LDS region of its own
+// (OBDM_LDS_PER_PARTICLE * N doubles), all K shifts in one go.  The region is
+// touched by that wavefront alone, so wave-level fences and wave barriers order
+// the stages (as dmc_pair_dist_kernel); the wavefronts of a block go round the
+// slot loop different numbers of times, so no block barrier may stand in it.
+// A wave-private LDS row of K running sums takes the walkers in the wave's
+// slot order: sum[k] is read and written by one lane only, the leader of the
+// group that owns shift k, the same for every walker.  est_block_sum adds up
+// the wavefronts of a block (its barrier is the only one of the block),
+// est_reduce_kernel the blocks.  No floating-point atomics: the same bits on
+// every run.  fp64 whatever fast_math says.
+//
+// Dynamic LDS: [NWAVE][K] sums, then [NWAVE][7 N] tables -- 120 KB at N = 512,
+// K = 256 (one block per CU then).  The model and the shift table travel
+// beside EstArgs, whose layout the other estimators share.
+static size_t dmc_obdm_lds_bytes(int n, int K)
+{
+    return (size_t)(BLOCK / 64) * ((size_t)K + (size_t)n * OBDM_LDS_PER_PARTICLE) *
+           sizeof(double);
+}
+
+template <int G>
+__global__ void __launch_bounds__(BLOCK)
+dmc_obdm_kernel(const DevModel *__restrict__ mp,
+                const double *__restrict__ stab, EstArgs a)
+{
+    constexpr int NWAVE = BLOCK / 64;
+    const DevModel &m = *mp;
+    extern __shared__ double smem[];
+    const int n = m.n, K = a.K;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double *sum = smem + (size_t)wave * K;                      // [NWAVE][K]
+    const ObdmLds l(smem + (size_t)NWAVE * K +
+                        (size_t)wave * n * OBDM_LDS_PER_PARTICLE, n);
+    for (int k = lane; k < K; k += 64) sum[k] = 0.0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    struct Out {
+        double *sum;
+        __device__ __forceinline__ void ith(int, int, double) const {}
+        __device__ __forceinline__ void g1(int k, double v) const { sum[k] += v; }
+    };
+    const Out out{ sum };
+    const long long nw = a.ctl->nw;
+    const long long wstride = (long long)gridDim.x * NWAVE;
+    for (long long s = (long long)blockIdx.x * NWAVE + wave; s < nw;
+         s += wstride) {
+        const long long par = a.ref[s];
+        obdm_fill_tables(m, a.ppos + (size_t)par * n, l, lane);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        obdm_unshifted_rows(m, l, lane);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        obdm_shift_loop<G>(m, l, lane, stab, K, 0, K, out);
+        __builtin_amdgcn_wave_barrier();    // the tables are rewritten next
+    }
+    est_block_sum(smem, K, K, a.partial);
 }
 
 // sums[k][0..1] (+)= sum_c w_c g1[c][k], sum_c w_c g1[c][k]^2 and, in the

@@ -1424,16 +1424,24 @@ static constexpr long long OBDM_TILE = 1ll << 16;
 // qmc_obdm keeps on the device at a time (128 MB).
 static constexpr long long OBDM_HOST_TILE_DOUBLES = 1ll << 24;
 
-// shift table of a set of device-resident shifts, on the engine's stream
+// rows [nshift][OBDM_SROW] of a set of device-resident shifts, on the
+// engine's stream
+static int obdm_fill_shift_table(const qmc_engine *e, int32_t nshift,
+                                 const double *shifts_dev, double *stab_dev)
+{
+    hipLaunchKernelGGL(obdm_shift_kernel, dim3((nshift + 63) / 64), dim3(64),
+                       0, e->stream, e->dm_dev, shifts_dev, (int)nshift,
+                       stab_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the engine's shift table (every qmc_obdm* call rewrites it)
 static int obdm_make_shift_table(qmc_engine *e, int32_t nshift,
                                  const double *shifts_dev)
 {
     if (e->obdm_stab.reserve((size_t)nshift * OBDM_SROW)) return 1;
-    hipLaunchKernelGGL(obdm_shift_kernel, dim3((nshift + 63) / 64), dim3(64),
-                       0, e->stream, e->dm_dev, shifts_dev, (int)nshift,
-                       e->obdm_stab);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return obdm_fill_shift_table(e, nshift, shifts_dev, e->obdm_stab);
 }
 
 // g1 (and ith) of nconf configurations against the engine's shift table
@@ -1757,7 +1765,7 @@ struct DmcEstSpec {
     long long pfw;
     bool aux;
     int A = 0;
-    int stride = 1;              // (F(k, tau) only)
+    int stride = 1;              // (F(k, tau), g1(s))
 };
 
 // One per-step estimator of a population: K modes or bins of C doubles each.
@@ -1768,9 +1776,12 @@ struct DmcEstSlot {
                                  // output, K * C
     int pure = 0;
     long long pfw = 1;           // forward-walking length; F(k, tau): lags
-    int stride = 1;              // F(k, tau): time steps per lag
+    int stride = 1;              // F(k, tau): time steps per lag; g1(s): time
+                                 // steps per evaluation
     DevBuf<double> aux[2];       // [maxw][aux_row()] per-walker rows (null: none kept)
     DevBuf<double> iter;         // [steps][K][C] per-step outputs, grown on demand
+    DevBuf<double> tab;          // a table of the estimator's own (g1(s): the
+                                 // shift rows), filled by its setter
     size_t row() const { return (size_t)K * C; }
     size_t aux_row() const { return A ? (size_t)A : row(); }
     bool on() const { return K > 0; }
@@ -1779,6 +1790,7 @@ struct DmcEstSlot {
         aux[0].release();
         aux[1].release();
         iter.release();
+        tab.release();
         K = 0; C = 1; A = 0; pure = 0; pfw = 1; stride = 1;
     }
     // on (K > 0), with the rows of `maxw` walkers if asked for; a failure
@@ -1797,7 +1809,7 @@ struct DmcEstSlot {
         return 0;
     }
 };
-enum { EST_SSF, EST_DENS, EST_PD, EST_CM, EST_ISF, EST_SLOTS };
+enum { EST_SSF, EST_DENS, EST_PD, EST_CM, EST_ISF, EST_OBDM, EST_SLOTS };
 
 struct qmc_dmc {
     qmc_engine *eng = nullptr;
@@ -1833,7 +1845,8 @@ struct qmc_dmc {
     // set together, the pair distribution (qmc_pairdist.h) and the
     // centre-of-mass diffusion (qmc_cmdiff.h: two sums per step, one double
     // per walker) and the imaginary-time density correlations (qmc_isf.h:
-    // K modes of lags + 2 doubles), each set on its own
+    // K modes of lags + 2 doubles), each set on its own, and the one-body
+    // density matrix (qmc_obdm.h: K shifts, its shift table in the slot)
     DmcEstSlot est[EST_SLOTS];
     DevBuf<double> est_partial;     // [EST_BLOCKS][widest row]
     long long est_block_steps = 0;  // steps of the estimator block in progress
@@ -2431,6 +2444,84 @@ extern "C" int qmc_dmc_read_isf(qmc_dmc *d, int64_t nsteps, double *iter_out)
                              "F(k, tau)");
 }
 
+// The one-body density matrix g1(s) (qmc_obdm.h) is set on its own as well:
+// mixed, no per-walker rows.  The shift rows live in the slot, not in the
+// engine's scratch table, which any qmc_obdm* call on the engine rewrites;
+// the slot's drop releases them.  The shifts as given sit behind the rows
+// (the shift kernel reads them there).  The estimator is evaluated at the
+// steps of a block with step_idx % eval_stride == 0; the rows of the other
+// steps stay zero.
+extern "C" int qmc_dmc_set_obdm_estimator(qmc_dmc *d, int32_t nshift,
+                                          const double *shifts,
+                                          int64_t eval_stride)
+{
+    const char *who = "qmc_dmc_set_obdm_estimator";
+    if (!d) return fail(std::string(who) + ": null argument");
+    if (nshift < 0 || nshift > EST_MAXK)
+        return fail(std::string(who) + ": nshift must be in [0, 256]");
+    if (nshift > 0) {
+        if (obdm_check_host_shifts(who, nshift, shifts)) return 1;
+        if (eval_stride < 1 || eval_stride > INT32_MAX)
+            return fail(std::string(who) +
+                        ": eval_stride must be in [1, 2^31 - 1]");
+    }
+    qmc_engine *e = d->eng;
+    HIP_TRY(hipSetDevice(e->device));
+    const bool on = nshift > 0;     // (off: the unchecked rest is not read)
+    const DmcEstSpec spec = { nshift, 1, 0, 1, false, 0,
+                              on ? (int)eval_stride : 1 };
+    if (dmc_set_est_slots(d, EST_OBDM, 1, &spec)) return 1;
+    if (!on) return 0;
+    DmcEstSlot &s = d->est[EST_OBDM];
+    const size_t K = (size_t)nshift;
+    int rc = s.tab.alloc(K * (OBDM_SROW + 1));
+    if (!rc) {
+        double *dsh = s.tab + K * OBDM_SROW;
+        hipError_t he = hipMemcpyAsync(dsh, shifts, K * sizeof(double),
+                                       hipMemcpyHostToDevice, e->stream);
+        if (he != hipSuccess)
+            rc = fail(std::string(who) + ": " + hipGetErrorString(he));
+        if (!rc) rc = obdm_fill_shift_table(e, nshift, dsh, s.tab);
+        if (!rc && (he = hipStreamSynchronize(e->stream)) != hipSuccess)
+            rc = fail(std::string(who) + ": " + hipGetErrorString(he));
+    }
+    if (rc) {
+        // nothing is ever on over a missing table (the message stays)
+        const std::string msg = g_err;
+        const DmcEstSpec off = { 0, 1, 0, 1, false };
+        (void)dmc_set_est_slots(d, EST_OBDM, 1, &off);
+        return fail(msg);
+    }
+    return 0;
+}
+
+extern "C" int qmc_dmc_read_obdm(qmc_dmc *d, int64_t nsteps, double *iter_out)
+{
+    return dmc_read_est_rows(d, EST_OBDM, nsteps, iter_out,
+                             "qmc_dmc_read_obdm", "one-body density");
+}
+
+// g1(s) of the walkers of a step: lane groups of est_width(N), the dynamic LDS
+// sized from N and K (beyond the default limit at large N: allow_lds).  (The
+// caller checks the launch with the reduction that follows.)
+static void launch_dmc_obdm(const qmc_engine *e, const double *stab,
+                            const EstArgs &a)
+{
+    const size_t lds = dmc_obdm_lds_bytes(a.n, a.K);
+    auto go = [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        allow_lds(dmc_obdm_kernel<G>, lds);
+        hipLaunchKernelGGL(dmc_obdm_kernel<G>, dim3(EST_BLOCKS), dim3(BLOCK),
+                           lds, e->stream, e->dm_dev, stab, a);
+    };
+    switch (est_width(a.n)) {
+    case 8: go(std::integral_constant<int, 8>{}); break;
+    case 16: go(std::integral_constant<int, 16>{}); break;
+    case 32: go(std::integral_constant<int, 32>{}); break;
+    default: go(std::integral_constant<int, 64>{}); break;
+    }
+}
+
 // Evaluate the estimators on the population yielded by the step that has just
 // been finished (its parents are the buffer that is not `cur`).
 static int dmc_enqueue_estimators(qmc_dmc *d, long long step_idx)
@@ -2447,7 +2538,10 @@ static int dmc_enqueue_estimators(qmc_dmc *d, long long step_idx)
     for (int k = 0; k < EST_SLOTS; ++k) {
         const DmcEstSlot &s = d->est[k];
         if (!s.on()) continue;
-        // (null where no per-walker rows are kept: the mixed g2)
+        // g1(s): only every s.stride-th step of the block, the first included
+        // (the rows of the others stay as begin_block zeroed them)
+        if (k == EST_OBDM && step_idx % s.stride != 0) continue;
+        // (null where no per-walker rows are kept: the mixed g2, g1)
         a.aux_prev = s.aux[prev]; a.aux_act = s.aux[act];
         a.K = s.K; a.pure = s.pure; a.pfw = s.pfw;
         a.scale2 = 0.0;
@@ -2474,6 +2568,10 @@ static int dmc_enqueue_estimators(qmc_dmc *d, long long step_idx)
             hipLaunchKernelGGL(dmc_cm_diffusion_kernel, dim3(EST_BLOCKS),
                                dim3(BLOCK), 0, e->stream, a);
             a.cpos = nullptr;
+            break;
+        case EST_OBDM:
+            a.scale = 0.0;
+            launch_dmc_obdm(e, s.tab, a);
             break;
         default:
             a.scale = 4.0 / e->dm.L;              // as S(k)

@@ -182,6 +182,11 @@ class DistributedDmc:
                 'its per-walker rows are not part of the walker record that '
                 'the population rebalance moves between ranks; switch it off '
                 '(set_isf_estimator(0)) for a distributed run')
+        if getattr(ensemble, 'obdm_shifts', None) is not None:
+            raise NotImplementedError(
+                'the one-body density estimator is single-GPU only: its rows '
+                'are not yet summed across ranks; switch it off '
+                '(set_obdm_estimator(None)) for a distributed run')
         self.ens = ensemble
         self.n = int(num_particles)
         self.device = torch.device(device)

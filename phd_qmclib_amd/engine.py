@@ -13,7 +13,7 @@ from ._lib import (DmcEstParams, DmcParams, ModelParams, QmcError, VmcParams,
                    _i64p, _u64p, _u8p)
 
 __all__ = ['ModelEngine', 'VmcEnsemble', 'DmcEnsemble', 'EvalResult',
-           'DeviceBuffer',
+           'DeviceBuffer', 'momentum_distribution',
            'model_params_struct', 'QmcError']
 
 
@@ -110,6 +110,27 @@ def intermediate_scattering(iter_isf, num_walkers, boson_number, time_step,
     tau = np.arange(num_lags) * (int(lag_stride) * float(time_step))
     rho_mean = last[:, num_lags] + 1j * last[:, num_lags + 1]
     return tau, last[:, :num_lags].T / int(boson_number), rho_mean
+
+
+def momentum_distribution(shifts, g1, momenta, density):
+    """n(k) = density * 2 int_0^{s_max} g1(s) cos(k s) ds by the trapezoid
+    rule on the grid `shifts` (non-negative, increasing; g1 is even in s) ->
+    n[..., len(momenta)] for g1[..., len(shifts)]."""
+    s = np.asarray(shifts, dtype=np.float64)
+    g1 = np.asarray(g1, dtype=np.float64)
+    k = np.atleast_1d(np.asarray(momenta, dtype=np.float64))
+    if s.ndim != 1 or s.size < 2 or g1.shape[-1] != s.size:
+        raise ValueError('shifts must be a 1-d grid of at least two points '
+                         'and the last axis of g1 must match it')
+    if s[0] < 0 or not np.all(np.diff(s) > 0):
+        raise ValueError('shifts must be non-negative and increasing')
+    # trapezoid weights of the grid
+    w = np.zeros_like(s)
+    ds = np.diff(s)
+    w[:-1] += 0.5 * ds
+    w[1:] += 0.5 * ds
+    kern = np.cos(s[:, None] * k[None, :]) * w[:, None]       # [S, M]
+    return 2.0 * float(density) * (g1 @ kern)
 
 
 def _pos2d(pos, num_particles,
@@ -624,6 +645,7 @@ class DmcEnsemble:
         self.pair_dist_bins = 0
         self.cm_diffusion = False
         self.isf_shape = None
+        self.obdm_shifts = None
 
     def close(self):
         if getattr(self, '_h', None):
@@ -786,6 +808,35 @@ class DmcEnsemble:
             raise QmcError('read_isf: the F(k, tau) estimator is not set')
         return self._read_rows(self._lib.qmc_dmc_read_isf, nsteps,
                                self.isf_shape)
+
+    def set_obdm_estimator(self, shifts, eval_stride=1):
+        """Enable the mixed one-body density matrix g1(s) of the estimator
+        blocks at the given shifts (1..256 finite values; None or an empty
+        sequence disables it), evaluated at every `eval_stride`-th step of a
+        block, the first included.  The ensemble keeps its own shift table:
+        `ModelEngine.one_body_density` calls in between do not disturb it.
+        Independent of the other estimators."""
+        sh = None if shifts is None else \
+            np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+        if sh is None or sh.size == 0:
+            check(self._lib.qmc_dmc_set_obdm_estimator(self._h, 0, None, 1))
+            self.obdm_shifts = None
+            return
+        self.obdm_shifts = None     # (a failed call leaves it off)
+        check(self._lib.qmc_dmc_set_obdm_estimator(
+            self._h, sh.size, ptr(sh), int(eval_stride)))
+        self.obdm_shifts = sh.copy()
+
+    def read_obdm(self, nsteps: int) -> np.ndarray:
+        """Rows of the last estimator block -> iter_obdm[nsteps, K]: per
+        evaluated time step the g1(shift_k) of the yielded walkers, summed
+        unweighted (divide by num_walkers for the mixed g1; a zero shift gives
+        num_walkers exactly); the rows of the steps in between are zero."""
+        if self.obdm_shifts is None:
+            raise QmcError('read_obdm: the one-body density estimator is not '
+                           'set')
+        return self._read_rows(self._lib.qmc_dmc_read_obdm, nsteps,
+                               (self.obdm_shifts.size,))
 
     def read_series(self, nsteps: int) -> DmcSeries:
         ser, ptrs = self._series(nsteps)

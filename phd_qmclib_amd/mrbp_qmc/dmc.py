@@ -33,7 +33,7 @@ from ..qmc_base import dmc as dmc_base
 from . import model
 
 __all__ = ['CFCSpec', 'DDFParams', 'DensityEstSpec', 'ISFEstSpec',
-           'PairDistEstSpec',
+           'OBDMEstSpec', 'PairDistEstSpec',
            'Sampling', 'SSFEstSpec', 'State', 'StateError',
            'SuperfluidEstSpec']
 
@@ -132,6 +132,35 @@ class ISFEstSpec:
     lag_stride: int = 1
 
 
+def _shift_tuple(shifts):
+    return tuple(float(s) for s in np.asarray(shifts, dtype=np.float64)
+                 .reshape(-1))
+
+
+@attr.s(auto_attribs=True, frozen=True)
+class OBDMEstSpec:
+    """One-body density matrix g1(s) as a block estimator, mixed (g1 is
+    non-local: forward walking does not apply; extrapolate with the VMC value,
+    2 DMC - VMC): 1..256 finite `shifts`, evaluated at every `eval_stride`-th
+    step of a block, the first included (one evaluation costs
+    len(shifts) N (N - 1) pair factors per walker, a time step N (N - 1) / 2
+    pair terms)."""
+    shifts: t.Tuple[float, ...] = attr.ib(converter=_shift_tuple)
+    eval_stride: int = 1
+
+    def __attrs_post_init__(self):
+        if not 1 <= len(self.shifts) <= 256:
+            raise ValueError('OBDMEstSpec: 1 to 256 shifts are needed')
+        if not all(np.isfinite(self.shifts)):
+            raise ValueError('OBDMEstSpec: the shifts must be finite')
+        stride = self.eval_stride
+        if isinstance(stride, bool) or stride != int(stride) or \
+                not 1 <= int(stride) <= 2 ** 31 - 1:
+            raise ValueError('OBDMEstSpec: eval_stride must be an integer in '
+                             '[1, 2^31 - 1]')
+        object.__setattr__(self, 'eval_stride', int(stride))
+
+
 @attr.s(auto_attribs=True, frozen=True)
 class Sampling:
     """A class to realize a DMC sampling (mrbp_qmc/dmc.py:143-160)."""
@@ -151,6 +180,8 @@ class Sampling:
     superfluid_est_spec: t.Optional[SuperfluidEstSpec] = attr.ib(
         default=None, kw_only=True)
     isf_est_spec: t.Optional[ISFEstSpec] = attr.ib(default=None, kw_only=True)
+    obdm_est_spec: t.Optional[OBDMEstSpec] = attr.ib(default=None,
+                                                     kw_only=True)
     pair_dist_est_spec: t.Optional[PairDistEstSpec] = None
 
     def __attrs_post_init__(self):
@@ -208,6 +239,14 @@ class Sampling:
             raise TypeError('the F(k, tau) spec has not been specified')
         return (np.arange(self.isf_est_spec.num_modes) * 2 * pi /
                 self.model_spec.supercell_size)
+
+    @property
+    def obdm_shifts(self) -> np.ndarray:
+        """Shifts s_k of the one-body density matrix estimator."""
+        if self.obdm_est_spec is None:
+            raise TypeError('the one-body density spec has not been '
+                            'specified')
+        return np.array(self.obdm_est_spec.shifts, dtype=np.float64)
 
     @property
     def cfc_spec(self) -> CFCSpec:
@@ -356,8 +395,12 @@ class Sampling:
         pd = self.pair_dist_est_spec
         sf = self.superfluid_est_spec
         isf = self.isf_est_spec
+        ob = self.obdm_est_spec
         with_est = not (dp.assume_none and sp.assume_none) or \
-            pd is not None or sf is not None or isf is not None
+            pd is not None or sf is not None or isf is not None or \
+            ob is not None
+        if ob is not None:
+            ens.set_obdm_estimator(ob.shifts, ob.eval_stride)
         if isf is not None:
             ens.set_isf_estimator(isf.num_modes, isf.num_lags, isf.lag_stride)
         if sf is not None:
@@ -375,7 +418,7 @@ class Sampling:
         try:
             while True:
                 iter_ssf = iter_density = iter_pair_dist = iter_cm = None
-                iter_isf = None
+                iter_isf = iter_obdm = None
                 if with_est:
                     # estimators only once the burn-in blocks are over
                     # (qmc_base/dmc.py:916, 928)
@@ -387,6 +430,8 @@ class Sampling:
                         iter_cm = ens.read_cm_diffusion(nts)
                     if isf is not None:
                         iter_isf = ens.read_isf(nts)
+                    if ob is not None:
+                        iter_obdm = ens.read_obdm(nts)
                 else:
                     ser = ens.run_block(nts)
                 props = dmc_base.PropsData(ser.energy, ser.weight,
@@ -396,7 +441,8 @@ class Sampling:
                 yield dmc_base.SamplingBlock(props, iter_density, iter_ssf,
                                              last, iter_cm_diffusion=iter_cm,
                                              iter_isf=iter_isf,
-                                             iter_pair_dist=iter_pair_dist)
+                                             iter_pair_dist=iter_pair_dist,
+                                             iter_obdm=iter_obdm)
                 block_idx += 1
         finally:
             ens.close()

@@ -14,7 +14,7 @@ from . import dmc, model
 from .vmc_exec import ModelSysConfSpec, _as_int, _opt
 
 __all__ = ['DensityEstSpec', 'ISFEstSpec', 'ModelSysConfSpec',
-           'PairDistEstSpec', 'Proc',
+           'OBDMEstSpec', 'PairDistEstSpec', 'Proc',
            'ProcInput', 'ProcResult', 'SSFEstSpec', 'SuperfluidEstSpec']
 
 ProcInputError = proc_base.ProcInputError
@@ -59,6 +59,32 @@ class ISFEstSpec:
     num_modes: int = attr.ib(converter=_as_int)
     num_lags: int = attr.ib(converter=_as_int)
     lag_stride: int = attr.ib(default=1, converter=_as_int)
+
+
+@attr.s(auto_attribs=True, frozen=True)
+class OBDMEstSpec:
+    """One-body density matrix g1(s), mixed (an extension; dmc.OBDMEstSpec):
+    num_shifts shifts spread evenly over [0, max_shift] (half the supercell
+    when not given), evaluated at every eval_stride-th step of a block."""
+    num_shifts: int = attr.ib(converter=_as_int)
+    max_shift: t.Optional[float] = attr.ib(default=None,
+                                           converter=_opt(float))
+    eval_stride: int = attr.ib(default=1, converter=_as_int)
+
+    def __attrs_post_init__(self):
+        if not 1 <= self.num_shifts <= 256:
+            raise ValueError('OBDMEstSpec: num_shifts must be in [1, 256]')
+        if self.max_shift is not None and not (
+                np.isfinite(self.max_shift) and self.max_shift > 0):
+            raise ValueError('OBDMEstSpec: max_shift must be positive')
+        if not 1 <= self.eval_stride <= 2 ** 31 - 1:
+            raise ValueError('OBDMEstSpec: eval_stride must be in '
+                             '[1, 2^31 - 1]')
+
+    def shifts(self, supercell_size) -> np.ndarray:
+        """The grid s_k = linspace(0, max_shift or L / 2, num_shifts)."""
+        top = self.max_shift or 0.5 * float(supercell_size)
+        return np.linspace(0.0, top, self.num_shifts)
 
 
 @attr.s(auto_attribs=True)
@@ -116,6 +142,7 @@ class Proc:
     pair_dist_spec: t.Optional[t.Any] = None
     superfluid_spec: t.Optional[t.Any] = None
     isf_spec: t.Optional[t.Any] = None
+    obdm_spec: t.Optional[t.Any] = None
 
     @classmethod
     def from_config(cls, config: t.Mapping):
@@ -155,9 +182,11 @@ class Proc:
                 **({} if sf_cfg is True else dict(sf_cfg)))
         isf_cfg = cfg.pop('isf_spec', None)
         isf = ISFEstSpec(**isf_cfg) if isf_cfg is not None else None
+        obdm_cfg = cfg.pop('obdm_spec', None)
+        obdm = OBDMEstSpec(**obdm_cfg) if obdm_cfg is not None else None
         return cls(model_spec=model_spec, density_spec=dens, ssf_spec=ssf,
                    pair_dist_spec=pair_dist, superfluid_spec=superfluid,
-                   isf_spec=isf, **cfg)
+                   isf_spec=isf, obdm_spec=obdm, **cfg)
 
     def as_config(self):
         return attr.asdict(self, filter=attr.filters.exclude(type(None)))
@@ -182,12 +211,20 @@ class Proc:
     def should_eval_isf(self):
         return self.isf_spec is not None
 
+    @property
+    def should_eval_obdm(self):
+        return self.obdm_spec is not None
+
     @functools.cached_property
     def sampling(self) -> dmc.Sampling:
         """dmc_exec/proc.py:336-371: the forward walking of the pure
         estimators spans one block."""
         pfw = self.num_time_steps_block
-        dens = ssf = pair_dist = isf = None
+        dens = ssf = pair_dist = isf = obdm = None
+        if self.should_eval_obdm:
+            obdm = dmc.OBDMEstSpec(
+                self.obdm_spec.shifts(self.model_spec.supercell_size),
+                self.obdm_spec.eval_stride)
         if self.should_eval_isf:
             isf = dmc.ISFEstSpec(self.isf_spec.num_modes,
                                  self.isf_spec.num_lags,
@@ -207,6 +244,7 @@ class Proc:
                             self.num_walkers_control_factor, self.rng_seed,
                             density_est_spec=dens, ssf_est_spec=ssf,
                             pair_dist_est_spec=pair_dist, isf_est_spec=isf,
+                            obdm_est_spec=obdm,
                             superfluid_est_spec=dmc.SuperfluidEstSpec()
                             if self.should_eval_superfluid else None)
 

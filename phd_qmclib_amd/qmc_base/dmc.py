@@ -98,6 +98,10 @@ class SamplingBlock(t.NamedTuple):
     #: F(k, tau) row sums per time step [nts, num_modes, num_lags + 2] (an
     #: extension: the imaginary-time density correlations), by keyword too
     iter_isf: t.Optional[np.ndarray] = None
+    #: g1(s) sums over the walkers per time step [nts, num_shifts] (an
+    #: extension: the mixed one-body density matrix; zero rows at the steps
+    #: its evaluation stride skips), by keyword too
+    iter_obdm: t.Optional[np.ndarray] = None
     #: pair histograms per time step [nts, num_bins] (an extension: g2(r))
     iter_pair_dist: t.Optional[np.ndarray] = None
 

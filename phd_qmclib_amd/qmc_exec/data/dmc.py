@@ -12,7 +12,7 @@ import numpy as np
 from ...stats import reblock
 
 __all__ = ['CMDiffusionBlocks', 'DensityBlocks', 'EnergyBlocks',
-           'ISFBlocks', 'NumWalkersBlocks',
+           'ISFBlocks', 'NumWalkersBlocks', 'OBDMBlocks',
            'PairDistBlocks', 'PropBlocks',
            'SSFBlocks', 'SSFPartBlocks',
            'PropsDataBlocks', 'PropsDataSeries', 'SamplingData', 'UnWeightedPropBlocks',
@@ -284,6 +284,45 @@ class ISFBlocks(UnWeightedPropBlocks):
 
 
 @attr.s(auto_attribs=True, frozen=True)
+class OBDMBlocks(SetPropBlocks):
+    """Mixed one-body density matrix in blocks (an extension: the reference
+    has no DMC g1): totals[num_blocks, num_shifts] holds, per kept block, the
+    sum over the evaluated time steps of iter_obdm[t] (each a sum over the
+    walkers, unweighted), weight_totals[num_blocks, 1] the number of walkers
+    of those steps.  A zero shift contributes exactly 1 per walker, so its
+    column equals the weights and g1(0) is exactly 1."""
+    totals: np.ndarray
+    weight_totals: np.ndarray
+
+    def one_body_density(self):
+        """-> (g1[num_shifts], g1_err[num_shifts]): the mean over the walkers
+        of all kept blocks and its error from the reblocking over blocks.  (A
+        column that equals the weights in every block, a zero shift, has the
+        ratio 1 with no error: the error formula is 0 / 0 there.)"""
+        with np.errstate(invalid='ignore', divide='ignore'):
+            err = np.asarray(self.mean_error, dtype=np.float64)
+        exact = np.all(np.asarray(self.totals) ==
+                       np.asarray(self.weight_totals), axis=0)
+        return self.mean, np.where(exact, 0.0, err)
+
+    def momentum_distribution(self, shifts, momenta, model_spec):
+        """-> (n[len(momenta)], n_err[len(momenta)]): the trapezoid-rule
+        transform of g1 on the non-negative increasing grid `shifts`
+        (`engine.momentum_distribution`) at the density N / L; the error adds
+        the errors of g1 in quadrature through the same weights, as if the
+        shifts were independent."""
+        from ...engine import momentum_distribution
+        g1, g1_err = self.one_body_density()
+        dens = model_spec.boson_number / model_spec.supercell_size
+        k = np.atleast_1d(np.asarray(momenta, dtype=np.float64))
+        nk = momentum_distribution(shifts, g1, k, dens)
+        # the transform is linear in g1: transform unit vectors scaled by the
+        # errors and add the squares
+        jac = momentum_distribution(shifts, np.diag(g1_err), k, dens)
+        return nk, np.sqrt((jac ** 2).sum(axis=0))
+
+
+@attr.s(auto_attribs=True, frozen=True)
 class SSFPartBlocks(SetPropBlocks):
     totals: np.ndarray
     weight_totals: np.ndarray
@@ -337,6 +376,7 @@ class PropsDataBlocks:
     # (keyword only: the positional order of the others is what it was)
     cm_diffusion: t.Optional[t.Any] = attr.ib(default=None, kw_only=True)
     isf: t.Optional[t.Any] = attr.ib(default=None, kw_only=True)
+    obdm: t.Optional[t.Any] = attr.ib(default=None, kw_only=True)
     pair_dist: t.Optional[t.Any] = None
 
 
@@ -352,6 +392,8 @@ class PropsDataSeries:
     cm_diffusion_blocks: t.Optional[np.ndarray] = None
     #: F(k, tau) row sums per block and time step [num_blocks, nts, K, T + 2]
     isf_blocks: t.Optional[np.ndarray] = None
+    #: g1(s) row sums per block and time step [num_blocks, nts, num_shifts]
+    obdm_blocks: t.Optional[np.ndarray] = None
 
     @property
     def props(self):
@@ -368,7 +410,7 @@ class SamplingData:
 # ---- HDF5 layout (qmc_exec/data/dmc.py:99-120, 192-211, 581-613, 683-735,
 # 770-793): <group>/totals [, weight_totals]; ss_factor/{fdk_sqr_abs,fdk_real,
 # fdk_imag}/...; blocks/{energy,weight,num_walkers[,density][,ss_factor]
-# [,pair_dist][,cm_diffusion][,isf]} ----
+# [,pair_dist][,cm_diffusion][,isf][,obdm]} ----
 def _export_weighted(self, group):
     group.create_dataset('totals', data=self.totals)
     group.create_dataset('weight_totals', data=self.weight_totals)
@@ -423,6 +465,8 @@ def _blocks_export(self, group):
         self.cm_diffusion.hdf5_export(group.require_group('cm_diffusion'))
     if self.isf is not None:
         self.isf.hdf5_export(group.require_group('isf'))
+    if self.obdm is not None:
+        self.obdm.hdf5_export(group.require_group('obdm'))
 
 
 def _blocks_import(cls, group):
@@ -430,6 +474,7 @@ def _blocks_import(cls, group):
     pdist = group.get('pair_dist')
     cmd = group.get('cm_diffusion')
     isf = group.get('isf')
+    obdm = group.get('obdm')
     return cls(EnergyBlocks.from_hdf5_data(group.get('energy')),
                WeightBlocks.from_hdf5_data(group.get('weight')),
                NumWalkersBlocks.from_hdf5_data(group.get('num_walkers')),
@@ -438,7 +483,9 @@ def _blocks_import(cls, group):
                None if pdist is None else PairDistBlocks.from_hdf5_data(pdist),
                cm_diffusion=None if cmd is None
                else CMDiffusionBlocks.from_hdf5_data(cmd),
-               isf=None if isf is None else ISFBlocks.from_hdf5_data(isf))
+               isf=None if isf is None else ISFBlocks.from_hdf5_data(isf),
+               obdm=None if obdm is None
+               else OBDMBlocks.from_hdf5_data(obdm))
 
 
 PropsDataBlocks.hdf5_export = _blocks_export

@@ -7,7 +7,8 @@ output:
     <group>/{vmc|dmc}/state       datasets + attributes of the last State
     <group>/{vmc|dmc}/proc_spec   attributes = Proc.as_config(); sub-groups
                                   model_spec, ssf_spec, density_spec,
-                                  pair_dist_spec, superfluid_spec, isf_spec
+                                  pair_dist_spec, superfluid_spec, isf_spec,
+                                  obdm_spec
     <group>/{vmc|dmc}/data/blocks/<property>/totals[, weight_totals]
 
 Access goes through `util.h5lite.open_file`: h5py when it is importable,
@@ -140,7 +141,7 @@ class HDF5FileHandler:
     def load_proc(self, group):
         proc_config = {'model_spec': attrs_dict(group.get('model_spec'))}
         for name in ('density_spec', 'ssf_spec', 'pair_dist_spec',
-                     'superfluid_spec', 'isf_spec'):
+                     'superfluid_spec', 'isf_spec', 'obdm_spec'):
             sub = group.get(name)
             proc_config[name] = None if sub is None else attrs_dict(sub)
         proc_config.update(attrs_dict(group))
@@ -152,7 +153,7 @@ class HDF5FileHandler:
         group.require_group('model_spec').attrs.update(
             **config.pop('model_spec'))
         for name in ('density_spec', 'ssf_spec', 'pair_dist_spec',
-                     'superfluid_spec', 'isf_spec'):
+                     'superfluid_spec', 'isf_spec', 'obdm_spec'):
             sub = config.pop(name, None)
             if sub is not None:
                 group.require_group(name).attrs.update(**sub)

@@ -72,8 +72,8 @@ def exec_vmc(proc, proc_input):
 
 def exec_dmc(proc, proc_input):
     """qmc_exec/dmc/proc.py:136-415: energy / weight / walkers series and the
-    density / S(k) / g2(r) / centre-of-mass diffusion / F(k, tau) estimators
-    of the kept blocks."""
+    density / S(k) / g2(r) / centre-of-mass diffusion / F(k, tau) / g1(s)
+    estimators of the kept blocks."""
     from ..mrbp_qmc.dmc_exec import ProcInput
     num_blocks, nts = proc.num_blocks, proc.num_time_steps_block
     keep = proc.keep_iter_data
@@ -88,6 +88,7 @@ def exec_dmc(proc, proc_input):
     pd_spec = getattr(proc, 'pair_dist_spec', None)
     sf_spec = getattr(proc, 'superfluid_spec', None)
     isf_spec = getattr(proc, 'isf_spec', None)
+    obdm_spec = getattr(proc, 'obdm_spec', None)
     blocks_iter = proc.sampling.blocks(proc_input.state, nts, burn)
     block = None
     try:
@@ -124,6 +125,16 @@ def exec_dmc(proc, proc_input):
             kc = (isf_spec.num_modes, isf_spec.num_lags + 2)
             isf_rows = np.zeros((num_blocks,) + kc)
             isf_iter = np.zeros((num_blocks, nts) + kc) if keep else None
+        # g1(s): per block the rows of the evaluated steps summed, weighed by
+        # the walkers of those steps (the walkers enter the rows unweighted,
+        # so a zero shift gives exactly 1), and the rows with keep_iter_data
+        obdm_tot = obdm_w = obdm_iter = None
+        if obdm_spec is not None:
+            ns = obdm_spec.num_shifts
+            evaluated = np.arange(nts) % obdm_spec.eval_stride == 0
+            obdm_tot = np.zeros((num_blocks, ns))
+            obdm_w = np.zeros((num_blocks, 1))
+            obdm_iter = np.zeros((num_blocks, nts, ns)) if keep else None
         pure_fac = np.ones(num_blocks)
         for b, block in enumerate(islice(blocks_iter, num_blocks)):
             p = block.iter_props
@@ -135,6 +146,11 @@ def exec_dmc(proc, proc_input):
                 isf_rows[b] = block.iter_isf[nts - 1] / p.num_walkers[nts - 1]
                 if keep:
                     isf_iter[b] = block.iter_isf
+            if obdm_tot is not None:
+                obdm_tot[b] = block.iter_obdm[evaluated].sum(axis=0)
+                obdm_w[b] = p.num_walkers[evaluated].sum()
+                if keep:
+                    obdm_iter[b] = block.iter_obdm
             if keep:
                 e[b], w[b], nw[b] = p.energy, p.weight, p.num_walkers
                 re[b], ae[b] = p.ref_energy, p.accum_energy
@@ -185,9 +201,12 @@ def exec_dmc(proc, proc_input):
         dens_blocks, ssf_blocks, pd_blocks,
         cm_diffusion=None if cm_curves is None
         else dmc_data.CMDiffusionBlocks(cm_curves),
-        isf=None if isf_rows is None else dmc_data.ISFBlocks(isf_rows))
+        isf=None if isf_rows is None else dmc_data.ISFBlocks(isf_rows),
+        obdm=None if obdm_tot is None
+        else dmc_data.OBDMBlocks(obdm_tot, obdm_w))
     data = dmc_data.SamplingData(
         blocks,
-        dmc_data.PropsDataSeries(props, ssf, pdist, cm_iter, isf_iter) if keep
+        dmc_data.PropsDataSeries(props, ssf, pdist, cm_iter, isf_iter,
+                                 obdm_iter) if keep
         else None)
     return proc.build_result(last_state, data)

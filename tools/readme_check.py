@@ -19,9 +19,13 @@ shifts, g1, g1_err = vmc.one_body_density(np.linspace(0, 32, 17))   # one-body d
 r, g2, g2_err = vmc.pair_distribution(64)                            # pair distribution function g2(r)
 dmc = mrbp_qmc.dmc.Sampling(spec, time_step=6.25e-4, max_num_walkers=4400,
                             target_num_walkers=4096, num_walkers_control_factor=0.5, rng_seed=1,
-                            pair_dist_est_spec=mrbp_qmc.dmc.PairDistEstSpec(64, pfw_num_time_steps=32))
+                            pair_dist_est_spec=mrbp_qmc.dmc.PairDistEstSpec(64, pfw_num_time_steps=32),
+                            obdm_est_spec=mrbp_qmc.dmc.OBDMEstSpec(shifts, eval_stride=16))   # mixed g1(s), every 16th step
 confs = np.zeros((4096, 2, 64)); confs[:, 0] = vmc.confs()
 for blk in islice(dmc.blocks(dmc.build_state(confs), 32, 1), 2):
     print(blk.iter_props.energy.sum() / blk.iter_props.weight.sum() / 64)
     g2_pure = blk.iter_pair_dist[-1] / blk.iter_props.num_walkers[-1]   # pure g2(r) histogram at dmc.pair_dist_bins
+    g1_dmc = blk.iter_obdm[::16].sum(axis=0) / blk.iter_props.num_walkers[::16].sum()   # mixed g1(s) (zero in the burn-in block)
+print('g1(0) =', g1_dmc[0], ' extrapolated g1(s):', 2 * g1_dmc - g1)   # 2 DMC - VMC
+assert g1_dmc[0] == 1.0
 print('README snippet OK')
