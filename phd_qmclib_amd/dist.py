@@ -41,6 +41,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .qmc_base import dmc_est
+
 __all__ = ['DistributedDmc', 'DistributedVmc', 'rebalance_plan']
 
 
@@ -164,29 +166,11 @@ class DistributedDmc:
         population lives on this rank alone whatever the process group's size
         (bench.py: the one-GPU strong-scaling reference timed by rank 0 inside
         a multi-rank run); no collective is issued."""
-        if getattr(ensemble, 'pair_dist_bins', 0):
-            raise NotImplementedError(
-                'the pair distribution estimator is single-GPU only: its '
-                'forward-walking rows are not part of the walker record that '
-                'the population rebalance moves between ranks; switch it off '
-                '(set_pair_dist_estimator(0)) for a distributed run')
-        if getattr(ensemble, 'cm_diffusion', False):
-            raise NotImplementedError(
-                'the centre-of-mass diffusion estimator is single-GPU only: '
-                'its per-walker rows are not part of the walker record that '
-                'the population rebalance moves between ranks; switch it off '
-                '(set_cm_diffusion_estimator(False)) for a distributed run')
-        if getattr(ensemble, 'isf_shape', None):
-            raise NotImplementedError(
-                'the F(k, tau) estimator is single-GPU only: '
-                'its per-walker rows are not part of the walker record that '
-                'the population rebalance moves between ranks; switch it off '
-                '(set_isf_estimator(0)) for a distributed run')
-        if getattr(ensemble, 'obdm_shifts', None) is not None:
-            raise NotImplementedError(
-                'the one-body density estimator is single-GPU only: its rows '
-                'are not yet summed across ranks; switch it off '
-                '(set_obdm_estimator(None)) for a distributed run')
+        for est in dmc_est.ESTIMATORS:
+            # (a stand-in may lack the attribute; off is 0, False or None)
+            state = est.refusal and getattr(ensemble, est.ensemble_attr, None)
+            if np.ndim(state) or state:
+                raise NotImplementedError(est.refusal)
         self.ens = ensemble
         self.n = int(num_particles)
         self.device = torch.device(device)

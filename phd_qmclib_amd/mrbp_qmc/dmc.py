@@ -13,12 +13,8 @@ reproduces the reference's branching weight, True uses the
 parent's energy.  The density / S(k) estimators (mixed and pure /
 forward-walking) run on the device after every kept
 time step and reproduce the reference's semantics, per-block resets included.
-The pair distribution g2(r) is a third such estimator and an extension (the
-reference has none): its forward walking goes through the cloning table, as
-that of S(k).  The centre-of-mass diffusion (the winding-number estimator of
-the superfluid fraction) is a fourth, an extension as well, and the
-imaginary-time density correlations F(k, tau), whose decay gives the
-excitation spectrum, are a fifth.
+The other block estimators of `qmc_base.dmc_est.ESTIMATORS` are extensions
+(the reference has none); their spec classes below say what each one is.
 """
 import typing as t
 from math import pi, sqrt
@@ -29,7 +25,7 @@ import numpy as np
 from .. import utils
 from ..engine import (DmcEnsemble, ModelEngine, pair_distribution_bins,
                       pair_distribution_norm)
-from ..qmc_base import dmc as dmc_base
+from ..qmc_base import dmc as dmc_base, dmc_est
 from . import model
 
 __all__ = ['CFCSpec', 'DDFParams', 'DensityEstSpec', 'ISFEstSpec',
@@ -100,7 +96,7 @@ class SSFEstSpec:
 class PairDistEstSpec:
     """Pair distribution g2(r) as a block estimator: `num_bins` uniform bins
     over [0, L/2] (1..256); pure (forward walking over `pfw_num_time_steps`
-    steps) or mixed."""
+    steps through the cloning table, as that of S(k)) or mixed."""
     num_bins: int
     as_pure_est: bool = True
     pfw_num_time_steps: t.Optional[int] = None
@@ -392,22 +388,12 @@ class Sampling:
         nts = int(num_time_steps_block)
         eng, ens = self._start(ini_state)
         dp, sp = self.density_params, self.ssf_params
-        pd = self.pair_dist_est_spec
-        sf = self.superfluid_est_spec
-        isf = self.isf_est_spec
-        ob = self.obdm_est_spec
-        with_est = not (dp.assume_none and sp.assume_none) or \
-            pd is not None or sf is not None or isf is not None or \
-            ob is not None
-        if ob is not None:
-            ens.set_obdm_estimator(ob.shifts, ob.eval_stride)
-        if isf is not None:
-            ens.set_isf_estimator(isf.num_modes, isf.num_lags, isf.lag_stride)
-        if sf is not None:
-            ens.set_cm_diffusion_estimator(True)
-        if pd is not None:
-            ens.set_pair_dist_estimator(pd.num_bins, pd.as_pure_est,
-                                        pd.pfw_num_time_steps)
+        # (S(k) and the density are one call of the ensemble, below)
+        others = [est for est in dmc_est.ESTIMATORS if est.enable and
+                  getattr(self, est.sampling_field) is not None]
+        with_est = not (dp.assume_none and sp.assume_none) or bool(others)
+        for est in others:
+            est.enable(ens, getattr(self, est.sampling_field))
         if not (dp.assume_none and sp.assume_none):
             ens.set_estimators(
                 0 if sp.assume_none else sp.num_modes, sp.as_pure_est,
@@ -417,21 +403,15 @@ class Sampling:
         block_idx = 0
         try:
             while True:
-                iter_ssf = iter_density = iter_pair_dist = iter_cm = None
-                iter_isf = iter_obdm = None
+                iter_ssf = iter_density = None
+                rows = {}
                 if with_est:
                     # estimators only once the burn-in blocks are over
                     # (qmc_base/dmc.py:916, 928)
                     ser, iter_ssf, iter_density = ens.run_block_est(
                         nts, block_idx >= burn_in_blocks)
-                    if pd is not None:
-                        iter_pair_dist = ens.read_pair_dist(nts)
-                    if sf is not None:
-                        iter_cm = ens.read_cm_diffusion(nts)
-                    if isf is not None:
-                        iter_isf = ens.read_isf(nts)
-                    if ob is not None:
-                        iter_obdm = ens.read_obdm(nts)
+                    rows = {est.block_field: est.read(ens, nts)
+                            for est in others}
                 else:
                     ser = ens.run_block(nts)
                 props = dmc_base.PropsData(ser.energy, ser.weight,
@@ -439,10 +419,7 @@ class Sampling:
                                            ser.accum_energy)
                 last = self._to_state(ens.get_state())
                 yield dmc_base.SamplingBlock(props, iter_density, iter_ssf,
-                                             last, iter_cm_diffusion=iter_cm,
-                                             iter_isf=iter_isf,
-                                             iter_pair_dist=iter_pair_dist,
-                                             iter_obdm=iter_obdm)
+                                             last, **rows)
                 block_idx += 1
         finally:
             ens.close()

@@ -8,7 +8,7 @@ import warnings
 import attr
 import numpy as np
 
-from ..qmc_base import dmc as dmc_base
+from ..qmc_base import dmc as dmc_base, dmc_est
 from ..qmc_exec import proc as proc_base
 from . import dmc, model
 from .vmc_exec import ModelSysConfSpec, _as_int, _opt
@@ -160,99 +160,44 @@ class Proc:
             if old in cfg:
                 cfg[new] = cfg.pop(old)
         model_spec = model.Spec(**cfg.pop('model_spec'))
-        dens_cfg = cfg.pop('density_spec', None)
-        dens = DensityEstSpec(**dens_cfg) if dens_cfg is not None else None
-        ssf_cfg = cfg.pop('ssf_spec', None)
-        ssf = None
-        if ssf_cfg is not None:
-            ssf_cfg = dict(ssf_cfg)
-            ssf_cfg.pop('pfw_num_time_steps', None)
-            ssf = SSFEstSpec(**ssf_cfg)
-        pd_cfg = cfg.pop('pair_dist_spec', None)
-        pair_dist = None
-        if pd_cfg is not None:
-            pd_cfg = dict(pd_cfg)
-            pd_cfg.pop('pfw_num_time_steps', None)
-            pair_dist = PairDistEstSpec(**pd_cfg)
-        sf_cfg = cfg.pop('superfluid_spec', None)
-        superfluid = None
-        if sf_cfg is not None and sf_cfg is not False:
-            # (no parameters: an empty mapping, or just `true`)
-            superfluid = SuperfluidEstSpec(
-                **({} if sf_cfg is True else dict(sf_cfg)))
-        isf_cfg = cfg.pop('isf_spec', None)
-        isf = ISFEstSpec(**isf_cfg) if isf_cfg is not None else None
-        obdm_cfg = cfg.pop('obdm_spec', None)
-        obdm = OBDMEstSpec(**obdm_cfg) if obdm_cfg is not None else None
-        return cls(model_spec=model_spec, density_spec=dens, ssf_spec=ssf,
-                   pair_dist_spec=pair_dist, superfluid_spec=superfluid,
-                   isf_spec=isf, obdm_spec=obdm, **cfg)
+        specs = {}
+        for est in dmc_est.ESTIMATORS:
+            kwargs = est.config_kwargs(cfg.pop(est.proc_field, None))
+            specs[est.proc_field] = None if kwargs is None else \
+                globals()[est.spec_class](**kwargs)
+        return cls(model_spec=model_spec, **specs, **cfg)
 
     def as_config(self):
         return attr.asdict(self, filter=attr.filters.exclude(type(None)))
-
-    @property
-    def should_eval_density(self):
-        return self.density_spec is not None
-
-    @property
-    def should_eval_ssf(self):
-        return self.ssf_spec is not None
-
-    @property
-    def should_eval_pair_dist(self):
-        return self.pair_dist_spec is not None
-
-    @property
-    def should_eval_superfluid(self):
-        return self.superfluid_spec is not None
-
-    @property
-    def should_eval_isf(self):
-        return self.isf_spec is not None
-
-    @property
-    def should_eval_obdm(self):
-        return self.obdm_spec is not None
 
     @functools.cached_property
     def sampling(self) -> dmc.Sampling:
         """dmc_exec/proc.py:336-371: the forward walking of the pure
         estimators spans one block."""
         pfw = self.num_time_steps_block
-        dens = ssf = pair_dist = isf = obdm = None
-        if self.should_eval_obdm:
-            obdm = dmc.OBDMEstSpec(
-                self.obdm_spec.shifts(self.model_spec.supercell_size),
-                self.obdm_spec.eval_stride)
-        if self.should_eval_isf:
-            isf = dmc.ISFEstSpec(self.isf_spec.num_modes,
-                                 self.isf_spec.num_lags,
-                                 self.isf_spec.lag_stride)
-        if self.should_eval_pair_dist:
-            pair_dist = dmc.PairDistEstSpec(self.pair_dist_spec.num_bins,
-                                            self.pair_dist_spec.as_pure_est,
-                                            pfw)
-        if self.should_eval_density:
-            dens = dmc.DensityEstSpec(self.density_spec.num_bins,
-                                      self.density_spec.as_pure_est, pfw)
-        if self.should_eval_ssf:
-            ssf = dmc.SSFEstSpec(self.ssf_spec.num_modes,
-                                 self.ssf_spec.as_pure_est, pfw)
+        specs = {}
+        for est in dmc_est.ESTIMATORS:
+            spec = getattr(self, est.proc_field)
+            specs[est.sampling_field] = None if spec is None else \
+                getattr(dmc, est.spec_class)(
+                    *est.sampling_args(spec, pfw, self.model_spec))
         return dmc.Sampling(self.model_spec, self.time_step,
                             self.max_num_walkers, self.target_num_walkers,
                             self.num_walkers_control_factor, self.rng_seed,
-                            density_est_spec=dens, ssf_est_spec=ssf,
-                            pair_dist_est_spec=pair_dist, isf_est_spec=isf,
-                            obdm_est_spec=obdm,
-                            superfluid_est_spec=dmc.SuperfluidEstSpec()
-                            if self.should_eval_superfluid else None)
+                            **specs)
 
     def build_result(self, state, data):
         return ProcResult(state, self, data)
 
     def exec(self, proc_input: ProcInput):
         return proc_base.exec_dmc(self, proc_input)
+
+
+# Proc.should_eval_density, .should_eval_ssf, .should_eval_pair_dist,
+# .should_eval_superfluid, .should_eval_isf, .should_eval_obdm
+for _est in dmc_est.ESTIMATORS:
+    setattr(Proc, 'should_eval_' + _est.proc_field[:-len('_spec')], property(
+        lambda self, _f=_est.proc_field: getattr(self, _f) is not None))
 
 
 # ---- result files + command-line application --------------------------

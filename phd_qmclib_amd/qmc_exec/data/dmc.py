@@ -9,6 +9,7 @@ import typing as t
 import attr
 import numpy as np
 
+from ...qmc_base import dmc_est
 from ...stats import reblock
 
 __all__ = ['CMDiffusionBlocks', 'DensityBlocks', 'EnergyBlocks',
@@ -409,8 +410,8 @@ class SamplingData:
 
 # ---- HDF5 layout (qmc_exec/data/dmc.py:99-120, 192-211, 581-613, 683-735,
 # 770-793): <group>/totals [, weight_totals]; ss_factor/{fdk_sqr_abs,fdk_real,
-# fdk_imag}/...; blocks/{energy,weight,num_walkers[,density][,ss_factor]
-# [,pair_dist][,cm_diffusion][,isf][,obdm]} ----
+# fdk_imag}/...; blocks/{energy,weight,num_walkers[,density][,ss_factor][,...
+# the further keys of `dmc_est.ESTIMATORS`, in that order]} ----
 def _export_weighted(self, group):
     group.create_dataset('totals', data=self.totals)
     group.create_dataset('weight_totals', data=self.weight_totals)
@@ -455,37 +456,20 @@ def _blocks_export(self, group):
     self.energy.hdf5_export(group.require_group('energy'))
     self.weight.hdf5_export(group.require_group('weight'))
     self.num_walkers.hdf5_export(group.require_group('num_walkers'))
-    if self.density is not None:
-        self.density.hdf5_export(group.require_group('density'))
-    if self.ss_factor is not None:
-        self.ss_factor.hdf5_export(group.require_group('ss_factor'))
-    if self.pair_dist is not None:
-        self.pair_dist.hdf5_export(group.require_group('pair_dist'))
-    if self.cm_diffusion is not None:
-        self.cm_diffusion.hdf5_export(group.require_group('cm_diffusion'))
-    if self.isf is not None:
-        self.isf.hdf5_export(group.require_group('isf'))
-    if self.obdm is not None:
-        self.obdm.hdf5_export(group.require_group('obdm'))
+    for est in dmc_est.ESTIMATORS:
+        est_blocks = getattr(self, est.key)
+        if est_blocks is not None:
+            est_blocks.hdf5_export(group.require_group(est.key))
 
 
 def _blocks_import(cls, group):
-    dens, ssf = group.get('density'), group.get('ss_factor')
-    pdist = group.get('pair_dist')
-    cmd = group.get('cm_diffusion')
-    isf = group.get('isf')
-    obdm = group.get('obdm')
+    est_blocks = {
+        est.key: globals()[est.blocks_class].from_hdf5_data(group.get(est.key))
+        for est in dmc_est.ESTIMATORS if group.get(est.key) is not None}
     return cls(EnergyBlocks.from_hdf5_data(group.get('energy')),
                WeightBlocks.from_hdf5_data(group.get('weight')),
                NumWalkersBlocks.from_hdf5_data(group.get('num_walkers')),
-               None if dens is None else DensityBlocks.from_hdf5_data(dens),
-               None if ssf is None else SSFBlocks.from_hdf5_data(ssf),
-               None if pdist is None else PairDistBlocks.from_hdf5_data(pdist),
-               cm_diffusion=None if cmd is None
-               else CMDiffusionBlocks.from_hdf5_data(cmd),
-               isf=None if isf is None else ISFBlocks.from_hdf5_data(isf),
-               obdm=None if obdm is None
-               else OBDMBlocks.from_hdf5_data(obdm))
+               **est_blocks)
 
 
 PropsDataBlocks.hdf5_export = _blocks_export

@@ -6,9 +6,8 @@ output:
 
     <group>/{vmc|dmc}/state       datasets + attributes of the last State
     <group>/{vmc|dmc}/proc_spec   attributes = Proc.as_config(); sub-groups
-                                  model_spec, ssf_spec, density_spec,
-                                  pair_dist_spec, superfluid_spec, isf_spec,
-                                  obdm_spec
+                                  model_spec and one per estimator spec
+                                  (ssf_spec, ...: `EST_SPEC_GROUPS`)
     <group>/{vmc|dmc}/data/blocks/<property>/totals[, weight_totals]
 
 Access goes through `util.h5lite.open_file`: h5py when it is importable,
@@ -20,6 +19,7 @@ import typing as t
 import attr
 import numpy as np
 
+from ..qmc_base import dmc_est
 from ..util import h5lite
 
 __all__ = ['HDF5FileHandler', 'HDF5FileHandlerGroupError',
@@ -27,6 +27,8 @@ __all__ = ['HDF5FileHandler', 'HDF5FileHandlerGroupError',
 
 IO_HANDLER_TYPES = ('HDF5_FILE',)
 IO_FILE_HANDLER_TYPES = ('HDF5_FILE',)
+#: sub-groups of proc_spec: the estimator specs (a VMC procedure has ssf_spec)
+EST_SPEC_GROUPS = tuple(est.proc_field for est in dmc_est.ESTIMATORS)
 
 
 class HDF5FileHandlerGroupError(ValueError):
@@ -140,8 +142,7 @@ class HDF5FileHandler:
     # -- reference: qmc_exec/io.py:157-212 ------------------------------
     def load_proc(self, group):
         proc_config = {'model_spec': attrs_dict(group.get('model_spec'))}
-        for name in ('density_spec', 'ssf_spec', 'pair_dist_spec',
-                     'superfluid_spec', 'isf_spec', 'obdm_spec'):
+        for name in EST_SPEC_GROUPS:
             sub = group.get(name)
             proc_config[name] = None if sub is None else attrs_dict(sub)
         proc_config.update(attrs_dict(group))
@@ -152,8 +153,7 @@ class HDF5FileHandler:
         config = dict(config)
         group.require_group('model_spec').attrs.update(
             **config.pop('model_spec'))
-        for name in ('density_spec', 'ssf_spec', 'pair_dist_spec',
-                     'superfluid_spec', 'isf_spec', 'obdm_spec'):
+        for name in EST_SPEC_GROUPS:
             sub = config.pop(name, None)
             if sub is not None:
                 group.require_group(name).attrs.update(**sub)

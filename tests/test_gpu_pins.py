@@ -169,6 +169,58 @@ def test_dmc_proc_exec_vs_reference(g_proc, tag):
     assert close(res.state.ref_energy, g[tag + '/last_ref_energy'])
 
 
+def _totals_bytes(blocks):
+    """Every array of a block container, as bytes."""
+    parts = [blocks] if hasattr(blocks, 'totals') else [
+        blocks.fdk_sqr_abs_part, blocks.fdk_real_part, blocks.fdk_imag_part]
+    return [np.asarray(a).tobytes() for p in parts
+            for a in (p.totals, getattr(p, 'weight_totals', None))
+            if a is not None]
+
+
+def test_dmc_proc_exec_estimators_together_and_alone():
+    """`Proc.exec` with all six block estimators on against one run per
+    estimator alone, same seed and input state: the block totals of every
+    estimator are the same bytes in both, and so are the energy block totals
+    of all seven runs (an estimator neither disturbs the walk nor another
+    estimator, and nothing above the C interface mixes their rows up)."""
+    from phd_qmclib_amd import mrbp_qmc
+    from phd_qmclib_amd.mrbp_qmc import dmc_exec
+    spec = mrbp_qmc.Spec(lattice_depth=5 * pi ** 2, lattice_ratio=1,
+                         interaction_strength=2, boson_number=16,
+                         supercell_size=16, tbf_contact_cutoff=4)
+    ests = dict(
+        density=dict(density_spec=dmc_exec.DensityEstSpec(5, False)),
+        ss_factor=dict(ssf_spec=dmc_exec.SSFEstSpec(4)),
+        pair_dist=dict(pair_dist_spec=dmc_exec.PairDistEstSpec(7)),
+        cm_diffusion=dict(superfluid_spec=dmc_exec.SuperfluidEstSpec()),
+        isf=dict(isf_spec=dmc_exec.ISFEstSpec(3, 2)),
+        obdm=dict(obdm_spec=dmc_exec.OBDMEstSpec(4, eval_stride=2)))
+
+    def proc(**specs):
+        return dmc_exec.Proc(spec, time_step=1e-3, max_num_walkers=64,
+                             target_num_walkers=48, rng_seed=21, num_blocks=3,
+                             num_time_steps_block=6, burn_in_blocks=1, **specs)
+    confs = np.zeros((48, 2, 16))
+    confs[:, 0, :] = 16 * np.random.RandomState(4).random_sample((48, 16))
+    ini = dmc_exec.ProcInput(proc().sampling.build_state(confs))
+    every = {}
+    for specs in ests.values():
+        every.update(specs)
+    full = proc(**every).exec(ini).data.blocks
+    energy = _totals_bytes(full.energy)
+    assert len(full.energy) == 3
+    for key, specs in ests.items():
+        solo = proc(**specs).exec(ini).data.blocks
+        for other in ests:
+            assert (getattr(solo, other) is None) == (other != key)
+        assert _totals_bytes(solo.energy) == energy, key
+        got, want = getattr(full, key), getattr(solo, key)
+        assert type(got) is type(want)
+        assert np.any(np.frombuffer(_totals_bytes(want)[0])), key
+        assert _totals_bytes(got) == _totals_bytes(want), key
+
+
 def test_dmc_state_data_blocks_target_quirk(g_proc):
     """qmc_base/dmc.py:974-1070: `state_data_blocks` overrides
     the target population with the initial number of walkers -- so its series
