@@ -485,6 +485,31 @@ int qmc_dmc_read_isf(qmc_dmc *d, int64_t nsteps, double *iter_out);
 int qmc_dmc_set_obdm_estimator(qmc_dmc *d, int32_t nshift,
                                const double *shifts, int64_t eval_stride);
 int qmc_dmc_read_obdm(qmc_dmc *d, int64_t nsteps, double *iter_out);
+/* Site occupation statistics as a seventh block estimator, last in launch
+ * order (an extension: the reference has none; csrc/qmc_site.h).  The lattice
+ * period is 1 and the supercell holds S = supercell_size sites; site c is well
+ * c with half a barrier (z_b / 2, z_b = 1 - z_a) on each side: particle i sits
+ * on site c_i = min((int)wrap_box(z_i + z_b / 2, L), S - 1), and n_c is the
+ * number of particles on site c.  Per time step num_occ + num_dist doubles,
+ * [occ | corr], summed over the yielded walkers: occ[n], n < num_occ, the
+ * number of sites with n_c = n (the last bin collects n_c >= num_occ - 1, so
+ * sum_n occ[n] = S per walker), and corr[d], d < num_dist, the sum over c of
+ * n_c n_{(c + d) mod S} (corr[0] = sum_c n_c^2; with num_dist = S,
+ * sum_d corr[d] = N^2 per walker).  Mixed, or pure with the per-walker rows
+ * carried through the cloning table for pfw steps and divided by
+ * min(step + 1, pfw), as the pair distribution; the operator is local and
+ * diagonal, so the pure estimate needs no extrapolation.  Every value is an
+ * integer held in a double; fp64 whatever fast_math says.  Limits:
+ * supercell_size integral, 1 <= S <= 512; num_occ >= 1, 0 <= num_dist <= S,
+ * num_occ + num_dist <= 256; pfw >= 1 when pure; num_occ = 0 switches it off
+ * (the rest is not read then).  Set on its own, as the pair distribution.
+ * read_site copies the first nsteps rows of the last estimator block to the
+ * host, iter_out[nsteps][num_occ + num_dist] (synchronises); rows of a block
+ * run with eval_estimators == 0 are zero.  Single-GPU only: the rows are not
+ * part of the walker record. */
+int qmc_dmc_set_site_estimator(qmc_dmc *d, int32_t num_occ, int32_t num_dist,
+                               int32_t pure, int64_t pfw);
+int qmc_dmc_read_site(qmc_dmc *d, int64_t nsteps, double *iter_out);
 /* The yielded ("actual") State after the last step (qmc_base/dmc.py:773-780):
  * confs[maxw][2][N], energy/weight[maxw], mask[maxw], cloning_ref[maxw];
  * scalars[5] = energy, weight, ref_energy, accum_energy, num_walkers. */

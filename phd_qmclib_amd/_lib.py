@@ -149,6 +149,9 @@ SIGNATURES = {
     'qmc_dmc_read_isf': (C.c_int, [_vp, C.c_int64, _dp]),
     'qmc_dmc_set_obdm_estimator': (C.c_int, [_vp, C.c_int32, _dp, C.c_int64]),
     'qmc_dmc_read_obdm': (C.c_int, [_vp, C.c_int64, _dp]),
+    'qmc_dmc_set_site_estimator': (C.c_int, [_vp, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int64]),
+    'qmc_dmc_read_site': (C.c_int, [_vp, C.c_int64, _dp]),
     'qmc_dmc_get_state': (C.c_int, [_vp, _dp, _dp, _dp, _u8p, _i64p, _dp]),
     'qmc_dmc_step_local': (C.c_int, [_vp, _vp]),
     'qmc_dmc_step_finish': (C.c_int, [_vp, _vp]),

@@ -299,11 +299,14 @@ struct EstArgs {
                               // its number of lags travels in pfw.  (It sits
                               // where the struct had padding: the kernel
                               // arguments of the others are laid out as before.)
+                              // The site statistics (qmc_site.h) hand their
+                              // number of occupation bins over in it.
     double scale;             // S(k): 4 / L (angle k_m z = (pi/2) * m * scale * z)
                               // density: bin size L / num_bins
-                              // g2(r), centre-of-mass diffusion: supercell
-                              // size L
+                              // g2(r), centre-of-mass diffusion, site
+                              // statistics: supercell size L
     double scale2;            // g2(r): 1 / delta = num_bins / (L / 2)
+                              // site statistics: half a barrier, z_b / 2
     // Forward walking (S(k), density, g2(r)): a pure estimator adds the
     // current step to the rows while step_idx < pfw and only transports them
     // afterwards; its per-step sum is over min(step_idx + 1, pfw) steps.

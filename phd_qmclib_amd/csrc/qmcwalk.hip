@@ -13,6 +13,7 @@
 #include "qmc_pairdist.h"
 #include "qmc_cmdiff.h"
 #include "qmc_isf.h"
+#include "qmc_site.h"
 #include "../../include/qmcwalk.h"
 #include "qmc_probe.h"
 
@@ -1765,7 +1766,7 @@ struct DmcEstSpec {
     long long pfw;
     bool aux;
     int A = 0;
-    int stride = 1;              // (F(k, tau), g1(s))
+    int stride = 1;              // (F(k, tau), g1(s); site statistics: P)
 };
 
 // One per-step estimator of a population: K modes or bins of C doubles each.
@@ -1777,7 +1778,8 @@ struct DmcEstSlot {
     int pure = 0;
     long long pfw = 1;           // forward-walking length; F(k, tau): lags
     int stride = 1;              // F(k, tau): time steps per lag; g1(s): time
-                                 // steps per evaluation
+                                 // steps per evaluation; site statistics: the
+                                 // occupation bins P of the K = P + D
     DevBuf<double> aux[2];       // [maxw][aux_row()] per-walker rows (null: none kept)
     DevBuf<double> iter;         // [steps][K][C] per-step outputs, grown on demand
     DevBuf<double> tab;          // a table of the estimator's own (g1(s): the
@@ -1809,7 +1811,8 @@ struct DmcEstSlot {
         return 0;
     }
 };
-enum { EST_SSF, EST_DENS, EST_PD, EST_CM, EST_ISF, EST_OBDM, EST_SLOTS };
+enum { EST_SSF, EST_DENS, EST_PD, EST_CM, EST_ISF, EST_OBDM, EST_SITE,
+       EST_SLOTS };
 
 struct qmc_dmc {
     qmc_engine *eng = nullptr;
@@ -1846,7 +1849,8 @@ struct qmc_dmc {
     // centre-of-mass diffusion (qmc_cmdiff.h: two sums per step, one double
     // per walker) and the imaginary-time density correlations (qmc_isf.h:
     // K modes of lags + 2 doubles), each set on its own, and the one-body
-    // density matrix (qmc_obdm.h: K shifts, its shift table in the slot)
+    // density matrix (qmc_obdm.h: K shifts, its shift table in the slot) and
+    // the site occupation statistics (qmc_site.h: K = P + D counts)
     DmcEstSlot est[EST_SLOTS];
     DevBuf<double> est_partial;     // [EST_BLOCKS][widest row]
     long long est_block_steps = 0;  // steps of the estimator block in progress
@@ -2501,6 +2505,42 @@ extern "C" int qmc_dmc_read_obdm(qmc_dmc *d, int64_t nsteps, double *iter_out)
                              "qmc_dmc_read_obdm", "one-body density");
 }
 
+// The site occupation statistics (qmc_site.h) are set on their own as well:
+// K = num_occ + num_dist counts per step, per-walker rows only when pure.  The
+// sites are the periods of the lattice, so the supercell must hold a whole
+// number of them.
+extern "C" int qmc_dmc_set_site_estimator(qmc_dmc *d, int32_t num_occ,
+                                          int32_t num_dist, int32_t pure,
+                                          int64_t pfw)
+{
+    const std::string who = "qmc_dmc_set_site_estimator: ";
+    if (!d) return fail(who + "null argument");
+    const bool on = num_occ != 0;   // (off: the unchecked rest is not read)
+    if (on) {
+        const double L = d->eng->dm.L;
+        if (!(L >= 1.0 && L <= (double)SITE_MAXS && L == std::floor(L)))
+            return fail(who + "supercell_size must be an integer in [1, 512] "
+                        "(the sites are the periods of the lattice)");
+        if (num_occ < 1 || num_dist < 0 || num_dist > (int32_t)L ||
+            (int64_t)num_occ + num_dist > EST_MAXK)
+            return fail(who + "num_occ >= 1, 0 <= num_dist <= supercell_size "
+                        "and num_occ + num_dist <= 256 are needed");
+        if (pure && pfw < 1) return fail(who + "pfw must be >= 1");
+    }
+    HIP_TRY(hipSetDevice(d->eng->device));
+    // per-walker rows only when pure: the mixed kernel keeps none
+    const DmcEstSpec spec = { on ? num_occ + num_dist : 0, 1,
+                              on && pure ? 1 : 0, on && pure ? pfw : 1,
+                              on && pure != 0, 0, on ? num_occ : 1 };
+    return dmc_set_est_slots(d, EST_SITE, 1, &spec);
+}
+
+extern "C" int qmc_dmc_read_site(qmc_dmc *d, int64_t nsteps, double *iter_out)
+{
+    return dmc_read_est_rows(d, EST_SITE, nsteps, iter_out,
+                             "qmc_dmc_read_site", "site occupation");
+}
+
 // g1(s) of the walkers of a step: lane groups of est_width(N), the dynamic LDS
 // sized from N and K (beyond the default limit at large N: allow_lds).  (The
 // caller checks the launch with the reduction that follows.)
@@ -2572,6 +2612,14 @@ static int dmc_enqueue_estimators(qmc_dmc *d, long long step_idx)
         case EST_OBDM:
             a.scale = 0.0;
             launch_dmc_obdm(e, s.tab, a);
+            break;
+        case EST_SITE:
+            a.scale = e->dm.L;
+            a.scale2 = 0.5 * (1.0 - e->dm.z_a);   // half a barrier
+            a.stride = s.stride;                  // P (qmc_site.h)
+            hipLaunchKernelGGL(dmc_site_kernel, dim3(EST_BLOCKS), dim3(BLOCK),
+                               0, e->stream, a);
+            a.stride = 1;
             break;
         default:
             a.scale = 4.0 / e->dm.L;              // as S(k)

@@ -13,7 +13,7 @@ from ._lib import (DmcEstParams, DmcParams, ModelParams, QmcError, VmcParams,
                    _i64p, _u64p, _u8p)
 
 __all__ = ['ModelEngine', 'VmcEnsemble', 'DmcEnsemble', 'EvalResult',
-           'DeviceBuffer', 'momentum_distribution',
+           'DeviceBuffer', 'momentum_distribution', 'site_statistics',
            'model_params_struct', 'QmcError']
 
 
@@ -110,6 +110,49 @@ def intermediate_scattering(iter_isf, num_walkers, boson_number, time_step,
     tau = np.arange(num_lags) * (int(lag_stride) * float(time_step))
     rho_mean = last[:, num_lags] + 1j * last[:, num_lags + 1]
     return tau, last[:, :num_lags].T / int(boson_number), rho_mean
+
+
+class SiteStatistics(t.NamedTuple):
+    """What `site_statistics` returns."""
+    #: P(n)[..., num_occ]: the share of the sites that hold n particles (the
+    #: last entry collects n >= num_occ - 1); it sums to 1
+    occupation_dist: np.ndarray
+    #: N / S
+    mean_occupation: float
+    #: <n_c^2> - (N / S)^2 [...], or None without a correlation part
+    variance: t.Optional[np.ndarray]
+    #: C(d) = <n_c n_{c+d}> - (N / S)^2 [..., num_dist]
+    correlation: np.ndarray
+
+    def number_variance(self, length):
+        """Variance of the number of particles on `length` consecutive sites,
+        sum_{|d| < length} (length - |d|) C(d) (C is even in d) -> [...];
+        it needs the distances d < length."""
+        ell = int(length)
+        if ell < 1 or ell > self.correlation.shape[-1]:
+            raise ValueError('number_variance: 1 <= length <= num_dist is '
+                             'needed')
+        w = np.full(ell, 2.0) * (ell - np.arange(ell))
+        w[0] = ell
+        return self.correlation[..., :ell] @ w
+
+
+def site_statistics(rows, num_walkers, boson_number, num_sites, num_occ):
+    """The site occupation statistics from rows[..., num_occ + num_dist] =
+    [occ | corr] (`DmcEnsemble.read_site`) summed over `num_walkers` walkers
+    (a number, or an array shaped as the leading axes of rows; for the sum of
+    the mixed rows of several steps, the summed walkers) -> SiteStatistics:
+    P(n) = occ / (S W), the mean occupation N / S, the on-site variance and the
+    connected correlation C(d) = corr[d] / (S W) - (N / S)^2."""
+    rows = np.asarray(rows, dtype=np.float64)
+    P, S = int(num_occ), int(num_sites)
+    if not 1 <= P <= rows.shape[-1]:
+        raise ValueError('site_statistics: num_occ must be in [1, row length]')
+    norm = S * np.asarray(num_walkers, dtype=np.float64)[..., np.newaxis]
+    mean = int(boson_number) / S
+    corr = rows[..., P:] / norm - mean ** 2
+    return SiteStatistics(rows[..., :P] / norm, mean,
+                          corr[..., 0] if corr.shape[-1] else None, corr)
 
 
 def momentum_distribution(shifts, g1, momenta, density):
@@ -646,6 +689,7 @@ class DmcEnsemble:
         self.cm_diffusion = False
         self.isf_shape = None
         self.obdm_shifts = None
+        self.site_shape = None
 
     def close(self):
         if getattr(self, '_h', None):
@@ -837,6 +881,30 @@ class DmcEnsemble:
                            'set')
         return self._read_rows(self._lib.qmc_dmc_read_obdm, nsteps,
                                (self.obdm_shifts.size,))
+
+    def set_site_estimator(self, num_occ, num_dist=0, pure=False, pfw=1):
+        """Enable the site occupation statistics of the estimator blocks
+        (`site_statistics`): per time step the `num_occ` counts occ[n] of the
+        sites that hold n particles (the last collects n >= num_occ - 1) and
+        the `num_dist` sums corr[d] = sum_c n_c n_{c+d} over the sites of the
+        supercell, mixed or pure with forward-walking length `pfw`.  The
+        supercell size must be an integer <= 512, num_occ >= 1,
+        0 <= num_dist <= supercell size, num_occ + num_dist <= 256;
+        num_occ = 0 disables it.  Independent of the other estimators."""
+        P, D = int(num_occ), int(num_dist)
+        check(self._lib.qmc_dmc_set_site_estimator(
+            self._h, P, D, int(bool(pure)), int(pfw)))
+        self.site_shape = (P, D) if P > 0 else None
+
+    def read_site(self, nsteps: int) -> np.ndarray:
+        """Rows of the last estimator block -> iter_site[nsteps, P + D]: per
+        time step [occ | corr] summed over the walkers (pure: the
+        forward-walking rows over min(step + 1, pfw))."""
+        if self.site_shape is None:
+            raise QmcError('read_site: the site occupation estimator is not '
+                           'set')
+        return self._read_rows(self._lib.qmc_dmc_read_site, nsteps,
+                               (sum(self.site_shape),))
 
     def read_series(self, nsteps: int) -> DmcSeries:
         ser, ptrs = self._series(nsteps)

@@ -30,7 +30,7 @@ from . import model
 
 __all__ = ['CFCSpec', 'DDFParams', 'DensityEstSpec', 'ISFEstSpec',
            'OBDMEstSpec', 'PairDistEstSpec',
-           'Sampling', 'SSFEstSpec', 'State', 'StateError',
+           'Sampling', 'SiteEstSpec', 'SSFEstSpec', 'State', 'StateError',
            'SuperfluidEstSpec']
 
 State = dmc_base.State
@@ -157,6 +157,45 @@ class OBDMEstSpec:
         object.__setattr__(self, 'eval_stride', int(stride))
 
 
+def _count(value, name):
+    if isinstance(value, bool) or value != int(value):
+        raise ValueError(f'SiteEstSpec: {name} must be an integer')
+    return int(value)
+
+
+@attr.s(auto_attribs=True, frozen=True)
+class SiteEstSpec:
+    """Site occupation statistics as a block estimator: per time step the
+    `num_occupations` counts occ[n] of the lattice sites that hold n particles
+    (the last collects n >= num_occupations - 1) and the `num_distances` sums
+    corr[d] = sum_c n_c n_{c+d} over the sites, a site being a well with half
+    a barrier on each side (`engine.site_statistics` turns them into P(n), the
+    number variance and the connected correlation).  Pure (forward walking
+    over `pfw_num_time_steps` steps through the cloning table, as that of
+    g2(r); the operator is local and diagonal, so the pure estimate is exact)
+    or mixed.  num_occupations >= 1, num_distances >= 0 and at most the
+    supercell size, which must be an integer <= 512, and num_occupations +
+    num_distances <= 256."""
+    num_occupations: int
+    num_distances: int = 0
+    as_pure_est: bool = True
+    pfw_num_time_steps: t.Optional[int] = None
+
+    def __attrs_post_init__(self):
+        P = _count(self.num_occupations, 'num_occupations')
+        D = _count(self.num_distances, 'num_distances')
+        if P < 1 or D < 0 or P + D > 256:
+            raise ValueError('SiteEstSpec: num_occupations >= 1, '
+                             'num_distances >= 0 and num_occupations + '
+                             'num_distances <= 256 are needed')
+        object.__setattr__(self, 'num_occupations', P)
+        object.__setattr__(self, 'num_distances', D)
+        if self.pfw_num_time_steps is None:
+            object.__setattr__(self, 'pfw_num_time_steps', 99999999)
+        elif _count(self.pfw_num_time_steps, 'pfw_num_time_steps') < 1:
+            raise ValueError('SiteEstSpec: pfw_num_time_steps must be >= 1')
+
+
 @attr.s(auto_attribs=True, frozen=True)
 class Sampling:
     """A class to realize a DMC sampling (mrbp_qmc/dmc.py:143-160)."""
@@ -177,6 +216,8 @@ class Sampling:
         default=None, kw_only=True)
     isf_est_spec: t.Optional[ISFEstSpec] = attr.ib(default=None, kw_only=True)
     obdm_est_spec: t.Optional[OBDMEstSpec] = attr.ib(default=None,
+                                                     kw_only=True)
+    site_est_spec: t.Optional[SiteEstSpec] = attr.ib(default=None,
                                                      kw_only=True)
     pair_dist_est_spec: t.Optional[PairDistEstSpec] = None
 

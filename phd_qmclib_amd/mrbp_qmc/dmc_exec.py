@@ -15,7 +15,8 @@ from .vmc_exec import ModelSysConfSpec, _as_int, _opt
 
 __all__ = ['DensityEstSpec', 'ISFEstSpec', 'ModelSysConfSpec',
            'OBDMEstSpec', 'PairDistEstSpec', 'Proc',
-           'ProcInput', 'ProcResult', 'SSFEstSpec', 'SuperfluidEstSpec']
+           'ProcInput', 'ProcResult', 'SiteEstSpec', 'SSFEstSpec',
+           'SuperfluidEstSpec']
 
 ProcInputError = proc_base.ProcInputError
 
@@ -87,6 +88,26 @@ class OBDMEstSpec:
         return np.linspace(0.0, top, self.num_shifts)
 
 
+@attr.s(auto_attribs=True, frozen=True)
+class SiteEstSpec:
+    """Site occupation statistics (an extension; dmc.SiteEstSpec):
+    num_occupations bins of P(n) and num_distances site distances of
+    <n_c n_{c+d}>."""
+    num_occupations: int = attr.ib(
+        converter=_as_int, validator=attr.validators.instance_of(int))
+    num_distances: int = attr.ib(
+        default=0, converter=_as_int,
+        validator=attr.validators.instance_of(int))
+    as_pure_est: bool = attr.ib(default=True, converter=bool)
+
+    def __attrs_post_init__(self):
+        P, D = self.num_occupations, self.num_distances
+        if P < 1 or D < 0 or P + D > 256:
+            raise ValueError('SiteEstSpec: num_occupations >= 1, '
+                             'num_distances >= 0 and num_occupations + '
+                             'num_distances <= 256 are needed')
+
+
 @attr.s(auto_attribs=True)
 class ProcInput:
     """dmc_exec/proc.py:100-143."""
@@ -143,6 +164,7 @@ class Proc:
     superfluid_spec: t.Optional[t.Any] = None
     isf_spec: t.Optional[t.Any] = None
     obdm_spec: t.Optional[t.Any] = None
+    site_spec: t.Optional[t.Any] = None
 
     @classmethod
     def from_config(cls, config: t.Mapping):
@@ -194,7 +216,8 @@ class Proc:
 
 
 # Proc.should_eval_density, .should_eval_ssf, .should_eval_pair_dist,
-# .should_eval_superfluid, .should_eval_isf, .should_eval_obdm
+# .should_eval_superfluid, .should_eval_isf, .should_eval_obdm,
+# .should_eval_site
 for _est in dmc_est.ESTIMATORS:
     setattr(Proc, 'should_eval_' + _est.proc_field[:-len('_spec')], property(
         lambda self, _f=_est.proc_field: getattr(self, _f) is not None))

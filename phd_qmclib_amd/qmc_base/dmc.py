@@ -102,6 +102,9 @@ class SamplingBlock(t.NamedTuple):
     #: extension: the mixed one-body density matrix; zero rows at the steps
     #: its evaluation stride skips), by keyword too
     iter_obdm: t.Optional[np.ndarray] = None
+    #: site occupation rows per time step [nts, num_occupations +
+    #: num_distances] (an extension: the site statistics), by keyword too
+    iter_site: t.Optional[np.ndarray] = None
     #: pair histograms per time step [nts, num_bins] (an extension: g2(r))
     iter_pair_dist: t.Optional[np.ndarray] = None
 

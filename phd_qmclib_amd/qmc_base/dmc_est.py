@@ -45,6 +45,12 @@ def _density_wrap(cls, totals, series, *rest):
                     None if series is None else series[..., 0], *rest)
 
 
+def _site_wrap(cls, totals, series, props, nts, keep, spec, pure_fac):
+    # (the container splits a row at the number of occupation bins)
+    return cls.from_data(nts, series if keep else totals[0], props, keep,
+                         spec.as_pure_est, pure_fac, spec.num_occupations)
+
+
 def _cm_reduce(rows, props, nts, keep, spec):
     """The curve <Y^2>(t) of the block."""
     return rows[:, 1] / props.num_walkers,
@@ -171,6 +177,22 @@ ESTIMATORS = (
         refusal='the one-body density estimator is single-GPU only: its rows '
         'are not yet summed across ranks; switch it off '
         '(set_obdm_estimator(None)) for a distributed run'),
+    Estimator(
+        'site', 'site_spec', 'site_est_spec', 'iter_site', None,
+        'SiteEstSpec', 'SiteBlocks', config_kwargs=_kwargs_no_pfw,
+        sampling_args=lambda spec, pfw, model_spec: (
+            spec.num_occupations, spec.num_distances, spec.as_pure_est, pfw),
+        row_shape=lambda spec: (spec.num_occupations + spec.num_distances,),
+        wrap=_site_wrap,
+        enable=lambda ens, s: ens.set_site_estimator(
+            s.num_occupations, s.num_distances, s.as_pure_est,
+            s.pfw_num_time_steps),
+        read=lambda ens, nts: ens.read_site(nts),
+        ensemble_attr='site_shape',
+        refusal='the site occupation estimator is single-GPU only: its '
+        'forward-walking rows are not part of the walker record that '
+        'the population rebalance moves between ranks; switch it off '
+        '(set_site_estimator(0)) for a distributed run'),
 )
 
 

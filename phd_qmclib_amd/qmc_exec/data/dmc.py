@@ -15,7 +15,7 @@ from ...stats import reblock
 __all__ = ['CMDiffusionBlocks', 'DensityBlocks', 'EnergyBlocks',
            'ISFBlocks', 'NumWalkersBlocks', 'OBDMBlocks',
            'PairDistBlocks', 'PropBlocks',
-           'SSFBlocks', 'SSFPartBlocks',
+           'SiteBlocks', 'SSFBlocks', 'SSFPartBlocks',
            'PropsDataBlocks', 'PropsDataSeries', 'SamplingData', 'UnWeightedPropBlocks',
            'WeightBlocks']
 
@@ -219,6 +219,84 @@ class PairDistBlocks(SetPropBlocks):
 
 
 @attr.s(auto_attribs=True, frozen=True)
+class SiteBlocks(SetPropBlocks):
+    """Site occupation rows in blocks (an extension: the reference has no
+    such estimator): totals[num_blocks, P + D] are sums over walkers (and, for
+    the mixed estimator, over the time steps of a block) of the integer rows
+    [occ | corr] of `engine.site_statistics`, P = `num_occupations`; the
+    weighted mean is the row of one walker, whose first P entries add up to
+    the number of sites."""
+    totals: np.ndarray
+    weight_totals: np.ndarray
+    num_occupations: int = 1
+
+    @classmethod
+    def from_data(cls, num_time_steps_block, site_data, props_data,
+                  reduce_data=True, as_pure_est=True,
+                  pure_est_reduce_factor=None, num_occupations=1):
+        return cls(*_est_totals(num_time_steps_block, site_data,
+                                props_data.weight, reduce_data, as_pure_est,
+                                pure_est_reduce_factor),
+                   num_occupations=int(num_occupations))
+
+    def __add__(self, other):
+        if not isinstance(other, SiteBlocks) or \
+                other.num_occupations != self.num_occupations:
+            return NotImplemented
+        return type(self)(
+            np.concatenate((self.totals, other.totals), axis=0),
+            np.concatenate((self.weight_totals, other.weight_totals), axis=0),
+            self.num_occupations)
+
+    def occupation_distribution(self):
+        """-> (P(n)[P], P_err[P]): the share of the sites that hold n
+        particles (the last entry collects n >= P - 1) and its error from the
+        reblocking over blocks.  The occupation counts of a walker add up to
+        the number of sites, which normalises them."""
+        P = self.num_occupations
+        occ = np.asarray(self.mean, dtype=np.float64)[:P]
+        with np.errstate(invalid='ignore', divide='ignore'):
+            err = np.asarray(self.mean_error, dtype=np.float64)[:P]
+        sites = occ.sum()
+        # (a count that is the same in every block has no scatter: the error
+        # formula is 0 / 0 there)
+        return occ / sites, np.nan_to_num(err) / sites
+
+    def site_correlation(self, model_spec):
+        """-> (C(d)[D], C_err[D]): the connected correlation
+        <n_c n_{c+d}> - (N / S)^2 of the site occupations, d = 0 .. D-1 (C(0)
+        is the on-site number variance), and its error."""
+        from ...engine import site_statistics
+        P = self.num_occupations
+        n, sites = model_spec.boson_number, int(model_spec.supercell_size)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            err = np.asarray(self.mean_error, dtype=np.float64)[P:]
+        stats = site_statistics(self.mean, 1.0, n, sites, P)
+        return stats.correlation, np.nan_to_num(err) / sites
+
+    def number_variance(self, max_len, model_spec):
+        """-> (ell[max_len], var[max_len], var_err[max_len]): the variance of
+        the number of particles on ell = 1 .. max_len consecutive sites,
+        sum_{|d| < ell} (ell - |d|) C(d) (max_len <= D); the error adds the
+        errors of C(d) in quadrature through the same weights, as if the
+        distances were independent."""
+        from ...engine import SiteStatistics
+        corr, err = self.site_correlation(model_spec)
+        max_len = int(max_len)
+        if not 1 <= max_len <= corr.shape[-1]:
+            raise ValueError('number_variance: 1 <= max_len <= num_distances '
+                             'is needed')
+        ells = np.arange(1, max_len + 1)
+        # the sum is linear in C: the same weights on the squared errors
+        var = np.array([SiteStatistics(None, 0.0, None, corr)
+                        .number_variance(ell) for ell in ells])
+        w = np.where(np.arange(max_len)[None, :] < ells[:, None],
+                     ells[:, None] - np.arange(max_len)[None, :], 0.0)
+        w[:, 1:] *= 2.0
+        return ells, var, np.sqrt((w ** 2) @ (err[:max_len] ** 2))
+
+
+@attr.s(auto_attribs=True, frozen=True)
 class CMDiffusionBlocks(UnWeightedPropBlocks):
     """Centre-of-mass diffusion curves in blocks (an extension: the reference
     has no superfluid fraction): totals[num_blocks, nts] holds, per kept block
@@ -378,6 +456,7 @@ class PropsDataBlocks:
     cm_diffusion: t.Optional[t.Any] = attr.ib(default=None, kw_only=True)
     isf: t.Optional[t.Any] = attr.ib(default=None, kw_only=True)
     obdm: t.Optional[t.Any] = attr.ib(default=None, kw_only=True)
+    site: t.Optional[t.Any] = attr.ib(default=None, kw_only=True)
     pair_dist: t.Optional[t.Any] = None
 
 
@@ -448,6 +527,19 @@ def _ssf_import(cls, group):
                SSFPartBlocks.from_hdf5_data(group.get('fdk_imag')))
 
 
+def _site_export(self, group):
+    _export_weighted(self, group)
+    group.attrs.update({'num_occupations': int(self.num_occupations)})
+
+
+def _site_import(cls, group):
+    return cls(totals=group.get('totals')[()],
+               weight_totals=group.get('weight_totals')[()],
+               num_occupations=int(group.attrs['num_occupations']))
+
+
+SiteBlocks.hdf5_export = _site_export
+SiteBlocks.from_hdf5_data = classmethod(_site_import)
 SSFBlocks.hdf5_export = _ssf_export
 SSFBlocks.from_hdf5_data = classmethod(_ssf_import)
 
