@@ -413,6 +413,23 @@ int qmc_dmc_run_block_est(qmc_dmc *d, int64_t nsteps, int eval_estimators,
 int qmc_dmc_est_begin_block(qmc_dmc *d, int64_t nsteps);
 int qmc_dmc_step_estimators(qmc_dmc *d, int64_t step_idx);
 int qmc_dmc_est_iter_dev(qmc_dmc *d, double **iter_ssf, double **iter_density);
+/* est_iter_dev for any estimator: the device address of the per-step outputs
+ * of slot `slot` ([nsteps][row_doubles] of the open block, sums over this
+ * rank's walkers) and the doubles per step; NULL and 0 for a slot that is
+ * off.  The slots, in the order in which a step evaluates them and in which
+ * their per-walker rows follow one another in a walker record: */
+enum {
+    QMC_EST_SSF = 0,            /* S(k) */
+    QMC_EST_DENSITY = 1,        /* density */
+    QMC_EST_PAIR_DIST = 2,      /* g2(r) */
+    QMC_EST_CM_DIFFUSION = 3,   /* centre-of-mass diffusion */
+    QMC_EST_ISF = 4,            /* F(k, tau) */
+    QMC_EST_OBDM = 5,           /* g1(s) */
+    QMC_EST_SITE = 6,           /* site occupation statistics */
+    QMC_EST_SLOTS = 7
+};
+int qmc_dmc_est_rows_dev(qmc_dmc *d, int32_t slot, double **rows,
+                         int64_t *row_doubles);
 /* Pair distribution g2(r) as a third block estimator (an extension: the
  * reference has none).  Per time step and bin, the pair-distance histograms
  * (as qmc_pair_dist: num_bins uniform bins over [0, L/2]) summed over the
@@ -531,7 +548,14 @@ int qmc_dmc_read_series(qmc_dmc *d, int64_t nsteps, double *energy,
  * own storage form: records are opaque between engines of one build) and,
  * when estimators are set, the
  * walker's forward-walking rows (S(k) parts [num_modes][3], density
- * [num_bins]).  export packs walkers [first, first+count) of the current
+ * [num_bins]).  After set_record_rows(d, 1) one segment follows for every
+ * other estimator that is on and keeps per-walker rows, in slot order: g2(r)
+ * when pure [num_bins], the centre-of-mass diffusion [1], F(k, tau)
+ * [num_modes][num_lags + 2], the site statistics when pure [num_occ +
+ * num_dist]; the mixed g2 / site statistics and g1(s) keep no rows and add
+ * nothing.  The switch may be set before or after the estimators: the layout
+ * is that of the slots at the time of each walker_record_size / export /
+ * import call (default off: S(k) and density rows only).  export packs walkers [first, first+count) of the current
  * population into buf_dev; import_walkers_at writes `count` records into
  * slots [first, first+count) and makes first+count the population size;
  * set_num_walkers drops the tail.  These three are stream-ordered (no host
@@ -539,6 +563,7 @@ int qmc_dmc_read_series(qmc_dmc *d, int64_t nsteps, double *energy,
  * rank).  num_walkers, import_walkers (append at the device's count) and
  * truncate (checked against it) read the device and synchronise. */
 int qmc_dmc_num_walkers(qmc_dmc *d, int64_t *nw);
+int qmc_dmc_set_record_rows(qmc_dmc *d, int32_t on);
 int qmc_dmc_walker_record_size(qmc_dmc *d, int64_t *doubles);
 int qmc_dmc_export_walkers(qmc_dmc *d, int64_t first, int64_t count,
                            double *buf_dev);

@@ -139,6 +139,9 @@ SIGNATURES = {
     'qmc_dmc_est_begin_block': (C.c_int, [_vp, C.c_int64]),
     'qmc_dmc_step_estimators': (C.c_int, [_vp, C.c_int64]),
     'qmc_dmc_est_iter_dev': (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    'qmc_dmc_est_rows_dev': (C.c_int, [_vp, C.c_int32, C.POINTER(_vp),
+                                       _i64p]),
+    'qmc_dmc_set_record_rows': (C.c_int, [_vp, C.c_int32]),
     'qmc_dmc_set_pair_dist_estimator': (C.c_int, [_vp, C.c_int32, C.c_int32,
                                                   C.c_int64]),
     'qmc_dmc_read_pair_dist': (C.c_int, [_vp, C.c_int64, _dp]),

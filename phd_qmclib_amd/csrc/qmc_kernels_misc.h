@@ -5,6 +5,7 @@
 #pragma once
 
 #include "qmc_kernels.h"
+#include "qmc_walker_record.h"
 
 struct BranchArgs {
     const double *weight;     // LOGARITHMS of the parent weights [maxw] (the
@@ -647,65 +648,7 @@ __global__ void dmc_gather_state_kernel(const double *ppos,
     confs[(s * 2 + 1) * n + li] = pdrift[p * n + i];
 }
 
-// Walker record of the population rebalance: pos[N], drift[N], label[N] (as
-// doubles), energy, weight, then the walker's forward-walking estimator rows
-// when estimators are enabled (S(k) parts [M][3], density [B]).
-struct WalkerRecArgs {
-    double *pos, *drift;
-    unsigned short *label;
-    double *energy, *weight;
-    double *eslot;                  // slot energies
-    double *ssf_aux, *dens_aux;     // current aux buffers or null
-    long long first, count;
-    int n, m3, nb;                  // particles, 3 * modes, bins
-};
-
-__device__ __forceinline__ int walker_rec_size(const WalkerRecArgs &a)
-{
-    return 3 * a.n + 2 + a.m3 + a.nb;
-}
-
-__global__ void pack_walkers_kernel(WalkerRecArgs a, double *buf)
-{
-    long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int rec = walker_rec_size(a), n = a.n;
-    if (idx >= a.count * rec) return;
-    long long s = idx / rec;
-    int j = (int)(idx % rec);
-    long long src = a.first + s;
-    double v;
-    if (j < n) v = a.pos[src * n + j];
-    else if (j < 2 * n) v = a.drift[src * n + (j - n)];
-    else if (j < 3 * n) v = (double)a.label[src * n + (j - 2 * n)];
-    else if (j == 3 * n) v = a.energy[src];
-    else if (j == 3 * n + 1) v = a.weight[src];
-    else if (j < 3 * n + 2 + a.m3) v = a.ssf_aux[src * a.m3 + (j - 3 * n - 2)];
-    else v = a.dens_aux[src * a.nb + (j - 3 * n - 2 - a.m3)];
-    buf[idx] = v;
-}
-
-__global__ void unpack_walkers_kernel(WalkerRecArgs a, const double *buf)
-{
-    long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int rec = walker_rec_size(a), n = a.n;
-    if (idx >= a.count * rec) return;
-    long long s = idx / rec;
-    int j = (int)(idx % rec);
-    long long dst = a.first + s;
-    double v = buf[idx];
-    if (j < n) a.pos[dst * n + j] = v;
-    else if (j < 2 * n) a.drift[dst * n + (j - n)] = v;
-    else if (j < 3 * n) a.label[dst * n + (j - 2 * n)] = (unsigned short)v;
-    else if (j == 3 * n) {
-        a.energy[dst] = v;
-        // the slot's previous occupant is gone: its "stale" energy (the
-        // reference's quirk D1 reads it) becomes the newcomer's own
-        a.eslot[dst] = v;
-    }
-    else if (j == 3 * n + 1) a.weight[dst] = v;
-    else if (j < 3 * n + 2 + a.m3) a.ssf_aux[dst * a.m3 + (j - 3 * n - 2)] = v;
-    else a.dens_aux[dst * a.nb + (j - 3 * n - 2 - a.m3)] = v;
-}
+// (the walker records of the population rebalance: qmc_walker_record.h)
 
 // The VMC chain records (VmcRec, qmc_kernels.h) and the compact [W] arrays
 // of the C ABI: the records into the arrays after a block (every field) ...

@@ -1813,6 +1813,12 @@ struct DmcEstSlot {
 };
 enum { EST_SSF, EST_DENS, EST_PD, EST_CM, EST_ISF, EST_OBDM, EST_SITE,
        EST_SLOTS };
+// (the header's names of the slots: qmc_dmc_est_rows_dev)
+static_assert(EST_SSF == QMC_EST_SSF && EST_DENS == QMC_EST_DENSITY &&
+              EST_PD == QMC_EST_PAIR_DIST && EST_CM == QMC_EST_CM_DIFFUSION &&
+              EST_ISF == QMC_EST_ISF && EST_OBDM == QMC_EST_OBDM &&
+              EST_SITE == QMC_EST_SITE && EST_SLOTS == QMC_EST_SLOTS,
+              "the estimator slots as include/qmcwalk.h names them");
 
 struct qmc_dmc {
     qmc_engine *eng = nullptr;
@@ -1855,6 +1861,8 @@ struct qmc_dmc {
     DevBuf<double> est_partial;     // [EST_BLOCKS][widest row]
     long long est_block_steps = 0;  // steps of the estimator block in progress
     int est_last_act = 1;           // aux buffer the last estimator step wrote
+    bool record_rows = false;       // the walker record carries every slot's
+                                    // rows, not those of S(k) / density alone
     bool any_est() const
     {
         return std::any_of(est, est + EST_SLOTS,
@@ -2736,6 +2744,21 @@ extern "C" int qmc_dmc_est_iter_dev(qmc_dmc *d, double **iter_ssf,
     return 0;
 }
 
+extern "C" int qmc_dmc_est_rows_dev(qmc_dmc *d, int32_t slot, double **rows,
+                                    int64_t *row_doubles)
+{
+    if (!d || !rows || !row_doubles)
+        return fail("qmc_dmc_est_rows_dev: null argument");
+    if (slot < 0 || slot >= EST_SLOTS)
+        return fail("qmc_dmc_est_rows_dev: no such estimator slot");
+    const DmcEstSlot &s = d->est[slot];
+    // (a slot that is off holds no buffer; one that is on has none before its
+    // first estimator block)
+    *rows = s.on() ? s.iter.get() : nullptr;
+    *row_doubles = s.on() ? (int64_t)s.row() : 0;
+    return 0;
+}
+
 extern "C" int qmc_dmc_step_local(qmc_dmc *d, double *partial_dev)
 {
     if (!d || !partial_dev) return fail("qmc_dmc_step_local: null argument");
@@ -2866,30 +2889,63 @@ extern "C" int qmc_dmc_get_state(qmc_dmc *d, double *confs, double *energy,
     return 0;
 }
 
+static_assert(REC_BASE_SEGS + EST_SLOTS <= REC_MAX_SEGS,
+              "a record segment per estimator slot");
+
+// The segment table of the walker records, from the slots as they are now.
 static WalkerRecArgs walker_rec_args(qmc_dmc *d, long long first,
                                      long long count)
 {
     WalkerRecArgs a;
-    a.pos = d->pos[d->cur]; a.drift = d->drift[d->cur];
-    a.label = d->label[d->cur];
-    a.energy = d->energy[d->cur]; a.weight = d->weight[d->cur];
+    const int n = d->eng->dm.n, cur = d->cur;
+    int k = 0, rec = 0;
+    auto add = [&](void *base, int width, int kind) {
+        a.seg[k].base = base; a.seg[k].width = width; a.seg[k].kind = kind;
+        rec += width;
+        ++k;
+    };
+    add(d->pos[cur].get(), n, REC_F64);
+    add(d->drift[cur].get(), n, REC_F64);
+    add(d->label[cur].get(), n, REC_U16);
+    a.e_off = rec;
+    add(d->energy[cur].get(), 1, REC_F64);
+    add(d->weight[cur].get(), 1, REC_F64);
+    // the rows the next estimator step reads as "previous": those of S(k) and
+    // the density always, those of the other slots with record_rows (a slot
+    // that is off or keeps no rows -- the mixed g2 and site statistics, g1 --
+    // adds nothing)
+    for (int e = 0; e < EST_SLOTS; ++e) {
+        const DmcEstSlot &s = d->est[e];
+        double *rows = s.aux[d->est_last_act].get();
+        if (!s.on() || !rows || (e > EST_DENS && !d->record_rows)) continue;
+        add(rows, (int)s.aux_row(), REC_F64);
+    }
+    for (int j = k; j < REC_MAX_SEGS; ++j) a.seg[j] = RecSeg{ nullptr, 0, 0 };
+    a.nseg = k; a.rec = rec;
     a.eslot = d->eslot;
-    // the rows the next estimator step reads as "previous" (null and no
-    // doubles for a slot that is off; the pair distribution's do not travel)
-    a.ssf_aux = d->est[EST_SSF].aux[d->est_last_act];
-    a.dens_aux = d->est[EST_DENS].aux[d->est_last_act];
     a.first = first; a.count = count;
-    a.n = d->eng->dm.n;
-    a.m3 = (int)d->est[EST_SSF].row();
-    a.nb = (int)d->est[EST_DENS].row();
     return a;
+}
+
+// One wavefront per record; enough blocks to fill the device, the rest by
+// the grid stride.
+static unsigned walker_rec_blocks(long long count)
+{
+    const long long want = (count + REC_WAVES - 1) / REC_WAVES;
+    return (unsigned)std::min<long long>(want, 4096);
+}
+
+extern "C" int qmc_dmc_set_record_rows(qmc_dmc *d, int32_t on)
+{
+    if (!d) return fail("qmc_dmc_set_record_rows: null argument");
+    d->record_rows = on != 0;
+    return 0;
 }
 
 extern "C" int qmc_dmc_walker_record_size(qmc_dmc *d, int64_t *doubles)
 {
     if (!d || !doubles) return fail("qmc_dmc_walker_record_size: null argument");
-    const WalkerRecArgs a = walker_rec_args(d, 0, 0);
-    *doubles = 3 * a.n + 2 + a.m3 + a.nb;
+    *doubles = walker_rec_args(d, 0, 0).rec;
     return 0;
 }
 
@@ -2903,9 +2959,8 @@ extern "C" int qmc_dmc_export_walkers(qmc_dmc *d, int64_t first, int64_t count,
     qmc_engine *e = d->eng;
     HIP_TRY(hipSetDevice(e->device));
     const WalkerRecArgs a = walker_rec_args(d, first, count);
-    long long tot = count * (long long)(3 * a.n + 2 + a.m3 + a.nb);
-    hipLaunchKernelGGL(pack_walkers_kernel, dim3((unsigned)((tot + 255) / 256)),
-                       dim3(256), 0, e->stream, a, buf_dev);
+    hipLaunchKernelGGL(pack_walkers_kernel, dim3(walker_rec_blocks(count)),
+                       dim3(64 * REC_WAVES), 0, e->stream, a, buf_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -2924,10 +2979,8 @@ extern "C" int qmc_dmc_import_walkers_at(qmc_dmc *d, int64_t first,
     HIP_TRY(hipSetDevice(e->device));
     d->init_weight.clear();
     const WalkerRecArgs a = walker_rec_args(d, first, count);
-    long long tot = count * (long long)(3 * a.n + 2 + a.m3 + a.nb);
-    hipLaunchKernelGGL(unpack_walkers_kernel,
-                       dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
-                       e->stream, a, buf_dev);
+    hipLaunchKernelGGL(unpack_walkers_kernel, dim3(walker_rec_blocks(count)),
+                       dim3(64 * REC_WAVES), 0, e->stream, a, buf_dev);
     // imported slots must not consume a spare normal stored for another walker
     hipLaunchKernelGGL(dmc_set_nw_kernel, dim3(1), dim3(64), 0, e->stream,
                        d->ctl, (long long)(first + count), (long long)first);

@@ -29,6 +29,15 @@ What is exchanged, and why only that:
 * The S(k) / density estimators are sums over walkers: every rank evaluates
   them on its own walkers (`step_estimators`) and the per-step rows are
   all-reduced once per block.
+* So are the per-step rows of every other block estimator (g2(r), the
+  centre-of-mass diffusion, F(k, tau), g1(s), the site statistics), the pure
+  ones included: a walker's forward-walking rows enter linearly.  With
+  `block_estimators=True` the walker record carries the per-walker rows of all
+  of them (`DmcEnsemble.set_record_rows`), so a rebalance moves a walker's
+  history with it, and `read_estimator` all-reduces a slot's rows on demand.
+  A rank's `num_walkers` series is local; the global count of step t is
+  `weight[t]` (unit weights), which `global_props` puts in its place for the
+  `dmc_est` reductions.
 
 The reference has no distributed path at all; its global cap
 `max_num_walkers` becomes a per-rank cap max_num_walkers / world here.
@@ -159,19 +168,28 @@ class DistributedDmc:
 
     def __init__(self, ensemble, num_particles: int, device,
                  rebalance_every: int = 32, imbalance_tol: float = 0.02,
-                 force_collectives: bool = False, solo: bool = False):
-        """`force_collectives` issues the per-step all-reduce even in a group
+                 force_collectives: bool = False, solo: bool = False,
+                 block_estimators: bool = False):
+        """`block_estimators`: accept an ensemble with any of the block
+        estimators of `dmc_est.ESTIMATORS` on (refused otherwise) and make its
+        walker records carry their per-walker rows; read them with
+        `read_estimator`.  `force_collectives` issues the per-step all-reduce even in a group
         of one rank (tests: the RCCL call and its stream ordering run on a
         single GPU; a one-rank all-reduce is the identity).  `solo`: the
         population lives on this rank alone whatever the process group's size
         (bench.py: the one-GPU strong-scaling reference timed by rank 0 inside
         a multi-rank run); no collective is issued."""
+        self.block_estimators = bool(block_estimators)
         for est in dmc_est.ESTIMATORS:
+            if self.block_estimators:
+                break
             # (a stand-in may lack the attribute; off is 0, False or None)
             state = est.refusal and getattr(ensemble, est.ensemble_attr, None)
             if np.ndim(state) or state:
                 raise NotImplementedError(est.refusal)
         self.ens = ensemble
+        if self.block_estimators and hasattr(ensemble, 'set_record_rows'):
+            ensemble.set_record_rows(True)
         self.n = int(num_particles)
         self.device = torch.device(device)
         self.rank, self.world = (0, 1) if solo else _world()
@@ -185,6 +203,8 @@ class DistributedDmc:
         self.walkers_moved = 0
         self.rebalances = 0
         self._inflight = []      # transfer buffers of the last rebalance
+        self._est_steps = 0      # steps of the last estimator block run
+        self._est_summed = set()     # its slots already summed over the ranks
         self._phase = None       # per-phase timings (enable_phase_timing)
 
     def _check_stream(self):
@@ -279,8 +299,12 @@ class DistributedDmc:
         """`num_steps` time steps with periodic population rebalance;
         -> the per-step series (global E_t, W_t; local walker counts), and
         with `estimators` also (iter_ssf[num_steps, M, 3] or None,
-        iter_density[num_steps, B] or None) summed over all ranks."""
+        iter_density[num_steps, B] or None) summed over all ranks.  The rows
+        of the other block estimators stay on the device until
+        `read_estimator` asks for them."""
         num_steps = int(num_steps)
+        self._est_steps = 0
+        self._est_summed.clear()
         if estimators:
             self.ens.est_begin_block(num_steps)
         for t_idx in range(num_steps):
@@ -293,8 +317,56 @@ class DistributedDmc:
                 self.ens.step_estimators(t_idx)
         if not estimators:
             return self.ens.read_series(num_steps)
+        self._est_steps = num_steps
         ssf, dens = self._reduce_estimators(num_steps)
         return self.ens.read_series(num_steps), ssf, dens
+
+    def read_estimator(self, key: str, num_steps: int) -> np.ndarray:
+        """Rows of block estimator `key` ('pair_dist', 'cm_diffusion', 'isf',
+        'obdm', 'site': the `dmc_est.ESTIMATORS` with `enable`) in the block
+        that `run_block(..., estimators=True)` has just run, summed over all
+        ranks -> [num_steps, *row shape of the table].  The all-reduce runs in
+        place on the engine's stream, once per slot and block.
+
+        The rows are plain sums over the walkers of ALL ranks, while the
+        `num_walkers` of a rank's series is local: normalise with
+        `global_props(series)`."""
+        by_key = {e.key: e for e in dmc_est.ESTIMATORS if e.enable is not None}
+        est = by_key.get(key)
+        if est is None:
+            raise KeyError(f'read_estimator: no block estimator {key!r}; '
+                           f'known: {", ".join(sorted(by_key))}')
+        num_steps = int(num_steps)
+        if not self._est_steps:
+            raise RuntimeError(
+                'read_estimator: no estimator block has run; call '
+                'run_block(num_steps, estimators=True) first')
+        if not 1 <= num_steps <= self._est_steps:
+            raise ValueError(
+                f'read_estimator: the last estimator block had '
+                f'{self._est_steps} steps, {num_steps} were asked for')
+        ptr, width = self.ens.est_rows_dev(est.slot)
+        if not ptr or not width:
+            raise RuntimeError(f'read_estimator: the {key!r} estimator is '
+                               f'not set on the ensemble')
+        # (the whole block: a second, shorter read must not sum a part again)
+        view = _wrap_f64(ptr, self._est_steps * width, self.device)
+        if self._collect and est.slot not in self._est_summed:
+            dist.all_reduce(view)               # in place, engine's stream
+            self._est_summed.add(est.slot)
+        rows = view[:num_steps * width].cpu().numpy().copy()
+        shape = tuple(est.ensemble_row_shape(self.ens))
+        return rows.reshape((num_steps,) + shape)
+
+    @staticmethod
+    def global_props(series):
+        """A copy of a rank's series whose `num_walkers` is the GLOBAL count
+        of every step: `weight[t]`, the all-reduced sum of the unit weights
+        of the yielded walkers.  With it the `reduce` functions of
+        `dmc_est.ESTIMATORS` take the rows of `read_estimator` as they take a
+        single ensemble's."""
+        return series._replace(
+            num_walkers=np.rint(series.weight).astype(np.uint64))
 
     def _reduce_estimators(self, num_steps: int):
         M = int(getattr(self.ens, 'num_modes', 0))

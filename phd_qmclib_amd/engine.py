@@ -690,6 +690,7 @@ class DmcEnsemble:
         self.isf_shape = None
         self.obdm_shifts = None
         self.site_shape = None
+        self._record_rows = False
 
     def close(self):
         if getattr(self, '_h', None):
@@ -948,7 +949,9 @@ class DmcEnsemble:
 
     def walker_record_size(self) -> int:
         """Doubles per walker record of export / import (3N + 2 + the
-        forward-walking estimator rows when estimators are set)."""
+        forward-walking rows of S(k) and the density when they are set, and
+        with `set_record_rows` those of every other estimator that keeps
+        per-walker rows)."""
         n = C.c_int64(0)
         check(self._lib.qmc_dmc_walker_record_size(self._h, C.byref(n)))
         return int(n.value)
@@ -987,3 +990,25 @@ class DmcEnsemble:
         a, b = C.c_void_p(), C.c_void_p()
         check(self._lib.qmc_dmc_est_iter_dev(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def est_rows_dev(self, slot: int):
+        """-> (device address or None, doubles per time step) of this rank's
+        per-step rows of estimator slot `slot` (`dmc_est.Estimator.slot`; the
+        QMC_EST_* of the header) in the open estimator block; (None, 0) for a
+        slot that is off."""
+        rows, width = C.c_void_p(), C.c_int64(0)
+        check(self._lib.qmc_dmc_est_rows_dev(self._h, int(slot),
+                                             C.byref(rows), C.byref(width)))
+        return rows.value, int(width.value)
+
+    def set_record_rows(self, on: bool = True):
+        """The walker records of export / import carry the per-walker rows of
+        every estimator that keeps some (pure g2, centre-of-mass diffusion,
+        F(k, tau), pure site statistics), not those of S(k) and the density
+        alone.  Before or after the estimator setters; default off."""
+        check(self._lib.qmc_dmc_set_record_rows(self._h, int(bool(on))))
+        self._record_rows = bool(on)
+
+    @property
+    def record_rows(self) -> bool:
+        return self._record_rows

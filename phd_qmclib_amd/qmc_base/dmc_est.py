@@ -69,6 +69,12 @@ def _obdm_reduce(rows, props, nts, keep, spec):
     return rows[evaluated].sum(axis=0), props.num_walkers[evaluated].sum()
 
 
+#: the closing sentence of every refusal
+_OPT_IN = ('.  Or pass block_estimators=True to DistributedDmc: the walker '
+           'record then carries the per-walker rows of every estimator, and '
+           'read_estimator returns the rows summed over the ranks')
+
+
 class Estimator(t.NamedTuple):
     """One DMC block estimator; `spec` is its `Proc` level spec."""
     #: group under blocks/ of the result file, and field of `PropsDataBlocks`
@@ -102,9 +108,18 @@ class Estimator(t.NamedTuple):
     wrap: t.Callable = lambda cls, totals, *rest: cls(*totals)
     #: `DmcEnsemble` attribute that tells it is on (a count, a flag, a shape
     #: or an array; off is 0, False or None, or no attribute at all), and why
-    #: `DistributedDmc` refuses it then (None: it works across ranks)
+    #: `DistributedDmc` refuses it then unless it was created with
+    #: `block_estimators=True` (None: it works across ranks either way)
     ensemble_attr: t.Optional[str] = None
     refusal: t.Optional[str] = None
+    #: its slot in the ensemble (the QMC_EST_* of include/qmcwalk.h):
+    #: `DmcEnsemble.est_rows_dev(slot)` gives a rank's rows on the device, and
+    #: the per-walker rows of the slots follow one another in this order in a
+    #: walker record
+    slot: t.Optional[int] = None
+    #: ensemble -> shape of one time step's row as the ensemble was set
+    #: (`row_shape` of the spec that switched it on)
+    ensemble_row_shape: t.Optional[t.Callable] = None
 
 
 #: in the order in which the groups of the result file are created
@@ -114,13 +129,13 @@ ESTIMATORS = (
         'DensityEstSpec', 'DensityBlocks',
         sampling_args=lambda spec, pfw, model_spec: (
             spec.num_bins, spec.as_pure_est, pfw),
-        row_shape=lambda spec: (spec.num_bins, 1), wrap=_density_wrap),
+        row_shape=lambda spec: (spec.num_bins, 1), wrap=_density_wrap, slot=1),
     Estimator(
         'ss_factor', 'ssf_spec', 'ssf_est_spec', 'iter_ssf', 'ssf_blocks',
         'SSFEstSpec', 'SSFBlocks', config_kwargs=_kwargs_no_pfw,
         sampling_args=lambda spec, pfw, model_spec: (
             spec.num_modes, spec.as_pure_est, pfw),
-        row_shape=lambda spec: (spec.num_modes, 3), wrap=_fw_wrap),
+        row_shape=lambda spec: (spec.num_modes, 3), wrap=_fw_wrap, slot=0),
     Estimator(
         'pair_dist', 'pair_dist_spec', 'pair_dist_est_spec', 'iter_pair_dist',
         'pair_dist_blocks', 'PairDistEstSpec', 'PairDistBlocks',
@@ -131,11 +146,12 @@ ESTIMATORS = (
         enable=lambda ens, s: ens.set_pair_dist_estimator(
             s.num_bins, s.as_pure_est, s.pfw_num_time_steps),
         read=lambda ens, nts: ens.read_pair_dist(nts),
-        ensemble_attr='pair_dist_bins',
+        ensemble_attr='pair_dist_bins', slot=2,
+        ensemble_row_shape=lambda ens: (ens.pair_dist_bins,),
         refusal='the pair distribution estimator is single-GPU only: its '
         'forward-walking rows are not part of the walker record that '
         'the population rebalance moves between ranks; switch it off '
-        '(set_pair_dist_estimator(0)) for a distributed run'),
+        '(set_pair_dist_estimator(0)) for a distributed run' + _OPT_IN),
     Estimator(
         'cm_diffusion', 'superfluid_spec', 'superfluid_est_spec',
         'iter_cm_diffusion', 'cm_diffusion_blocks', 'SuperfluidEstSpec',
@@ -145,11 +161,13 @@ ESTIMATORS = (
         enable=lambda ens, s: ens.set_cm_diffusion_estimator(True),
         read=lambda ens, nts: ens.read_cm_diffusion(nts),
         totals_shapes=lambda row, nts: ((nts,),), reduce=_cm_reduce,
-        ensemble_attr='cm_diffusion',
+        ensemble_attr='cm_diffusion', slot=3,
+        ensemble_row_shape=lambda ens: (2,),
         refusal='the centre-of-mass diffusion estimator is single-GPU only: '
         'its per-walker rows are not part of the walker record that '
         'the population rebalance moves between ranks; switch it off '
-        '(set_cm_diffusion_estimator(False)) for a distributed run'),
+        '(set_cm_diffusion_estimator(False)) for a distributed run'
+        + _OPT_IN),
     Estimator(
         'isf', 'isf_spec', 'isf_est_spec', 'iter_isf', 'isf_blocks',
         'ISFEstSpec', 'ISFBlocks',
@@ -159,11 +177,12 @@ ESTIMATORS = (
         enable=lambda ens, s: ens.set_isf_estimator(
             s.num_modes, s.num_lags, s.lag_stride),
         read=lambda ens, nts: ens.read_isf(nts),
-        reduce=_isf_reduce, ensemble_attr='isf_shape',
+        reduce=_isf_reduce, ensemble_attr='isf_shape', slot=4,
+        ensemble_row_shape=lambda ens: tuple(ens.isf_shape),
         refusal='the F(k, tau) estimator is single-GPU only: '
         'its per-walker rows are not part of the walker record that '
         'the population rebalance moves between ranks; switch it off '
-        '(set_isf_estimator(0)) for a distributed run'),
+        '(set_isf_estimator(0)) for a distributed run' + _OPT_IN),
     Estimator(
         'obdm', 'obdm_spec', 'obdm_est_spec', 'iter_obdm', 'obdm_blocks',
         'OBDMEstSpec', 'OBDMBlocks',
@@ -173,10 +192,11 @@ ESTIMATORS = (
         enable=lambda ens, s: ens.set_obdm_estimator(s.shifts, s.eval_stride),
         read=lambda ens, nts: ens.read_obdm(nts),
         totals_shapes=lambda row, nts: (row, (1,)), reduce=_obdm_reduce,
-        ensemble_attr='obdm_shifts',
+        ensemble_attr='obdm_shifts', slot=5,
+        ensemble_row_shape=lambda ens: (len(ens.obdm_shifts),),
         refusal='the one-body density estimator is single-GPU only: its rows '
         'are not yet summed across ranks; switch it off '
-        '(set_obdm_estimator(None)) for a distributed run'),
+        '(set_obdm_estimator(None)) for a distributed run' + _OPT_IN),
     Estimator(
         'site', 'site_spec', 'site_est_spec', 'iter_site', None,
         'SiteEstSpec', 'SiteBlocks', config_kwargs=_kwargs_no_pfw,
@@ -188,11 +208,12 @@ ESTIMATORS = (
             s.num_occupations, s.num_distances, s.as_pure_est,
             s.pfw_num_time_steps),
         read=lambda ens, nts: ens.read_site(nts),
-        ensemble_attr='site_shape',
+        ensemble_attr='site_shape', slot=6,
+        ensemble_row_shape=lambda ens: (sum(ens.site_shape),),
         refusal='the site occupation estimator is single-GPU only: its '
         'forward-walking rows are not part of the walker record that '
         'the population rebalance moves between ranks; switch it off '
-        '(set_site_estimator(0)) for a distributed run'),
+        '(set_site_estimator(0)) for a distributed run' + _OPT_IN),
 )
 
 
