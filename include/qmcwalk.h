@@ -87,8 +87,19 @@ typedef struct {
     int32_t fix_stale_energy;  /* 0: reference behaviour         */
     int32_t external_reduce;   /* 1: E_t/W_t are reduced across ranks by the
                                   caller between step_local and step_finish  */
-    int32_t reserved;
+    int32_t propagator;        /* QMC_DMC_LINEAR: the reference's step, error
+                                  O(dt); QMC_DMC_QUADRATIC: the symmetric
+                                  drift / diffusion split, error O(dt^2) (an
+                                  extension, csrc/qmc_evolve2.h: three pair
+                                  sums per step, fix_stale_energy without
+                                  effect, tapes of [slot][2][N] normals per
+                                  step).  Anything else: qmc_dmc_create fails.
+                                  (Was `reserved`, 0: same place and size.)
+                                  The centre-of-mass estimator's condition
+                                  |sum of displacements| < L / 2 per step holds
+                                  for either (csrc/qmc_cmdiff.h).              */
 } qmc_dmc_params;
+enum { QMC_DMC_LINEAR = 0, QMC_DMC_QUADRATIC = 1 };
 
 /* Estimator specs of a DMC sampling (mrbp_qmc/dmc.py:103-140, 187-225):
  * static structure factor over num_modes momenta k_m = 2 pi m / L and density

@@ -53,7 +53,7 @@ class DmcParams(C.Structure):
                 ('num_walkers_control_factor', C.c_double),
                 ('rng_seed', C.c_uint64), ('slot0', C.c_uint32),
                 ('fix_stale_energy', C.c_int32),
-                ('external_reduce', C.c_int32), ('reserved', C.c_int32)]
+                ('external_reduce', C.c_int32), ('propagator', C.c_int32)]
 
 
 class DmcEstParams(C.Structure):

@@ -1,0 +1,4 @@
+// Explicit instantiations of the second-order DMC step (qmc_evolve2.h),
+// translation unit E2_16; see qmc_inst.h.
+#include "qmc_inst.h"
+QMC_TU_E2_16(QMC_NO_KW)

@@ -340,6 +340,23 @@ struct LaunchEvolve {
     }
 };
 
+// The second-order step (qmc_evolve2.h): the same arguments, two more rows of
+// LDS per walker.
+template <int G, int P, bool PAD, bool ZC>
+struct LaunchEvolve2 {
+    static int run(const qmc_engine *e, const EvolveArgs &a)
+    {
+        ProfScope prof(e);
+        const size_t lds = (size_t)(WalkBlock<G>::N / G) *
+                           Step2Lds<G, P, PAD, ZC>::DOUBLES * sizeof(double);
+        return with_pair_type<G, ZC>(e, [&](auto r) {
+            return launch_walkers<G>(
+                e, dmc_evolve2_kernel<G, P, PAD, ZC, decltype(r)>, lds, a.maxw,
+                a);
+        });
+    }
+};
+
 // -------------------------------------------------------------- engine ----
 static void build_dev_model(const qmc_model_params &p, DevModel &d)
 {
@@ -1919,6 +1936,9 @@ extern "C" int qmc_dmc_create(qmc_engine *e, const qmc_dmc_params *p,
     if (p->max_num_walkers <= 0 || p->target_num_walkers <= 0)
         return fail("qmc_dmc_create: walker counts must be positive");
     if (!(p->time_step > 0)) return fail("qmc_dmc_create: time_step <= 0");
+    if (p->propagator != QMC_DMC_LINEAR && p->propagator != QMC_DMC_QUADRATIC)
+        return fail("qmc_dmc_create: unknown propagator (0: linear, "
+                    "1: second order)");
     HIP_TRY(hipSetDevice(e->device));
     std::unique_ptr<qmc_dmc> d(new qmc_dmc());
     d->eng = e;
@@ -1934,7 +1954,8 @@ extern "C" int qmc_dmc_create(qmc_engine *e, const qmc_dmc_params *p,
             return 1;
     // (the cached second Box-Muller normal: one particle per lane only,
     // qmc_kernels.h: DmcSpare)
-    const bool need_spare = e->P == 1;
+    // (the second-order step uses both normals of a block at once: no cache)
+    const bool need_spare = e->P == 1 && p->propagator == QMC_DMC_LINEAR;
     if (d->eslot.alloc(W) || (need_spare && d->spare.alloc(W * n)) ||
         d->ref.alloc(W) || d->count.alloc(W) ||
         d->block_tot.alloc(d->nblocks) || d->block_off.alloc(d->nblocks) ||
@@ -2143,8 +2164,10 @@ extern "C" int qmc_dmc_set_tape(qmc_dmc *d, const double *u, int64_t nu,
     d->tape_step = 0;
     if (!u || !g || nsteps <= 0) return 0;
     // pad so that a step may read up to maxw uniforms / maxw*N normals
+    // (the second-order step: [slot][2][N], two rows per walker)
+    const size_t rows = d->p.propagator == QMC_DMC_QUADRATIC ? 2 : 1;
     size_t upad = (size_t)nu + (size_t)d->maxw;
-    size_t gpad = (size_t)ng + (size_t)d->maxw * (size_t)d->eng->dm.n;
+    size_t gpad = (size_t)ng + rows * (size_t)d->maxw * (size_t)d->eng->dm.n;
     if (d->u_tape.alloc(upad) || d->g_tape.alloc(gpad)) return 1;
     HIP_TRY(hipMemset(d->u_tape, 0, upad * sizeof(double)));
     HIP_TRY(hipMemset(d->g_tape, 0, gpad * sizeof(double)));
@@ -2238,6 +2261,11 @@ static int dmc_enqueue_local(qmc_dmc *d, double *partial_dev,
     a.sigma = sqrt(2 * d->p.time_step);           // mrbp_qmc/dmc.py:178
     a.seed = d->p.rng_seed; a.slot0 = d->p.slot0;
     a.fix_stale = d->p.fix_stale_energy;
+    if (d->p.propagator == QMC_DMC_QUADRATIC) {
+        // two half diffusions of spread sqrt(dt) each around the drift
+        a.sigma = sqrt(d->p.time_step);
+        return dispatch_shape<LaunchEvolve2>(e, a);
+    }
     int rc = dispatch_shape<LaunchEvolve>(e, a);
     if (rc) return rc;
     return 0;

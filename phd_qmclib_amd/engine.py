@@ -664,14 +664,42 @@ class DmcSeries(t.NamedTuple):
     accum_energy: np.ndarray
 
 
+#: DmcEnsemble(propagator=...) -> qmc_dmc_params.propagator
+DMC_PROPAGATORS = {'linear': 0, 'quadratic': 1}
+
+
+def dmc_propagator_code(name) -> int:
+    """The C ABI's code of a propagator name; ValueError for an unknown one."""
+    if not isinstance(name, str) or name not in DMC_PROPAGATORS:
+        raise ValueError(f'unknown DMC propagator {name!r}: one of '
+                         f'{sorted(DMC_PROPAGATORS)}')
+    return DMC_PROPAGATORS[name]
+
+
 class DmcEnsemble:
-    """A walker population resident on the GPU (qmc_dmc)."""
+    """A walker population resident on the GPU (qmc_dmc).
+
+    `propagator`: 'linear' -- the reference's step z' = wrap(z + 2 F dt +
+    sqrt(2 dt) g), time-step error O(dt) -- or 'quadratic', an extension: the
+    symmetric split half diffusion, drift (RK2 through the midpoint), half
+    diffusion, with the branching weight averaged over the PARENT's and the
+    child's energy, error O(dt^2), three pair sums per step
+    (csrc/qmc_evolve2.h).  `fix_stale_energy` has no effect with 'quadratic':
+    the stale-slot average would break the symmetry the order
+    rests on.  Both normals of a particle's Philox block move it in ONE step
+    (the block is keyed with the step counter t, not t >> 1); a replay tape
+    holds [slot][2][N] normals per step.  The centre-of-mass estimator's
+    condition |sum of displacements| < L / 2 per step (csrc/qmc_cmdiff.h)
+    holds for either propagator: mind it at the longer steps this one
+    allows."""
 
     def __init__(self, engine: ModelEngine, time_step: float,
                  max_num_walkers: int, target_num_walkers: int,
                  num_walkers_control_factor: float, rng_seed: int,
                  slot0: int = 0, fix_stale_energy: bool = False,
-                 external_reduce: bool = False):
+                 external_reduce: bool = False, propagator: str = 'linear'):
+        self.propagator = propagator
+        code = dmc_propagator_code(propagator)
         self.engine = engine
         self._lib = engine._lib
         self.max_num_walkers = int(max_num_walkers)
@@ -680,7 +708,7 @@ class DmcEnsemble:
                       float(time_step), float(num_walkers_control_factor),
                       int(rng_seed) & 0xFFFFFFFFFFFFFFFF, int(slot0),
                       int(bool(fix_stale_energy)), int(bool(external_reduce)),
-                      0)
+                      code)
         h = C.c_void_p()
         check(self._lib.qmc_dmc_create(engine._h, C.byref(p), C.byref(h)))
         self._h = h

@@ -10,7 +10,10 @@ round trip and only the per-step series come back.
 `jit_fastmath` selects the engine's reduced-precision pair loop (float), as in
 the reference only together with `jit_parallel`.  `fix_stale_energy` is an extension: False
 reproduces the reference's branching weight, True uses the
-parent's energy.  The density / S(k) estimators (mixed and pure /
+parent's energy.  `propagator` is an extension too: 'linear' is the
+reference's step, 'quadratic' the symmetric drift / diffusion split with error
+O(dt^2) (`engine.DmcEnsemble`; `fix_stale_energy` has no effect with it).
+The density / S(k) estimators (mixed and pure /
 forward-walking) run on the device after every kept
 time step and reproduce the reference's semantics, per-block resets included.
 The other block estimators of `qmc_base.dmc_est.ESTIMATORS` are extensions
@@ -23,8 +26,8 @@ import attr
 import numpy as np
 
 from .. import utils
-from ..engine import (DmcEnsemble, ModelEngine, pair_distribution_bins,
-                      pair_distribution_norm)
+from ..engine import (DmcEnsemble, ModelEngine, dmc_propagator_code,
+                      pair_distribution_bins, pair_distribution_norm)
 from ..qmc_base import dmc as dmc_base, dmc_est
 from . import model
 
@@ -219,9 +222,11 @@ class Sampling:
                                                      kw_only=True)
     site_est_spec: t.Optional[SiteEstSpec] = attr.ib(default=None,
                                                      kw_only=True)
+    propagator: str = attr.ib(default='linear', kw_only=True)
     pair_dist_est_spec: t.Optional[PairDistEstSpec] = None
 
     def __attrs_post_init__(self):
+        dmc_propagator_code(self.propagator)    # (ValueError if unknown)
         if self.rng_seed is None:
             object.__setattr__(self, 'rng_seed',
                                int(utils.get_random_rng_seed()))
@@ -348,7 +353,8 @@ class Sampling:
                           else self.target_num_walkers,
                           self.num_walkers_control_factor, self.rng_seed,
                           slot0=slot0, fix_stale_energy=self.fix_stale_energy,
-                          external_reduce=external_reduce)
+                          external_reduce=external_reduce,
+                          propagator=self.propagator)
         return eng, ens
 
     def _to_state(self, s) -> State:

@@ -9,6 +9,7 @@ import attr
 import numpy as np
 
 from ..qmc_base import dmc as dmc_base, dmc_est
+from ..engine import dmc_propagator_code
 from ..qmc_exec import proc as proc_base
 from . import dmc, model
 from .vmc_exec import ModelSysConfSpec, _as_int, _opt
@@ -165,6 +166,13 @@ class Proc:
     isf_spec: t.Optional[t.Any] = None
     obdm_spec: t.Optional[t.Any] = None
     site_spec: t.Optional[t.Any] = None
+    #: 'linear' (the reference's step) or 'quadratic' (dmc.Sampling); a
+    #: config or result file without the attribute means 'linear'
+    propagator: str = attr.ib(default='linear')
+
+    @propagator.validator
+    def _known_propagator(self, attribute, value):
+        dmc_propagator_code(value)              # (ValueError if unknown)
 
     @classmethod
     def from_config(cls, config: t.Mapping):
@@ -190,7 +198,13 @@ class Proc:
         return cls(model_spec=model_spec, **specs, **cfg)
 
     def as_config(self):
-        return attr.asdict(self, filter=attr.filters.exclude(type(None)))
+        """(`propagator` appears only when it is not the default: the config
+        of a linear procedure, and the proc_spec of its result file, are what
+        they were before the option existed.)"""
+        cfg = attr.asdict(self, filter=attr.filters.exclude(type(None)))
+        if cfg['propagator'] == 'linear':
+            del cfg['propagator']
+        return cfg
 
     @functools.cached_property
     def sampling(self) -> dmc.Sampling:
@@ -206,7 +220,7 @@ class Proc:
         return dmc.Sampling(self.model_spec, self.time_step,
                             self.max_num_walkers, self.target_num_walkers,
                             self.num_walkers_control_factor, self.rng_seed,
-                            **specs)
+                            propagator=self.propagator, **specs)
 
     def build_result(self, state, data):
         return ProcResult(state, self, data)
