@@ -66,14 +66,20 @@ typedef struct {
 } qmc_model_params;
 
 /* mrbp_qmc/vmc.py:29-38 (TPFParams) + Sampling fields :70-80; `gaussian`
- * selects the vmc_ndf proposal (mrbp_qmc/vmc_ndf.py:23-51, move_spread =
- * sigma = sqrt(time_step)). */
+ * is the proposal code: QMC_VMC_UNIFORM, the reference's all-particle move;
+ * QMC_VMC_GAUSSIAN, the vmc_ndf proposal (mrbp_qmc/vmc_ndf.py:23-51,
+ * move_spread = sigma = sqrt(time_step)); QMC_VMC_PARTICLE, an extension: one
+ * yield is a sweep of N single-particle Metropolis moves in label order
+ * (csrc/qmc_vmc_sweep.h: word 0 of a particle's move block displaces it, word
+ * 1 is that move's accept draw; num_accepted counts particle moves; no tape).
+ * Anything else: qmc_vmc_create fails. */
+enum { QMC_VMC_UNIFORM = 0, QMC_VMC_GAUSSIAN = 1, QMC_VMC_PARTICLE = 2 };
 typedef struct {
     int64_t num_chains;
     double move_spread;
     uint64_t rng_seed;
     uint32_t chain0;      /* Philox slot of chain 0 (rank offset)          */
-    int32_t gaussian;
+    int32_t gaussian;     /* QMC_VMC_* */
 } qmc_vmc_params;
 
 /* mrbp_qmc/dmc.py:143-185 (Sampling fields + DDFParams) */

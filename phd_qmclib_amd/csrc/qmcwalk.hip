@@ -14,6 +14,7 @@
 #include "qmc_cmdiff.h"
 #include "qmc_isf.h"
 #include "qmc_site.h"
+#include "qmc_vmc_sweep.h"
 #include "../../include/qmcwalk.h"
 #include "qmc_probe.h"
 
@@ -182,6 +183,8 @@ static int pick_shape(int n, int &G, int &P, bool &pad)
 #define QMC_EXTERN_TU(name) QMC_TU_##name(extern)
 QMC_FOR_ALL_TUS(QMC_EXTERN_TU)
 #undef QMC_EXTERN_TU
+// (the single-particle sweeps, qmc_vmc_sweep.h: inst_SWEEP.hip)
+QMC_TU_SWEEP(extern)
 
 // ------------------------------------------------------------ dispatch ----
 // The masked variant is also the leaner one in registers (its per-pair guards
@@ -324,6 +327,21 @@ struct LaunchVmc {
                                  : vmc_step_kernel<G, P, PAD, ZC, false, R, false>;
             return launch_walkers<G>(e, kernel, lds, a.W, a);
         });
+    }
+};
+
+// The single-particle sweeps (qmc_vmc_sweep.h): every yield of a block in one
+// launch, fp64 whatever fast_math says; the proposals and the by-label tables
+// of a chain behind the LDS region of the pair sums.
+template <int G, int P, bool PAD, bool ZC>
+struct LaunchSweep {
+    static int run(const qmc_engine *e, const VmcArgs &a)
+    {
+        ProfScope prof(e);
+        const size_t lds = (size_t)(WalkBlock<G>::N / G) *
+                           SweepLds<G, P, PAD, ZC>::DOUBLES * sizeof(double);
+        return launch_walkers<G>(e, vmc_sweep_kernel<G, P, PAD, ZC>, lds, a.W,
+                                 a);
     }
 };
 
@@ -1190,6 +1208,9 @@ extern "C" int qmc_vmc_create(qmc_engine *e, const qmc_vmc_params *p,
 {
     if (!e || !p || !out) return fail("qmc_vmc_create: null argument");
     if (p->num_chains <= 0) return fail("qmc_vmc_create: num_chains <= 0");
+    if (p->gaussian != QMC_VMC_UNIFORM && p->gaussian != QMC_VMC_GAUSSIAN &&
+        p->gaussian != QMC_VMC_PARTICLE)
+        return fail("qmc_vmc_create: unknown proposal code");
     HIP_TRY(hipSetDevice(e->device));
     std::unique_ptr<qmc_vmc> v(new qmc_vmc());
     v->eng = e;
@@ -1272,6 +1293,9 @@ extern "C" int qmc_vmc_get_state(qmc_vmc *v, double *pos, double *wf,
 extern "C" int qmc_vmc_set_tape(qmc_vmc *v, const double *tape, int64_t steps)
 {
     if (!v) return fail("qmc_vmc_set_tape: null argument");
+    // (the sweep's stream is restated exactly: nothing to replay)
+    if (v->p.gaussian == QMC_VMC_PARTICLE)
+        return fail("qmc_vmc_set_tape: no tape with single-particle sweeps");
     qmc_engine *e = v->eng;
     HIP_TRY(hipSetDevice(e->device));
     v->tape.release();
@@ -1735,7 +1759,20 @@ extern "C" int qmc_vmc_run_block(qmc_vmc *v, int64_t nyield, double *sum_e,
     a.gaussian = v->p.gaussian;
     a.chain0 = v->p.chain0;
     a.seed = v->p.rng_seed; a.move_spread = v->p.move_spread;
-    for (long long y = 0; y < nyield;) {
+    if (v->p.gaussian == QMC_VMC_PARTICLE) {
+        // single-particle sweeps: the whole block in one launch
+        a.y = 0;
+        a.forced = v->yield_initial ? 1 : 0;
+        a.reset_sums = 1;
+        a.step = v->step;
+        a.tape = nullptr; a.tape_steps = 0; a.tape_idx = 0;
+        a.nsteps = (unsigned int)nyield;
+        int rc = dispatch_shape<LaunchSweep>(e, a);
+        if (rc) return rc;
+        v->step += (unsigned int)real;
+    }
+    for (long long y = (v->p.gaussian == QMC_VMC_PARTICLE) ? nyield : 0;
+         y < nyield;) {
         a.y = y;
         a.forced = (y == 0 && v->yield_initial) ? 1 : 0;
         a.reset_sums = (y == 0) ? 1 : 0;

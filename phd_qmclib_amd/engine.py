@@ -13,7 +13,8 @@ from ._lib import (DmcEstParams, DmcParams, ModelParams, QmcError, VmcParams,
                    _i64p, _u64p, _u8p)
 
 __all__ = ['ModelEngine', 'VmcEnsemble', 'DmcEnsemble', 'EvalResult',
-           'DeviceBuffer', 'momentum_distribution', 'site_statistics',
+           'vmc_move_code', 'DeviceBuffer', 'momentum_distribution',
+           'site_statistics',
            'model_params_struct', 'QmcError']
 
 
@@ -519,19 +520,47 @@ class ModelEngine:
                                               sums_ptr, wsum_ptr))
 
 
+#: VmcEnsemble(move=...) -> qmc_vmc_params.gaussian (the proposal code;
+#: 1 is the Gaussian all-particle proposal, `gaussian=True`)
+VMC_MOVES = {'all': 0, 'particle': 2}
+
+
+def vmc_move_code(name) -> int:
+    """The C ABI's code of a move type; ValueError for an unknown one."""
+    if not isinstance(name, str) or name not in VMC_MOVES:
+        raise ValueError(f'unknown VMC move {name!r}: one of '
+                         f'{sorted(VMC_MOVES)}')
+    return VMC_MOVES[name]
+
+
 class VmcEnsemble:
-    """W independent Metropolis chains resident on the GPU (qmc_vmc)."""
+    """W independent Metropolis chains resident on the GPU (qmc_vmc).
+
+    `move`: 'all' -- the reference's step, every particle displaced at once
+    -- or 'particle', an extension: one yield is a SWEEP of N single-particle
+    Metropolis moves in label order (the label is the particle's index in the
+    rows of `set_state`), each within +- move_spread / 2 and each accepted or
+    rejected on its own (csrc/qmc_vmc_sweep.h).  Word 0 of a particle's Philox
+    move block displaces it, word 1 of the same block is that move's accept
+    draw.  The yielded log|psi| and energy are those of the configuration after
+    the sweep, `num_accepted` counts accepted particle moves (the initial yield
+    counts N) and `move_stat` says whether any move of the sweep was accepted.
+    No tape, no Gaussian proposal, fp64 whatever `set_fast_math` says."""
 
     def __init__(self, engine: ModelEngine, num_chains: int,
                  move_spread: float, rng_seed: int, chain0: int = 0,
-                 gaussian: bool = False):
+                 gaussian: bool = False, move: str = 'all'):
+        code = vmc_move_code(move)
+        if code and gaussian:
+            raise ValueError("move='particle' has no Gaussian proposal")
+        self.move = move
         self.engine = engine
         self._lib = engine._lib
         self.num_chains = int(num_chains)
         self.num_particles = engine.num_particles
         p = VmcParams(self.num_chains, float(move_spread),
                       int(rng_seed) & 0xFFFFFFFFFFFFFFFF, int(chain0),
-                      int(bool(gaussian)))
+                      code or int(bool(gaussian)))
         h = C.c_void_p()
         check(self._lib.qmc_vmc_create(engine._h, C.byref(p), C.byref(h)))
         self._h = h

@@ -254,7 +254,9 @@ class NDFSampling(Sampling):
 class EnsembleSampling:
     """W independent VMC chains advanced together on one GPU (extension of the
     reference's single-chain sampling: every chain is statistically the chain
-    `Sampling` generates, with Philox stream = global chain index)."""
+    `Sampling` generates, with Philox stream = global chain index).
+    `move='particle'`: a yield is a sweep of N single-particle moves instead
+    (`engine.VmcEnsemble`)."""
 
     model_spec: model.Spec
     move_spread: float
@@ -263,6 +265,7 @@ class EnsembleSampling:
     first_chain: int = 0          # global index of chain 0 (multi-GPU shard)
     device: t.Optional[int] = None
     stream: t.Optional[int] = None
+    move: str = 'all'
 
     def __attrs_post_init__(self):
         if self.rng_seed is None:
@@ -271,7 +274,7 @@ class EnsembleSampling:
                                   stream=self.stream)
         self.ensemble = VmcEnsemble(self.engine, self.num_chains,
                                     self.move_spread, self.rng_seed,
-                                    chain0=self.first_chain)
+                                    chain0=self.first_chain, move=self.move)
 
     def set_confs(self, pos):
         """pos[W, N] initial positions (log|psi| is evaluated on the device)."""
@@ -285,10 +288,11 @@ class EnsembleSampling:
 
     def blocks(self, num_steps_block: int) -> t.Iterator[vmc_base.EnsembleBlock]:
         ns = int(num_steps_block)
+        moves = self.model_spec.boson_number if self.move == 'particle' else 1
         while True:
             out = self.ensemble.run_block(ns)
             yield vmc_base.EnsembleBlock(out['sum_energy'], out['sum_energy2'],
-                                         out['num_accepted'], ns)
+                                         out['num_accepted'], ns, moves)
 
     def confs(self):
         """Current positions of every chain, [W, N] (VMC -> DMC hand-off)."""

@@ -80,6 +80,7 @@ class EnsembleBlock(t.NamedTuple):
     sum_energy2: np.ndarray       # [W]
     num_accepted: np.ndarray      # [W]
     num_steps: int
+    moves_per_step: int = 1       # N for single-particle sweeps
 
     @property
     def energy(self):
@@ -88,4 +89,4 @@ class EnsembleBlock(t.NamedTuple):
 
     @property
     def accept_rate(self):
-        return self.num_accepted / self.num_steps
+        return self.num_accepted / (self.num_steps * self.moves_per_step)
