@@ -318,6 +318,39 @@ int qmc_pair_dist_reduce_dev(qmc_engine *eng, int64_t nconf,
                              int32_t num_bins, double *sums_dev,
                              double *wsum_dev);
 
+/* Three-body distribution g3(d): per configuration the histogram of the spans
+ * of the N (N - 1) (N - 2) / 6 particle triples on the ring of length L.  The
+ * span of a triple is the shortest arc that holds its three (wrapped)
+ * positions, L minus the largest of the three gaps between them, in
+ * [0, 2 L / 3].  num_bins uniform bins of width delta = max_span / num_bins
+ * cover [0, max_span), 0 < max_span <= L/2: a span d < max_span counts in
+ * bin min(floor(d / delta), num_bins - 1), every other one in the overflow bin
+ * num_bins.  counts[nconf][num_bins + 1]; every row adds up to
+ * N (N - 1) (N - 2) / 6 (all zeros for N < 3), and
+ * g3(d_b) = counts[b] / (C(N,3) 3 (delta/L)^2 (2 b + 1)) at
+ * d_b = (b + 1/2) delta is 1 on average for uncorrelated uniform particles.
+ * Positions outside [0, L) are brought into the box first; the particle order
+ * is irrelevant.  Always fp64: qmc_engine_set_fast_math does not apply
+ * (csrc/qmc_tripledist.h).
+ * qmc_triple_dist: host buffers, synchronous; a NULL pos / counts, num_bins
+ * outside [1, 4096] or max_span outside (0, L/2] is an error. */
+int qmc_triple_dist(qmc_engine *eng, int64_t nconf, const double *pos,
+                    int32_t num_bins, double max_span, uint32_t *counts);
+/* Same on device-resident buffers, asynchronous on the engine's stream. */
+int qmc_triple_dist_dev(qmc_engine *eng, int64_t nconf, const double *pos_dev,
+                        int32_t num_bins, double max_span,
+                        uint32_t *counts_dev);
+/* Weighted sums over the configurations, device buffers, asynchronous:
+ * sums_dev[num_bins + 1][2] = sum_c w_c T_c[b], sum_c w_c T_c[b]^2 and (unless
+ * NULL) wsum_dev[0] = sum_c w_c; w_dev = NULL means unit weights.  Fixed
+ * summation order, as qmc_pair_dist_reduce_dev; the per-configuration rows
+ * live in an engine-owned scratch filled in tiles of at most 2^16
+ * configurations. */
+int qmc_triple_dist_reduce_dev(qmc_engine *eng, int64_t nconf,
+                               const double *pos_dev, const double *w_dev,
+                               int32_t num_bins, double max_span,
+                               double *sums_dev, double *wsum_dev);
+
 /* Plain device buffers, so that a configuration set can stay resident across
  * many qmc_evaluate_dev calls with different engines: the correlated-sampling
  * optimiser re-evaluates wf_abs_log / energy of one fixed set for every trial
@@ -372,6 +405,13 @@ int qmc_vmc_obdm(qmc_vmc *v, int32_t nshift, const double *shifts, double *out);
  * leaves the device and the chain state is not touched.  Host buffer;
  * synchronous; num_bins checked as by qmc_pair_dist. */
 int qmc_vmc_pair_dist(qmc_vmc *v, int32_t num_bins, double *out);
+/* Triple-span histogram parts of the CURRENT configurations summed over the
+ * chains: out[num_bins + 1][2] = sum_w T_w[b], sum_w T_w[b]^2 (T as
+ * qmc_triple_dist), on the resident rows, after either move type; no position
+ * leaves the device and the chain state is not touched.  Host buffer;
+ * synchronous; num_bins and max_span checked as by qmc_triple_dist. */
+int qmc_vmc_triple_dist(qmc_vmc *v, int32_t num_bins, double max_span,
+                        double *out);
 /* Device addresses of the per-chain block sums of the last block
  * (sum_e[W], sum_e2[W], n_acc[W]) for on-device reductions / collectives. */
 int qmc_vmc_block_sums_dev(qmc_vmc *v, double **sum_e, double **sum_e2,

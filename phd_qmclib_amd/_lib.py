@@ -105,6 +105,13 @@ SIGNATURES = {
     'qmc_pair_dist_dev': (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _vp]),
     'qmc_pair_dist_reduce_dev': (C.c_int, [_vp, C.c_int64, _vp, _vp,
                                            C.c_int32, _vp, _vp]),
+    'qmc_triple_dist': (C.c_int, [_vp, C.c_int64, _dp, C.c_int32, C.c_double,
+                                  _u32p]),
+    'qmc_triple_dist_dev': (C.c_int, [_vp, C.c_int64, _vp, C.c_int32,
+                                      C.c_double, _vp]),
+    'qmc_triple_dist_reduce_dev': (C.c_int, [_vp, C.c_int64, _vp, _vp,
+                                             C.c_int32, C.c_double, _vp,
+                                             _vp]),
     'qmc_buffer_alloc': (C.c_int, [C.c_int, C.c_size_t, C.POINTER(_vp)]),
     'qmc_buffer_free': (C.c_int, [_vp]),
     'qmc_buffer_upload': (C.c_int, [_vp, _vp, C.c_size_t]),
@@ -116,6 +123,7 @@ SIGNATURES = {
     'qmc_vmc_ssf': (C.c_int, [_vp, C.c_int32, _dp]),
     'qmc_vmc_obdm': (C.c_int, [_vp, C.c_int32, _dp, _dp]),
     'qmc_vmc_pair_dist': (C.c_int, [_vp, C.c_int32, _dp]),
+    'qmc_vmc_triple_dist': (C.c_int, [_vp, C.c_int32, C.c_double, _dp]),
     'qmc_vmc_run_block': (C.c_int, [_vp, C.c_int64, _dp, _dp, _i64p, _dp, _dp,
                                     _u8p, _dp]),
     'qmc_vmc_state_dev': (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),

@@ -11,6 +11,7 @@
 #include "qmc_kernels_misc.h"
 #include "qmc_obdm.h"
 #include "qmc_pairdist.h"
+#include "qmc_tripledist.h"
 #include "qmc_cmdiff.h"
 #include "qmc_isf.h"
 #include "qmc_site.h"
@@ -118,6 +119,8 @@ struct qmc_engine {
     // pair distribution scratch (qmc_pair_dist*): the per-configuration tile
     // of histograms as doubles and the sums of qmc_vmc_pair_dist
     DevBuf<double> pd_hist, pd_sums;
+    // three-body distribution scratch (qmc_triple_dist*), as the pair one
+    DevBuf<double> td_hist, td_sums;
 
     qmc_engine() = default;
     qmc_engine(const qmc_engine &) = delete;
@@ -1718,6 +1721,124 @@ extern "C" int qmc_vmc_pair_dist(qmc_vmc *v, int32_t num_bins, double *out)
                                       e->pd_sums, nullptr);
     return rc ? rc : read_doubles(e, out, e->pd_sums, 2 * B);
 }
+
+// ---- three-body distribution g3(d) (csrc/qmc_tripledist.h) ---------------
+// Tiles as for g2 (PD_TILE, PD_SCRATCH_ELEMS), on rows of num_bins + 1.
+static int triple_dist_check(const char *who, const qmc_engine *e,
+                             int64_t nconf, int32_t num_bins, double max_span)
+{
+    if (num_bins < 1 || num_bins > TD_MAX_BINS)
+        return fail(std::string(who) + ": num_bins outside [1, " +
+                    std::to_string(TD_MAX_BINS) + "]");
+    if (!(max_span > 0.0) || !(max_span <= 0.5 * e->dm.L))
+        return fail(std::string(who) + ": max_span outside (0, L/2]");
+    if (nconf < 0) return fail(std::string(who) + ": nconf < 0");
+    return 0;
+}
+
+// histograms of nconf device-resident configurations -> out[nconf][B + 1]
+template <typename OutT>
+static int triple_dist_launch(qmc_engine *e, long long nconf,
+                              const double *pos_dev, int32_t B, double max_span,
+                              OutT *out)
+{
+    if (nconf <= 0) return 0;
+    const int n = e->dm.n;
+    int G = est_width(n);
+    const size_t per_conf = td_lds_per_conf(n, B);
+    while (G < 64 && (64 / G) * per_conf > TD_LDS_BUDGET) G *= 2;
+    const int gpw = 64 / G;
+    const size_t lds = gpw * per_conf;
+    const unsigned ntriples =
+        (unsigned)((long long)n * (n - 1) * (n - 2) / 6);
+    return launch_width_chunks(G, nconf, (1ll << 30) * gpw,
+                               [&](auto g, long long c0, long long nc) {
+        TripleDistArgs a{ pos_dev + (size_t)c0 * n,
+                          out + (size_t)c0 * (B + 1), nc, n, (int)B, ntriples,
+                          e->dm.L, max_span, (double)B / max_span };
+        hipLaunchKernelGGL((triple_dist_kernel<decltype(g)::value, OutT>),
+                           dim3((unsigned)((nc + gpw - 1) / gpw)), dim3(64),
+                           lds, e->stream, a);
+    });
+}
+
+extern "C" int qmc_triple_dist_dev(qmc_engine *e, int64_t nconf,
+                                   const double *pos, int32_t num_bins,
+                                   double max_span, uint32_t *counts)
+{
+    if (!e || !pos || !counts)
+        return fail("qmc_triple_dist_dev: null argument");
+    if (triple_dist_check("qmc_triple_dist_dev", e, nconf, num_bins, max_span))
+        return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    return triple_dist_launch(e, nconf, pos, num_bins, max_span, counts);
+}
+
+extern "C" int qmc_triple_dist_reduce_dev(qmc_engine *e, int64_t nconf,
+                                          const double *pos, const double *w,
+                                          int32_t num_bins, double max_span,
+                                          double *sums, double *wsum)
+{
+    if (!e || !pos || !sums)
+        return fail("qmc_triple_dist_reduce_dev: null argument");
+    if (triple_dist_check("qmc_triple_dist_reduce_dev", e, nconf, num_bins,
+                          max_span))
+        return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n = (size_t)e->dm.n;
+    const int K = num_bins + 1;
+    const long long tile = std::min<long long>(
+        std::max<long long>(nconf, 1),
+        std::min(PD_TILE, PD_SCRATCH_ELEMS / K));
+    if (e->td_hist.reserve((size_t)tile * K)) return 1;
+    return reduce_tiles(e, nconf, tile, e->td_hist, w, K, sums, wsum,
+                        [&](long long c0, long long nc) {
+        return triple_dist_launch(e, nc, pos + (size_t)c0 * n, num_bins,
+                                  max_span, e->td_hist.get());
+    });
+}
+
+extern "C" int qmc_triple_dist(qmc_engine *e, int64_t nconf, const double *pos,
+                               int32_t num_bins, double max_span,
+                               uint32_t *counts)
+{
+    if (!e || !pos || !counts) return fail("qmc_triple_dist: null argument");
+    if (triple_dist_check("qmc_triple_dist", e, nconf, num_bins, max_span))
+        return 1;
+    if (nconf == 0) return 0;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n = (size_t)e->dm.n, K = (size_t)num_bins + 1;
+    const long long tile = std::max<long long>(
+        1, std::min<long long>(nconf, PD_SCRATCH_ELEMS / (long long)std::max(n, K)));
+    DevBuf<double> dpos;
+    DevBuf<uint32_t> dcnt;
+    if (dpos.alloc((size_t)tile * n) || dcnt.alloc((size_t)tile * K)) return 1;
+    return run_host_tiles(e, nconf, tile, pos, dpos,
+                          { { counts, dcnt.get(), K * sizeof(uint32_t) } },
+                          [&](long long nc) {
+        return triple_dist_launch(e, nc, dpos, num_bins, max_span, dcnt.get());
+    });
+}
+
+// Histogram sums of the CURRENT configurations of the chains, on the resident
+// rows (the kernel orders every row itself, so neither the position order of
+// the 'all' rows nor the label order of the 'particle' rows matters); the
+// chain state is only read.
+extern "C" int qmc_vmc_triple_dist(qmc_vmc *v, int32_t num_bins,
+                                   double max_span, double *out)
+{
+    if (!v || !out) return fail("qmc_vmc_triple_dist: null argument");
+    qmc_engine *e = v->eng;
+    if (triple_dist_check("qmc_vmc_triple_dist", e, 0, num_bins, max_span))
+        return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t K = (size_t)num_bins + 1;
+    if (e->td_sums.reserve(2 * K)) return 1;
+    int rc = qmc_triple_dist_reduce_dev(e, v->W, v->pos, nullptr, num_bins,
+                                        max_span, e->td_sums, nullptr);
+    return rc ? rc : read_doubles(e, out, e->td_sums, 2 * K);
+}
+
 
 
 extern "C" int qmc_vmc_block_sums_dev(qmc_vmc *v, double **se, double **se2,

@@ -78,6 +78,48 @@ def pair_distribution_norm(counts, boson_number, supercell_size):
     return counts * (L / (n * (n - 1) * delta))
 
 
+MAX_TRIPLE_DIST_BINS = 4096    # TD_MAX_BINS of csrc/qmc_tripledist.h
+
+
+def _max_span(supercell_size, max_span):
+    """max_span of the triple-span histograms: None is L/2, anything outside
+    (0, L/2] a ValueError."""
+    half = 0.5 * float(supercell_size)
+    if max_span is None:
+        return half
+    span = float(max_span)
+    if not 0.0 < span <= half:
+        raise ValueError('max_span must be in (0, supercell_size / 2]')
+    return span
+
+
+def triple_distribution_bins(supercell_size, num_bins, max_span=None):
+    """Bin centres d_b = (b + 1/2) delta, delta = max_span / num_bins, of the
+    triple-span histograms (without the overflow bin) -> d[num_bins]."""
+    nb = ModelEngine._num_bins(num_bins)
+    delta = _max_span(supercell_size, max_span) / nb
+    return (np.arange(nb) + 0.5) * delta
+
+
+def triple_distribution_norm(counts, boson_number, supercell_size,
+                             max_span=None):
+    """g3 = T / (C(N,3) 3 (delta/L)^2 (2 b + 1)) of (mean) histograms
+    T[..., num_bins + 1], the overflow bin dropped -> [..., num_bins]: 1 on
+    average for uncorrelated uniform particles (three uniform points of a ring
+    lie within an arc x L with probability 3 x^2, x <= 1/2)."""
+    counts = np.asarray(counts, dtype=np.float64)
+    n, L = int(boson_number), float(supercell_size)
+    nb = counts.shape[-1] - 1
+    if nb < 1:
+        raise ValueError('counts[..., num_bins + 1] expected')
+    if n < 3:
+        raise ValueError('g3 needs boson_number >= 3')
+    delta = _max_span(L, max_span) / nb
+    triples = n * (n - 1) * (n - 2) / 6.0
+    expect = triples * 3.0 * (delta / L) ** 2 * (2.0 * np.arange(nb) + 1.0)
+    return counts[..., :nb] / expect
+
+
 def superfluid_ratio(iter_cm, num_walkers, boson_number, time_step):
     """The normalised centre-of-mass diffusion curve of one estimator block,
     iter_cm[nts, 2] (`DmcEnsemble.read_cm_diffusion`) and num_walkers[nts]:
@@ -519,6 +561,52 @@ class ModelEngine:
             self.pair_distribution_reduce_dev(nconf, pos_ptr, w_ptr, nb,
                                               sums_ptr, wsum_ptr))
 
+    def _span(self, max_span):
+        return _max_span(self.cfc_spec.model_params.supercell_size, max_span)
+
+    def triple_distribution(self, pos, num_bins, max_span=None):
+        """Triple-span histogram of every configuration in pos[W, N]:
+        counts[W, num_bins + 1] (uint32) of the unordered triples over num_bins
+        uniform bins of the span (the shortest arc that holds the three) in
+        [0, max_span) and one overflow bin; max_span in (0, L/2], None = L/2.
+        Every row adds up to N (N - 1) (N - 2) / 6.
+        `triple_distribution_norm` turns counts into g3."""
+        pos = _pos2d(pos, self.num_particles)
+        nb, span = self._num_bins(num_bins), self._span(max_span)
+        counts = np.zeros((pos.shape[0], nb + 1), dtype=np.uint32)
+        check(self._lib.qmc_triple_dist(self._h, pos.shape[0], ptr(pos), nb,
+                                        span, ptr(counts, _lib._u32p)))
+        return counts
+
+    def triple_distribution_dev(self, nconf, pos_ptr, num_bins, max_span,
+                                counts_ptr):
+        """Asynchronous histograms on device-resident buffers (raw pointers):
+        pos[nconf, N] (fp64) -> counts[nconf, num_bins + 1] (uint32)."""
+        check(self._lib.qmc_triple_dist_dev(self._h, int(nconf), pos_ptr,
+                                            int(num_bins),
+                                            self._span(max_span), counts_ptr))
+
+    def triple_distribution_reduce_dev(self, nconf, pos_ptr, w_ptr, num_bins,
+                                       max_span, sums_ptr, wsum_ptr=0):
+        """Asynchronous weighted sums over the configurations, device buffers:
+        sums[num_bins + 1, 2] = sum_c w_c T_c, sum_c w_c T_c^2 and wsum[0] =
+        sum_c w_c (w_ptr = 0: unit weights), in a fixed summation order."""
+        check(self._lib.qmc_triple_dist_reduce_dev(
+            self._h, int(nconf), pos_ptr, w_ptr, int(num_bins),
+            self._span(max_span), sums_ptr, wsum_ptr))
+
+    def triple_distribution_weighted(self, pos, weights, num_bins,
+                                     max_span=None):
+        """sum_c w_c T_c / sum_c w_c over the configurations pos[W, N] (one
+        upload of the positions, the weighted reduction on the device)
+        -> mean histogram[num_bins + 1]."""
+        nb, span = self._num_bins(num_bins), self._span(max_span)
+        return self._weighted_mean(
+            pos, weights, nb + 1, [],
+            lambda nconf, pos_ptr, w_ptr, sums_ptr, wsum_ptr:
+            self.triple_distribution_reduce_dev(nconf, pos_ptr, w_ptr, nb,
+                                                span, sums_ptr, wsum_ptr))
+
 
 #: VmcEnsemble(move=...) -> qmc_vmc_params.gaussian (the proposal code;
 #: 1 is the Gaussian all-particle proposal, `gaussian=True`)
@@ -605,6 +693,16 @@ class VmcEnsemble:
         nb = ModelEngine._num_bins(num_bins)
         out = np.zeros((nb, 2))
         check(self._lib.qmc_vmc_pair_dist(self._h, nb, ptr(out)))
+        return out
+
+    def triple_dist_parts(self, num_bins, max_span=None) -> np.ndarray:
+        """Sums over the chains of the triple-span histogram T and of T^2 of
+        the current configurations -> [num_bins + 1, 2]; computed on the
+        resident rows, which are only read."""
+        nb = ModelEngine._num_bins(num_bins)
+        span = self.engine._span(max_span)
+        out = np.zeros((nb + 1, 2))
+        check(self._lib.qmc_vmc_triple_dist(self._h, nb, span, ptr(out)))
         return out
 
     def get_state(self):

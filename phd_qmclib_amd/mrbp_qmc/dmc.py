@@ -27,7 +27,8 @@ import numpy as np
 
 from .. import utils
 from ..engine import (DmcEnsemble, ModelEngine, dmc_propagator_code,
-                      pair_distribution_bins, pair_distribution_norm)
+                      pair_distribution_bins, pair_distribution_norm,
+                      triple_distribution_bins, triple_distribution_norm)
 from ..qmc_base import dmc as dmc_base, dmc_est
 from . import model
 
@@ -530,6 +531,27 @@ class Sampling:
         return (pair_distribution_bins(spec.supercell_size, num_bins),
                 pair_distribution_norm(hist, spec.boson_number,
                                        spec.supercell_size))
+
+    def triple_distribution(self, state: State, num_bins, max_span=None):
+        """Mixed estimate of the three-body distribution over the live
+        walkers of a State: sum_w W_w T_w / sum_w W_w, T the triple-span
+        histogram of a walker, normalised to g3 -> (d[num_bins], g3[num_bins])
+        for spans below `max_span` (in (0, L/2], None = L/2).  Slots beyond
+        `num_walkers` do not count.  The positions are uploaded once; the
+        weighted reduction runs on the device.  Extrapolate with the VMC value
+        of `vmc.EnsembleSampling.triple_distribution`: 2 DMC - VMC."""
+        nw = int(state.num_walkers)
+        confs = np.asarray(state.confs, dtype=np.float64)
+        pos = confs[:nw, model.SysConfSlot.pos, :]
+        weight = np.asarray(state.props.weight, dtype=np.float64)[:nw]
+        eng = model.core_funcs._engine(*self.model_spec.cfc_spec)
+        spec = self.model_spec
+        hist = eng.triple_distribution_weighted(pos, weight, num_bins,
+                                                max_span)
+        return (triple_distribution_bins(spec.supercell_size, num_bins,
+                                         max_span),
+                triple_distribution_norm(hist, spec.boson_number,
+                                         spec.supercell_size, max_span))
 
 
     @property

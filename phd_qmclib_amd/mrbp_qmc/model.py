@@ -21,7 +21,8 @@ from .. import ideal
 
 __all__ = ['CSWFOptimizer', 'CFCSpec', 'OBFParams', 'Params', 'Spec', 'TBFParams',
            'SysConfSlot', 'SysConfDistType', 'DIST_RAND', 'DIST_REGULAR',
-           'core_funcs', 'PhysicalFuncs', 'pair_distribution_bins']
+           'core_funcs', 'PhysicalFuncs', 'pair_distribution_bins',
+           'triple_distribution_bins']
 
 import enum
 
@@ -370,6 +371,7 @@ class PhysicalFuncs:
         energy(sys_conf)                  (ns,nop)->()
         one_body_density(sz, sys_conf)    (),(ns,nop)->()
         pair_distribution(num_bins, sys_conf)  (ns,nop)->(B)
+        triple_distribution(num_bins, sys_conf)  (ns,nop)->(B)
         fourier_density(kz_set, sys_conf) (nkz),(ns,nop)->(nkz)   complex
 
     The loop dimensions broadcast as NumPy's; the whole broadcast batch goes to
@@ -443,6 +445,22 @@ class PhysicalFuncs:
         g2 = pair_distribution_norm(counts, mp.boson_number, mp.supercell_size)
         return g2.reshape(loop + g2.shape[-1:])
 
+    def triple_distribution(self, num_bins, sys_conf, max_span=None):
+        """Three-body distribution g3(d_b) of every configuration at the
+        `num_bins` bin centres of `triple_distribution_bins`: the histogram of
+        the triple spans (the shortest arc of the ring that holds the three
+        particles) below `max_span` (in (0, L/2], None = L/2) over
+        C(N,3) 3 (delta/L)^2 (2 b + 1), which is 1 on average for uncorrelated
+        particles.  `num_bins` and `max_span` are scalars; the loop dimensions
+        of sys_conf broadcast."""
+        from ..engine import triple_distribution_norm
+        loop, pos = self._conf_batch(sys_conf)
+        counts = self._engine().triple_distribution(pos, num_bins, max_span)
+        mp = self.cfc_spec_nt.model_params
+        g3 = triple_distribution_norm(counts, mp.boson_number,
+                                      mp.supercell_size, max_span)
+        return g3.reshape(loop + g3.shape[-1:])
+
     def fourier_density(self, kz_set, sys_conf):
         """Fourier density component with momentum k: sum_i exp(i k z_i)."""
         kz_set = np.asarray(kz_set, dtype=np.float64)
@@ -465,6 +483,15 @@ def pair_distribution_bins(model_spec, num_bins):
     from ..engine import pair_distribution_bins as bins
     mp = getattr(model_spec, 'model_params', model_spec)
     return bins(mp.supercell_size, num_bins)
+
+
+def triple_distribution_bins(model_spec, num_bins, max_span=None):
+    """Bin centres d_b = (b + 1/2) delta, delta = max_span / num_bins
+    (max_span None = L/2), of the three-body distribution of a model Spec (or
+    CFCSpec) -> d[num_bins]."""
+    from ..engine import triple_distribution_bins as bins
+    mp = getattr(model_spec, 'model_params', model_spec)
+    return bins(mp.supercell_size, num_bins, max_span)
 
 
 class CSWFOptimizer:

@@ -18,7 +18,8 @@ import numpy as np
 
 from .. import utils
 from ..engine import (ModelEngine, VmcEnsemble, pair_distribution_bins,
-                      pair_distribution_norm)
+                      pair_distribution_norm, triple_distribution_bins,
+                      triple_distribution_norm)
 from ..qmc_base import vmc as vmc_base
 from . import model
 
@@ -336,6 +337,23 @@ class EnsembleSampling:
         return (pair_distribution_bins(L, num_bins),
                 pair_distribution_norm(mean, n, L),
                 pair_distribution_norm(stderr, n, L))
+
+    def triple_distribution(self, num_bins, max_span=None):
+        """Three-body distribution g3(d) over the chains' current
+        configurations -> (d, mean, stderr) at the `num_bins` bin centres of
+        [0, max_span) (max_span in (0, L/2], None = L/2); computed on the rows
+        resident on the device after either move type (no position is copied
+        to the host, the chains are not touched).  The standard error is that
+        of the mean over the chains.  Its limit d -> 0 is the local g3."""
+        parts = self.ensemble.triple_dist_parts(num_bins, max_span)
+        w = self.num_chains
+        n, L = self.model_spec.boson_number, self.model_spec.supercell_size
+        mean = parts[:, 0] / w
+        var = np.maximum(parts[:, 1] / w - mean ** 2, 0.0)
+        stderr = np.sqrt(var / max(w - 1, 1))
+        return (triple_distribution_bins(L, num_bins, max_span),
+                triple_distribution_norm(mean, n, L, max_span),
+                triple_distribution_norm(stderr, n, L, max_span))
 
     def close(self):
         self.ensemble.close()
