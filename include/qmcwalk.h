@@ -351,6 +351,48 @@ int qmc_triple_dist_reduce_dev(qmc_engine *eng, int64_t nconf,
                                int32_t num_bins, double max_span,
                                double *sums_dev, double *wsum_dev);
 
+/* Renyi-2 entanglement entropy of a segment by replica swap (no counterpart
+ * in the reference).  The configurations 2p and 2p + 1 of pos[nconf][N]
+ * (nconf even) are the replicas R1, R2 of pair p; nlen segments
+ * A_k = [origin, origin + lengths[k]) of the ring of length L, each length in
+ * (0, L), B_k the complement.  Particle z is in A_k when t < lengths[k],
+ * t = zw - a0w (+ L where negative), zw and a0w the images of z and origin in
+ * [0, L).  n_a[nconf][nlen] is the number of particles of every configuration
+ * in A_k (exact).  Where the two replicas of a pair hold the same number
+ * (a matched pair) the particles inside A_k can be exchanged,
+ * R1' = A(R2) u B(R1), R2' = A(R1) u B(R2), and
+ *   log_ratio[nconf / 2][nlen] =
+ *       ln|psi(R1')| + ln|psi(R2')| - ln|psi(R1)| - ln|psi(R2)|,
+ * formed from the pair factors across the cut alone (the one-body factors and
+ * the pairs inside A and inside B cancel identically: exactly 0 without
+ * interactions); -inf where the pair is not matched.  With swap =
+ * exp(log_ratio) (0 where unmatched) over P independent pairs drawn from
+ * |psi|^2, S2(l_k) = -ln(sum_p swap[p][k] / P) is the Renyi-2 entropy of the
+ * segment in the state psi: for VMC chains the variational S2 of the trial
+ * wave function.  Always fp64: qmc_engine_set_fast_math does not apply
+ * (csrc/qmc_renyi.h).
+ * qmc_renyi_swap: host buffers, synchronous; either output may be NULL, not
+ * both.  An odd or non-positive nconf, nlen outside [1, 4096], a length
+ * outside (0, L) or not finite, an origin that is not finite, a NULL pos /
+ * lengths is an error. */
+int qmc_renyi_swap(qmc_engine *eng, int64_t nconf, const double *pos,
+                   int32_t nlen, const double *lengths, double origin,
+                   int32_t *n_a, double *log_ratio);
+/* Same on device-resident buffers, asynchronous on the engine's stream (the
+ * values of lengths_dev are not checked: the host does not see them). */
+int qmc_renyi_swap_dev(qmc_engine *eng, int64_t nconf, const double *pos_dev,
+                       int32_t nlen, const double *lengths_dev, double origin,
+                       int32_t *n_a_dev, double *log_ratio_dev);
+/* Sums over the nconf / 2 pairs, device buffers, asynchronous:
+ * sums_dev[nlen][3] = sum_p swap, sum_p swap^2, number of matched pairs (the
+ * argument of exp clamped to +-700).  Fixed summation order: two calls give
+ * the same bits; the per-pair rows live in an engine-owned scratch filled in
+ * tiles of at most 2^16 pairs. */
+int qmc_renyi_swap_reduce_dev(qmc_engine *eng, int64_t nconf,
+                              const double *pos_dev, int32_t nlen,
+                              const double *lengths_dev, double origin,
+                              double *sums_dev);
+
 /* Plain device buffers, so that a configuration set can stay resident across
  * many qmc_evaluate_dev calls with different engines: the correlated-sampling
  * optimiser re-evaluates wf_abs_log / energy of one fixed set for every trial
@@ -412,6 +454,14 @@ int qmc_vmc_pair_dist(qmc_vmc *v, int32_t num_bins, double *out);
  * synchronous; num_bins and max_span checked as by qmc_triple_dist. */
 int qmc_vmc_triple_dist(qmc_vmc *v, int32_t num_bins, double max_span,
                         double *out);
+/* Replica-swap sums of the CURRENT configurations, the chains 2p and 2p + 1
+ * being the replicas of pair p: out[nlen][3] as sums_dev of
+ * qmc_renyi_swap_reduce_dev, on the resident rows, after either move type; no
+ * position leaves the device and the chain state is not touched.  An odd
+ * num_chains is an error.  Host buffers; synchronous; nlen, lengths and origin
+ * checked as by qmc_renyi_swap. */
+int qmc_vmc_renyi_swap(qmc_vmc *v, int32_t nlen, const double *lengths,
+                       double origin, double *out);
 /* Device addresses of the per-chain block sums of the last block
  * (sum_e[W], sum_e2[W], n_acc[W]) for on-device reductions / collectives. */
 int qmc_vmc_block_sums_dev(qmc_vmc *v, double **sum_e, double **sum_e2,

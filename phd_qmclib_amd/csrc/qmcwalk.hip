@@ -12,6 +12,7 @@
 #include "qmc_obdm.h"
 #include "qmc_pairdist.h"
 #include "qmc_tripledist.h"
+#include "qmc_renyi.h"
 #include "qmc_cmdiff.h"
 #include "qmc_isf.h"
 #include "qmc_site.h"
@@ -121,6 +122,10 @@ struct qmc_engine {
     DevBuf<double> pd_hist, pd_sums;
     // three-body distribution scratch (qmc_triple_dist*), as the pair one
     DevBuf<double> td_hist, td_sums;
+    // replica-swap scratch (qmc_renyi_swap*): the per-pair tile of rows
+    // (swap, matched), their column sums, and the lengths and sums of
+    // qmc_vmc_renyi_swap
+    DevBuf<double> ry_rows, ry_colsum, ry_vmc;
 
     qmc_engine() = default;
     qmc_engine(const qmc_engine &) = delete;
@@ -1839,6 +1844,164 @@ extern "C" int qmc_vmc_triple_dist(qmc_vmc *v, int32_t num_bins,
     return rc ? rc : read_doubles(e, out, e->td_sums, 2 * K);
 }
 
+
+// ---- Renyi-2 replica swap (csrc/qmc_renyi.h) -----------------------------
+// Tiles as for g2 (PD_TILE, PD_SCRATCH_ELEMS), on rows of 2 nlen per pair.
+static int renyi_check(const char *who, int64_t nconf, int32_t nlen,
+                       double origin)
+{
+    if (nlen < 1 || nlen > RENYI_MAX_LEN)
+        return fail(std::string(who) + ": nlen outside [1, " +
+                    std::to_string(RENYI_MAX_LEN) + "]");
+    if (nconf <= 0 || (nconf & 1))
+        return fail(std::string(who) +
+                    ": nconf must be positive and even (replica pairs)");
+    if (!std::isfinite(origin))
+        return fail(std::string(who) + ": origin is not finite");
+    return 0;
+}
+
+static int renyi_check_host_lengths(const char *who, const qmc_engine *e,
+                                    int32_t nlen, const double *lengths)
+{
+    for (int32_t k = 0; k < nlen; ++k)
+        if (!std::isfinite(lengths[k]) || !(lengths[k] > 0.0) ||
+            !(lengths[k] < e->dm.L))
+            return fail(std::string(who) + ": length " + std::to_string(k) +
+                        " outside (0, L)");
+    return 0;
+}
+
+// npair device-resident replica pairs -> n_a, log_ratio and / or rows
+static int renyi_launch(qmc_engine *e, long long npair, const double *pos_dev,
+                        int32_t K, const double *lengths_dev, double origin,
+                        int32_t *n_a, double *log_ratio, double *rows)
+{
+    const size_t n2 = 2 * (size_t)e->dm.n;
+    const size_t lds = renyi_lds_bytes(e->dm.n, K);
+    if (lds > RENYI_LDS_LIMIT)
+        return fail("qmc_renyi_swap: boson_number too large for the LDS of a "
+                    "workgroup");
+    allow_lds(renyi_swap_kernel, lds);      // 56 KB at N = 512, K = 4096
+    const long long xmax = 1ll << 30;
+    for (long long p0 = 0; p0 < npair; p0 += xmax) {
+        const long long np = std::min(xmax, npair - p0);
+        RenyiArgs a{ pos_dev + (size_t)p0 * n2, lengths_dev,
+                     n_a ? n_a + (size_t)p0 * 2 * K : nullptr,
+                     log_ratio ? log_ratio + (size_t)p0 * K : nullptr,
+                     rows ? rows + (size_t)p0 * 2 * K : nullptr, np, (int)K,
+                     origin };
+        hipLaunchKernelGGL(renyi_swap_kernel, dim3((unsigned)np), dim3(64),
+                           lds, e->stream, e->dm_dev, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int qmc_renyi_swap_dev(qmc_engine *e, int64_t nconf,
+                                  const double *pos, int32_t nlen,
+                                  const double *lengths, double origin,
+                                  int32_t *n_a, double *log_ratio)
+{
+    if (!e || !pos || !lengths || (!n_a && !log_ratio))
+        return fail("qmc_renyi_swap_dev: null argument");
+    if (renyi_check("qmc_renyi_swap_dev", nconf, nlen, origin)) return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    return renyi_launch(e, nconf / 2, pos, nlen, lengths, origin, n_a,
+                        log_ratio, nullptr);
+}
+
+extern "C" int qmc_renyi_swap_reduce_dev(qmc_engine *e, int64_t nconf,
+                                         const double *pos, int32_t nlen,
+                                         const double *lengths, double origin,
+                                         double *sums)
+{
+    if (!e || !pos || !lengths || !sums)
+        return fail("qmc_renyi_swap_reduce_dev: null argument");
+    if (renyi_check("qmc_renyi_swap_reduce_dev", nconf, nlen, origin))
+        return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n2 = 2 * (size_t)e->dm.n;
+    const int C = 2 * nlen;                     // columns of a pair's row
+    const long long npair = nconf / 2;
+    const long long tile = std::min<long long>(
+        npair, std::min(PD_TILE, PD_SCRATCH_ELEMS / C));
+    if (e->ry_rows.reserve((size_t)tile * C) ||
+        e->ry_colsum.reserve((size_t)2 * C))
+        return 1;
+    if (reduce_tiles(e, npair, tile, e->ry_rows, nullptr, C, e->ry_colsum,
+                     nullptr, [&](long long p0, long long np) {
+            return renyi_launch(e, np, pos + (size_t)p0 * n2, nlen, lengths,
+                                origin, nullptr, nullptr, e->ry_rows.get());
+        }))
+        return 1;
+    hipLaunchKernelGGL(renyi_pack_kernel, dim3((nlen + 63) / 64), dim3(64), 0,
+                       e->stream, e->ry_colsum.get(), (int)nlen, sums);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int qmc_renyi_swap(qmc_engine *e, int64_t nconf, const double *pos,
+                              int32_t nlen, const double *lengths,
+                              double origin, int32_t *n_a, double *log_ratio)
+{
+    if (!e || !pos || !lengths || (!n_a && !log_ratio))
+        return fail("qmc_renyi_swap: null argument");
+    if (renyi_check("qmc_renyi_swap", nconf, nlen, origin) ||
+        renyi_check_host_lengths("qmc_renyi_swap", e, nlen, lengths))
+        return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n = (size_t)e->dm.n, K = (size_t)nlen;
+    // an even number of configurations to a tile: whole pairs
+    const long long tile = std::max<long long>(
+        2, std::min<long long>(
+               nconf, PD_SCRATCH_ELEMS / (long long)std::max(n, K)) & ~1ll);
+    DevBuf<double> dlen, dpos, dlr;
+    DevBuf<int32_t> dna;
+    if (dlen.alloc(K) || dpos.alloc((size_t)tile * n) ||
+        (n_a && dna.alloc((size_t)tile * K)) ||
+        (log_ratio && dlr.alloc((size_t)(tile / 2) * K)))
+        return 1;
+    HIP_TRY(hipMemcpyAsync(dlen, lengths, K * sizeof(double),
+                           hipMemcpyHostToDevice, e->stream));
+    // log_ratio has a row per pair: half a row per configuration
+    return run_host_tiles(e, nconf, tile, pos, dpos,
+                          { { n_a, dna.get(), K * sizeof(int32_t) },
+                            { log_ratio, dlr.get(), K * sizeof(double) / 2 } },
+                          [&](long long nc) {
+        return renyi_launch(e, nc / 2, dpos, nlen, dlen, origin, dna.get(),
+                            dlr.get(), nullptr);
+    });
+}
+
+// Swap sums of the CURRENT configurations of the chains, chains 2p and 2p + 1
+// the replicas of pair p, on the resident rows (the estimator is symmetric in
+// the particles of a row, so neither the position order of the 'all' rows nor
+// the label order of the 'particle' rows matters); the chain state is only
+// read.
+extern "C" int qmc_vmc_renyi_swap(qmc_vmc *v, int32_t nlen,
+                                  const double *lengths, double origin,
+                                  double *out)
+{
+    if (!v || !lengths || !out)
+        return fail("qmc_vmc_renyi_swap: null argument");
+    qmc_engine *e = v->eng;
+    if (v->W & 1)
+        return fail("qmc_vmc_renyi_swap: an odd number of chains has no "
+                    "replica pairs");
+    if (renyi_check("qmc_vmc_renyi_swap", v->W, nlen, origin) ||
+        renyi_check_host_lengths("qmc_vmc_renyi_swap", e, nlen, lengths))
+        return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t K = (size_t)nlen;
+    if (e->ry_vmc.reserve(4 * K)) return 1;
+    double *dlen = e->ry_vmc + 3 * K;
+    HIP_TRY(hipMemcpyAsync(dlen, lengths, K * sizeof(double),
+                           hipMemcpyHostToDevice, e->stream));
+    int rc = qmc_renyi_swap_reduce_dev(e, v->W, v->pos, nlen, dlen, origin,
+                                       e->ry_vmc);
+    return rc ? rc : read_doubles(e, out, e->ry_vmc, 3 * K);
+}
 
 
 extern "C" int qmc_vmc_block_sums_dev(qmc_vmc *v, double **se, double **se2,

@@ -120,6 +120,47 @@ def triple_distribution_norm(counts, boson_number, supercell_size,
     return counts[..., :nb] / expect
 
 
+MAX_RENYI_LENGTHS = 4096       # RENYI_MAX_LEN of csrc/qmc_renyi.h
+
+
+def renyi_lengths(supercell_size, lengths):
+    """Segment lengths of the replica-swap estimator as a contiguous fp64
+    array: 1 to 4096 finite values in (0, L), anything else a ValueError."""
+    ln = np.ascontiguousarray(lengths, dtype=np.float64)
+    if ln.ndim != 1 or not 1 <= ln.size <= MAX_RENYI_LENGTHS:
+        raise ValueError('lengths must be a 1-d array of 1 to %d values'
+                         % MAX_RENYI_LENGTHS)
+    if not np.all((ln > 0.0) & (ln < float(supercell_size))):
+        raise ValueError('every length must be in (0, supercell_size)')
+    return ln
+
+
+def _renyi_origin(origin):
+    a0 = float(origin)
+    if not np.isfinite(a0):
+        raise ValueError('origin must be finite')
+    return a0
+
+
+def renyi_entropy(sums, num_pairs):
+    """Renyi-2 entropy from the replica-swap sums[K, 3] = sum swap,
+    sum swap^2, matched pairs over `num_pairs` replica pairs
+    -> (S2[K], S2_err[K], p_match[K]): S2 = -ln(mean swap), its standard error
+    stderr(swap) / mean(swap), and the fraction of matched pairs.  A length no
+    pair matched at has S2 = inf and S2_err = nan."""
+    sums = np.asarray(sums, dtype=np.float64)
+    p = int(num_pairs)
+    if sums.ndim != 2 or sums.shape[1] != 3:
+        raise ValueError('sums[K, 3] expected')
+    if p != num_pairs or p < 1:
+        raise ValueError('num_pairs must be a positive integer')
+    mean = sums[:, 0] / p
+    var = np.maximum(sums[:, 1] / p - mean ** 2, 0.0)
+    stderr = np.sqrt(var / max(p - 1, 1))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return -np.log(mean), stderr / mean, sums[:, 2] / p
+
+
 def superfluid_ratio(iter_cm, num_walkers, boson_number, time_step):
     """The normalised centre-of-mass diffusion curve of one estimator block,
     iter_cm[nts, 2] (`DmcEnsemble.read_cm_diffusion`) and num_walkers[nts]:
@@ -607,6 +648,55 @@ class ModelEngine:
             self.triple_distribution_reduce_dev(nconf, pos_ptr, w_ptr, nb,
                                                 span, sums_ptr, wsum_ptr))
 
+    def _lengths(self, lengths):
+        return renyi_lengths(self.cfc_spec.model_params.supercell_size,
+                             lengths)
+
+    @staticmethod
+    def _num_replicas(nconf):
+        nconf = int(nconf)
+        if nconf < 2 or nconf % 2:
+            raise ValueError('an even, positive number of configurations '
+                             'expected: rows 2p and 2p + 1 are a replica pair')
+        return nconf
+
+    def renyi_swap(self, pos, lengths, origin=0.0):
+        """Replica swap of the segments A_k = [origin, origin + lengths[k]) of
+        the ring between the rows (2p, 2p + 1) of pos[W, N], W even
+        -> (n_a[W, K] (int32), log_ratio[W / 2, K]): the particles of every
+        row inside A_k, and ln|psi(R1') psi(R2') / (psi(R1) psi(R2))| of the
+        pair with its particles inside A_k exchanged, -inf where the two rows
+        hold different numbers there.  swap = exp(log_ratio);
+        S2 = -ln(mean swap) over independent pairs drawn from |psi|^2
+        (`renyi_entropy`)."""
+        pos = _pos2d(pos, self.num_particles)
+        ln, a0 = self._lengths(lengths), _renyi_origin(origin)
+        W = self._num_replicas(pos.shape[0])
+        n_a = np.zeros((W, ln.size), dtype=np.int32)
+        log_ratio = np.zeros((W // 2, ln.size))
+        check(self._lib.qmc_renyi_swap(self._h, W, ptr(pos), ln.size, ptr(ln),
+                                       a0, ptr(n_a, _lib._i32p),
+                                       ptr(log_ratio)))
+        return n_a, log_ratio
+
+    def renyi_swap_dev(self, nconf, pos_ptr, nlen, lengths_ptr, origin,
+                       n_a_ptr, log_ratio_ptr):
+        """Asynchronous replica swap on device-resident buffers (raw
+        pointers): pos[nconf, N], lengths[nlen] (fp64) -> n_a[nconf, nlen]
+        (int32) and log_ratio[nconf / 2, nlen]; either output may be 0."""
+        check(self._lib.qmc_renyi_swap_dev(
+            self._h, self._num_replicas(nconf), pos_ptr, int(nlen),
+            lengths_ptr, _renyi_origin(origin), n_a_ptr, log_ratio_ptr))
+
+    def renyi_swap_reduce_dev(self, nconf, pos_ptr, nlen, lengths_ptr, origin,
+                              sums_ptr):
+        """Asynchronous sums over the nconf / 2 replica pairs, device buffers:
+        sums[nlen, 3] = sum swap, sum swap^2, matched pairs, in a fixed
+        summation order (`renyi_entropy` turns them into S2)."""
+        check(self._lib.qmc_renyi_swap_reduce_dev(
+            self._h, self._num_replicas(nconf), pos_ptr, int(nlen),
+            lengths_ptr, _renyi_origin(origin), sums_ptr))
+
 
 #: VmcEnsemble(move=...) -> qmc_vmc_params.gaussian (the proposal code;
 #: 1 is the Gaussian all-particle proposal, `gaussian=True`)
@@ -703,6 +793,19 @@ class VmcEnsemble:
         span = self.engine._span(max_span)
         out = np.zeros((nb + 1, 2))
         check(self._lib.qmc_vmc_triple_dist(self._h, nb, span, ptr(out)))
+        return out
+
+    def renyi_parts(self, lengths, origin=0.0) -> np.ndarray:
+        """Replica-swap sums of the current configurations, the chains 2p and
+        2p + 1 being the replicas of pair p -> [K, 3] = sum swap, sum swap^2,
+        matched pairs (`ModelEngine.renyi_swap_reduce_dev`); computed on the
+        resident rows, which are only read.  An odd number of chains is a
+        ValueError."""
+        ln, a0 = self.engine._lengths(lengths), _renyi_origin(origin)
+        ModelEngine._num_replicas(self.num_chains)
+        out = np.zeros((ln.size, 3))
+        check(self._lib.qmc_vmc_renyi_swap(self._h, ln.size, ptr(ln), a0,
+                                           ptr(out)))
         return out
 
     def get_state(self):

@@ -372,6 +372,7 @@ class PhysicalFuncs:
         one_body_density(sz, sys_conf)    (),(ns,nop)->()
         pair_distribution(num_bins, sys_conf)  (ns,nop)->(B)
         triple_distribution(num_bins, sys_conf)  (ns,nop)->(B)
+        renyi_swap(lengths, sys_conf)     (2,ns,nop)->(K)
         fourier_density(kz_set, sys_conf) (nkz),(ns,nop)->(nkz)   complex
 
     The loop dimensions broadcast as NumPy's; the whole broadcast batch goes to
@@ -460,6 +461,29 @@ class PhysicalFuncs:
         g3 = triple_distribution_norm(counts, mp.boson_number,
                                       mp.supercell_size, max_span)
         return g3.reshape(loop + g3.shape[-1:])
+
+    def renyi_swap(self, lengths, sys_conf, origin=0.0):
+        """Replica-swap ratio of the Renyi-2 entanglement entropy: for the two
+        replicas sys_conf[..., 0, :, :] and sys_conf[..., 1, :, :] and every
+        segment A_k = [origin, origin + lengths[k]) of the ring,
+        |psi(R1') psi(R2') / (psi(R1) psi(R2))| with the particles inside A_k
+        exchanged between the replicas, 0 where the two hold different numbers
+        of particles there.  The mean over independent pairs drawn from
+        |psi|^2 is exp(-S2(l_k)): psi is the trial wave function, so this is
+        the variational S2 of the Bijl-Jastrow state.  `lengths` (each in
+        (0, L)) and `origin` are shared by the batch; the loop dimensions of
+        sys_conf in front of the replica axis broadcast.  A lattice user who
+        wants segments of whole sites passes origin = -barrier_width / 2 (the
+        cut in mid-barrier, the site convention of the site statistics) and
+        lengths that are multiples of the lattice period."""
+        sys_conf = np.asarray(sys_conf, dtype=np.float64)
+        if sys_conf.ndim < 3 or sys_conf.shape[-3] != 2:
+            raise ValueError('sys_conf must have the core shape (2, ns, nop)')
+        loop, pos = self._conf_batch(sys_conf)
+        _, log_ratio = self._engine().renyi_swap(pos, lengths, origin)
+        swap = np.exp(np.clip(log_ratio, -700.0, 700.0))
+        swap[np.isneginf(log_ratio)] = 0.0
+        return swap.reshape(loop[:-1] + swap.shape[-1:])
 
     def fourier_density(self, kz_set, sys_conf):
         """Fourier density component with momentum k: sum_i exp(i k z_i)."""

@@ -18,8 +18,8 @@ import numpy as np
 
 from .. import utils
 from ..engine import (ModelEngine, VmcEnsemble, pair_distribution_bins,
-                      pair_distribution_norm, triple_distribution_bins,
-                      triple_distribution_norm)
+                      pair_distribution_norm, renyi_entropy, renyi_lengths,
+                      triple_distribution_bins, triple_distribution_norm)
 from ..qmc_base import vmc as vmc_base
 from . import model
 
@@ -354,6 +354,23 @@ class EnsembleSampling:
         return (triple_distribution_bins(L, num_bins, max_span),
                 triple_distribution_norm(mean, n, L, max_span),
                 triple_distribution_norm(stderr, n, L, max_span))
+
+    def renyi_entropy(self, lengths, origin=0.0):
+        """Renyi-2 entanglement entropy of the segments
+        A_k = [origin, origin + lengths[k]) of the ring by replica swap over
+        the chains' current configurations, the chains 2p and 2p + 1 being the
+        two replicas of pair p (independent chains: an even `num_chains` is
+        needed) -> (lengths, S2, S2_err, p_match): S2 = -ln(mean swap), its
+        standard error over the pairs, and the fraction of pairs whose
+        replicas hold the same number of particles in A_k (the others
+        contribute swap = 0).  Computed on the rows resident on the device
+        after either move type; the chains are not touched.  The chains sample
+        the trial wave function, so S2 is the variational entropy of the
+        Bijl-Jastrow state.  In a lattice origin = -barrier_width / 2 puts the
+        cut in mid-barrier (segments of whole sites)."""
+        ln = renyi_lengths(self.model_spec.supercell_size, lengths)
+        parts = self.ensemble.renyi_parts(ln, origin)
+        return (ln,) + renyi_entropy(parts, self.num_chains // 2)
 
     def close(self):
         self.ensemble.close()
