@@ -393,6 +393,42 @@ int qmc_renyi_swap_reduce_dev(qmc_engine *eng, int64_t nconf,
                               const double *lengths_dev, double origin,
                               double *sums_dev);
 
+/* Purity of the one-body density matrix by a one-particle replica swap (no
+ * counterpart in the reference).  The configurations 2p and 2p + 1 of
+ * pos[nconf][N] (nconf even, N <= 512) are the replicas R1 = x1, R2 = x2 of
+ * pair p, in any particle order.  For the exchange x1_i <-> x2_j,
+ *   log_ratio[nconf / 2][N][N] =
+ *       ln|psi(R1')| + ln|psi(R2')| - ln|psi(R1)| - ln|psi(R2)|,
+ * R1' being R1 with its particle i replaced by particle j of R2 and R2' the
+ * converse, formed from the pair factors alone (the one-body factors cancel
+ * identically: exactly 0 without interactions), and
+ *   mean[nconf / 2] = N^-2 sum_ij exp(log_ratio[p][i][j])
+ * (the argument of exp clamped to +-700), a symmetric function of each row:
+ * the order of the particles in a row does not matter.  Over P independent
+ * pairs drawn from |psi|^2, sum_p mean[p] / P = Tr rho1^2 = sum_k lambda_k^2,
+ * the purity of the one-body density matrix normalised to trace 1, and
+ * S2 = -ln Tr rho1^2 the particle-partition Renyi-2 entropy at n = 1; the
+ * condensate fraction obeys Tr rho1^2 <= lambda_max <= sqrt(Tr rho1^2).  For
+ * VMC chains this is the variational purity of the trial wave function.
+ * Positions enter through their images in [0, L).  Two particles of the same
+ * row at the same place (psi = 0) are undefined.  Always fp64:
+ * qmc_engine_set_fast_math does not apply (csrc/qmc_partent.h).
+ * qmc_particle_swap: host buffers, synchronous; either output may be NULL, not
+ * both.  An odd or non-positive nconf or a NULL pos is an error (N is at
+ * most 512 for every engine). */
+int qmc_particle_swap(qmc_engine *eng, int64_t nconf, const double *pos,
+                      double *mean, double *log_ratio);
+/* Same on device-resident buffers, asynchronous on the engine's stream. */
+int qmc_particle_swap_dev(qmc_engine *eng, int64_t nconf,
+                          const double *pos_dev, double *mean_dev,
+                          double *log_ratio_dev);
+/* Sums over the P = nconf / 2 pairs, device buffers, asynchronous:
+ * sums_dev[3] = sum_p mean[p], sum_p mean[p]^2, P.  Fixed summation order: two
+ * calls give the same bits; the per-pair means live in an engine-owned scratch
+ * filled in tiles of at most 2^16 pairs. */
+int qmc_particle_swap_reduce_dev(qmc_engine *eng, int64_t nconf,
+                                 const double *pos_dev, double *sums_dev);
+
 /* Plain device buffers, so that a configuration set can stay resident across
  * many qmc_evaluate_dev calls with different engines: the correlated-sampling
  * optimiser re-evaluates wf_abs_log / energy of one fixed set for every trial
@@ -462,6 +498,13 @@ int qmc_vmc_triple_dist(qmc_vmc *v, int32_t num_bins, double max_span,
  * checked as by qmc_renyi_swap. */
 int qmc_vmc_renyi_swap(qmc_vmc *v, int32_t nlen, const double *lengths,
                        double origin, double *out);
+/* One-particle swap sums of the CURRENT configurations, the chains 2p and
+ * 2p + 1 being the replicas of pair p: out[3] as sums_dev of
+ * qmc_particle_swap_reduce_dev, on the resident rows, after either move type
+ * (the estimator does not depend on the order of a row); no position leaves
+ * the device and the chain state is not touched.  An odd num_chains is an
+ * error.  Host buffer; synchronous. */
+int qmc_vmc_particle_swap(qmc_vmc *v, double *out);
 /* Device addresses of the per-chain block sums of the last block
  * (sum_e[W], sum_e2[W], n_acc[W]) for on-device reductions / collectives. */
 int qmc_vmc_block_sums_dev(qmc_vmc *v, double **sum_e, double **sum_e2,

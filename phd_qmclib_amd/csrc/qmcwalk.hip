@@ -13,6 +13,7 @@
 #include "qmc_pairdist.h"
 #include "qmc_tripledist.h"
 #include "qmc_renyi.h"
+#include "qmc_partent.h"
 #include "qmc_cmdiff.h"
 #include "qmc_isf.h"
 #include "qmc_site.h"
@@ -126,6 +127,9 @@ struct qmc_engine {
     // (swap, matched), their column sums, and the lengths and sums of
     // qmc_vmc_renyi_swap
     DevBuf<double> ry_rows, ry_colsum, ry_vmc;
+    // one-particle swap scratch (qmc_particle_swap*): the per-pair tile of
+    // means and the sums of qmc_vmc_particle_swap
+    DevBuf<double> pe_mean, pe_vmc;
 
     qmc_engine() = default;
     qmc_engine(const qmc_engine &) = delete;
@@ -2001,6 +2005,120 @@ extern "C" int qmc_vmc_renyi_swap(qmc_vmc *v, int32_t nlen,
     int rc = qmc_renyi_swap_reduce_dev(e, v->W, v->pos, nlen, dlen, origin,
                                        e->ry_vmc);
     return rc ? rc : read_doubles(e, out, e->ry_vmc, 3 * K);
+}
+
+
+// ---- one-particle replica swap (csrc/qmc_partent.h) -----------------------
+// Tiles of at most PD_TILE pairs, one mean per pair.
+static int partent_check(const char *who, int64_t nconf)
+{
+    if (nconf <= 0 || (nconf & 1))
+        return fail(std::string(who) +
+                    ": nconf must be positive and even (replica pairs)");
+    return 0;
+}
+
+// npair device-resident replica pairs -> mean and / or log_ratio
+static int partent_launch(qmc_engine *e, long long npair,
+                          const double *pos_dev, double *mean,
+                          double *log_ratio)
+{
+    const size_t n = (size_t)e->dm.n;
+    const size_t lds = partent_lds_bytes(e->dm.n);
+    if (lds > PARTENT_LDS_LIMIT)
+        return fail("qmc_particle_swap: boson_number too large for the LDS of "
+                    "a workgroup");
+    allow_lds(particle_swap_kernel, lds);       // 40 KB at N = 512
+    const long long xmax = 1ll << 30;
+    for (long long p0 = 0; p0 < npair; p0 += xmax) {
+        const long long np = std::min(xmax, npair - p0);
+        PartEntArgs a{ pos_dev + (size_t)p0 * 2 * n,
+                       mean ? mean + p0 : nullptr,
+                       log_ratio ? log_ratio + (size_t)p0 * n * n : nullptr,
+                       np };
+        hipLaunchKernelGGL(particle_swap_kernel, dim3((unsigned)np), dim3(64),
+                           lds, e->stream, e->dm_dev, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int qmc_particle_swap_dev(qmc_engine *e, int64_t nconf,
+                                     const double *pos, double *mean,
+                                     double *log_ratio)
+{
+    if (!e || !pos || (!mean && !log_ratio))
+        return fail("qmc_particle_swap_dev: null argument");
+    if (partent_check("qmc_particle_swap_dev", nconf)) return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    return partent_launch(e, nconf / 2, pos, mean, log_ratio);
+}
+
+extern "C" int qmc_particle_swap_reduce_dev(qmc_engine *e, int64_t nconf,
+                                            const double *pos, double *sums)
+{
+    if (!e || !pos || !sums)
+        return fail("qmc_particle_swap_reduce_dev: null argument");
+    if (partent_check("qmc_particle_swap_reduce_dev", nconf)) return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n2 = 2 * (size_t)e->dm.n;
+    const long long npair = nconf / 2;
+    const long long tile = std::min(npair, PD_TILE);
+    if (e->pe_mean.reserve((size_t)tile)) return 1;
+    // one column: sums[0..1] = sum m, sum m^2, and the count of rows in
+    // sums[2] (the weight sum of unweighted rows)
+    return reduce_tiles(e, npair, tile, e->pe_mean, nullptr, 1, sums, sums + 2,
+                        [&](long long p0, long long np) {
+        return partent_launch(e, np, pos + (size_t)p0 * n2, e->pe_mean.get(),
+                              nullptr);
+    });
+}
+
+extern "C" int qmc_particle_swap(qmc_engine *e, int64_t nconf,
+                                 const double *pos, double *mean,
+                                 double *log_ratio)
+{
+    if (!e || !pos || (!mean && !log_ratio))
+        return fail("qmc_particle_swap: null argument");
+    if (partent_check("qmc_particle_swap", nconf)) return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n = (size_t)e->dm.n;
+    // an even number of configurations to a tile: whole pairs; a pair holds
+    // N^2 doubles of log_ratio, half of them to a configuration
+    const long long per_conf =
+        log_ratio ? (long long)std::max<size_t>(n * n / 2, n) : (long long)n;
+    const long long tile = std::max<long long>(
+        2, std::min<long long>(nconf, PD_SCRATCH_ELEMS / per_conf) & ~1ll);
+    DevBuf<double> dpos, dmean, dlr;
+    if (dpos.alloc((size_t)tile * n) ||
+        (mean && dmean.alloc((size_t)(tile / 2))) ||
+        (log_ratio && dlr.alloc((size_t)(tile / 2) * n * n)))
+        return 1;
+    return run_host_tiles(e, nconf, tile, pos, dpos,
+                          { { mean, dmean.get(), sizeof(double) / 2 },
+                            { log_ratio, dlr.get(),
+                              n * n * sizeof(double) / 2 } },
+                          [&](long long nc) {
+        return partent_launch(e, nc / 2, dpos, dmean.get(), dlr.get());
+    });
+}
+
+// Sums of the CURRENT configurations of the chains, chains 2p and 2p + 1 the
+// replicas of pair p, on the resident rows (the estimator is symmetric in the
+// particles of a row, so neither the position order of the 'all' rows nor the
+// label order of the 'particle' rows matters); the chain state is only read.
+extern "C" int qmc_vmc_particle_swap(qmc_vmc *v, double *out)
+{
+    if (!v || !out) return fail("qmc_vmc_particle_swap: null argument");
+    qmc_engine *e = v->eng;
+    if (v->W & 1)
+        return fail("qmc_vmc_particle_swap: an odd number of chains has no "
+                    "replica pairs");
+    if (partent_check("qmc_vmc_particle_swap", v->W)) return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    if (e->pe_vmc.reserve(3)) return 1;
+    int rc = qmc_particle_swap_reduce_dev(e, v->W, v->pos, e->pe_vmc);
+    return rc ? rc : read_doubles(e, out, e->pe_vmc, 3);
 }
 
 

@@ -161,6 +161,29 @@ def renyi_entropy(sums, num_pairs):
         return -np.log(mean), stderr / mean, sums[:, 2] / p
 
 
+def particle_entropy(sums, num_pairs):
+    """One-particle Renyi-2 entropy from the one-particle swap
+    sums[3] = sum m, sum m^2, P over `num_pairs` = P replica pairs
+    -> (S2, S2_err, purity, purity_err): purity = mean m = Tr rho1^2 (rho1 of
+    trace 1), its standard error over the pairs, S2 = -ln purity and
+    S2_err = purity_err / purity.  The condensate fraction lies in
+    [purity, sqrt(purity)]."""
+    sums = np.asarray(sums, dtype=np.float64)
+    p = int(num_pairs)
+    if sums.shape != (3,):
+        raise ValueError('sums[3] expected')
+    if p != num_pairs or p < 1:
+        raise ValueError('num_pairs must be a positive integer')
+    if sums[2] != p:
+        raise ValueError('sums[2] is not num_pairs')
+    mean = sums[0] / p
+    var = max(sums[1] / p - mean ** 2, 0.0)
+    stderr = np.sqrt(var / max(p - 1, 1))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return (float(-np.log(mean)), float(stderr / mean), float(mean),
+                float(stderr))
+
+
 def superfluid_ratio(iter_cm, num_walkers, boson_number, time_step):
     """The normalised centre-of-mass diffusion curve of one estimator block,
     iter_cm[nts, 2] (`DmcEnsemble.read_cm_diffusion`) and num_walkers[nts]:
@@ -697,6 +720,39 @@ class ModelEngine:
             self._h, self._num_replicas(nconf), pos_ptr, int(nlen),
             lengths_ptr, _renyi_origin(origin), sums_ptr))
 
+    def particle_swap(self, pos, matrix=False):
+        """One-particle replica swap between the rows (2p, 2p + 1) of
+        pos[W, N], W even, N <= 512 -> mean[W / 2], or with `matrix`
+        (mean, log_ratio[W / 2, N, N]): log_ratio[p, i, j] is
+        ln|psi(R1') psi(R2') / (psi(R1) psi(R2))| for the exchange of particle
+        i of row 2p with particle j of row 2p + 1, and mean[p] the average of
+        exp(log_ratio[p]) over all N^2 exchanges, which does not depend on the
+        order of the particles in a row.  The mean over independent pairs drawn
+        from |psi|^2 is the purity Tr rho1^2 of the one-body density matrix
+        (`particle_entropy`)."""
+        pos = _pos2d(pos, self.num_particles)
+        W, n = self._num_replicas(pos.shape[0]), self.num_particles
+        mean = np.zeros(W // 2)
+        log_ratio = np.zeros((W // 2, n, n)) if matrix else None
+        check(self._lib.qmc_particle_swap(self._h, W, ptr(pos), ptr(mean),
+                                          ptr(log_ratio)))
+        return (mean, log_ratio) if matrix else mean
+
+    def particle_swap_dev(self, nconf, pos_ptr, mean_ptr, log_ratio_ptr):
+        """Asynchronous one-particle swap on device-resident buffers (raw
+        pointers): pos[nconf, N] -> mean[nconf / 2] and
+        log_ratio[nconf / 2, N, N]; either output may be 0."""
+        check(self._lib.qmc_particle_swap_dev(
+            self._h, self._num_replicas(nconf), pos_ptr, mean_ptr,
+            log_ratio_ptr))
+
+    def particle_swap_reduce_dev(self, nconf, pos_ptr, sums_ptr):
+        """Asynchronous sums over the P = nconf / 2 replica pairs, device
+        buffers: sums[3] = sum mean, sum mean^2, P, in a fixed summation order
+        (`particle_entropy` turns them into the purity and S2)."""
+        check(self._lib.qmc_particle_swap_reduce_dev(
+            self._h, self._num_replicas(nconf), pos_ptr, sums_ptr))
+
 
 #: VmcEnsemble(move=...) -> qmc_vmc_params.gaussian (the proposal code;
 #: 1 is the Gaussian all-particle proposal, `gaussian=True`)
@@ -806,6 +862,17 @@ class VmcEnsemble:
         out = np.zeros((ln.size, 3))
         check(self._lib.qmc_vmc_renyi_swap(self._h, ln.size, ptr(ln), a0,
                                            ptr(out)))
+        return out
+
+    def particle_swap_parts(self) -> np.ndarray:
+        """One-particle swap sums of the current configurations, the chains 2p
+        and 2p + 1 being the replicas of pair p -> [3] = sum mean,
+        sum mean^2, pairs (`ModelEngine.particle_swap_reduce_dev`); computed
+        on the resident rows, which are only read.  An odd number of chains is
+        a ValueError."""
+        ModelEngine._num_replicas(self.num_chains)
+        out = np.zeros(3)
+        check(self._lib.qmc_vmc_particle_swap(self._h, ptr(out)))
         return out
 
     def get_state(self):

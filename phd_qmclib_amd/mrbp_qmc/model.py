@@ -373,6 +373,7 @@ class PhysicalFuncs:
         pair_distribution(num_bins, sys_conf)  (ns,nop)->(B)
         triple_distribution(num_bins, sys_conf)  (ns,nop)->(B)
         renyi_swap(lengths, sys_conf)     (2,ns,nop)->(K)
+        particle_swap(sys_conf)           (2,ns,nop)->()
         fourier_density(kz_set, sys_conf) (nkz),(ns,nop)->(nkz)   complex
 
     The loop dimensions broadcast as NumPy's; the whole broadcast batch goes to
@@ -484,6 +485,25 @@ class PhysicalFuncs:
         swap = np.exp(np.clip(log_ratio, -700.0, 700.0))
         swap[np.isneginf(log_ratio)] = 0.0
         return swap.reshape(loop[:-1] + swap.shape[-1:])
+
+    def particle_swap(self, sys_conf):
+        """One-particle replica-swap ratio: for the two replicas
+        sys_conf[..., 0, :, :] and sys_conf[..., 1, :, :], the average of
+        |psi(R1') psi(R2') / (psi(R1) psi(R2))| over all N^2 exchanges of one
+        particle of the first with one particle of the second (the order of
+        the particles in a configuration does not matter).  The mean over
+        independent pairs drawn from |psi|^2 is the purity Tr rho1^2 of the
+        one-body density matrix (trace 1) and minus its logarithm the
+        particle-partition Renyi-2 entropy at n = 1: psi is the trial wave
+        function, so this is the variational purity of the Bijl-Jastrow state.
+        The loop dimensions of sys_conf in front of the replica axis
+        broadcast."""
+        sys_conf = np.asarray(sys_conf, dtype=np.float64)
+        if sys_conf.ndim < 3 or sys_conf.shape[-3] != 2:
+            raise ValueError('sys_conf must have the core shape (2, ns, nop)')
+        loop, pos = self._conf_batch(sys_conf)
+        mean = self._engine().particle_swap(pos)
+        return mean.reshape(loop[:-1])[()]
 
     def fourier_density(self, kz_set, sys_conf):
         """Fourier density component with momentum k: sum_i exp(i k z_i)."""

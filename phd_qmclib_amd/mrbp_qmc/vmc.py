@@ -18,7 +18,8 @@ import numpy as np
 
 from .. import utils
 from ..engine import (ModelEngine, VmcEnsemble, pair_distribution_bins,
-                      pair_distribution_norm, renyi_entropy, renyi_lengths,
+                      pair_distribution_norm, particle_entropy, renyi_entropy,
+                      renyi_lengths,
                       triple_distribution_bins, triple_distribution_norm)
 from ..qmc_base import vmc as vmc_base
 from . import model
@@ -371,6 +372,23 @@ class EnsembleSampling:
         ln = renyi_lengths(self.model_spec.supercell_size, lengths)
         parts = self.ensemble.renyi_parts(ln, origin)
         return (ln,) + renyi_entropy(parts, self.num_chains // 2)
+
+    def particle_entropy(self):
+        """Purity of the one-body density matrix and the one-particle
+        (particle-partition, n = 1) Renyi-2 entropy by replica swap over the
+        chains' current configurations, the chains 2p and 2p + 1 being the two
+        replicas of pair p (independent chains: an even `num_chains` is
+        needed) -> (S2, S2_err, purity, purity_err): purity = Tr rho1^2 =
+        sum_k lambda_k^2 over the occupations of the natural orbitals (rho1 of
+        trace 1), S2 = -ln purity, the errors over the pairs.  Every pair
+        averages over all N^2 one-particle exchanges, so neither the position
+        order of the resident rows nor an ordered start biases it; the chains
+        are not touched.  The condensate fraction n0 / N = lambda_max obeys
+        purity <= n0 / N <= sqrt(purity).  The chains sample the trial wave
+        function, so this is the variational purity of the Bijl-Jastrow
+        state."""
+        parts = self.ensemble.particle_swap_parts()
+        return particle_entropy(parts, self.num_chains // 2)
 
     def close(self):
         self.ensemble.close()
