@@ -17,6 +17,23 @@ Y_t[s] is N times the unwrapped displacement of the centre of mass of walker s
 since the first step of the block: a clone inherits the Y of its parent, a dead
 walker's history ends.  X does not change under a permutation of a row, and a
 wrap of one particle by L moves raw by L, which the minimum image takes out.
+
+Rounding bound of a comparison with the kernel (`tolerance`).  The kernel sums
+the N differences c_i - p_i of two rows, the restatement subtracts the sums of
+two yielded rows; every term is below L in magnitude and every partial sum
+below N L, so any order of either sum errs by at most g = 4 N^2 L 2^-53 (N
+additions, each off by at most half an ulp of N L, on both sides, with a factor
+two to spare), and as long as both pick the same image (the callers assert
+max |d| < L / 4) the minimum image step does not add to it.  Y_t is a sum of at
+most T such steps: |Y - Y'| <= T g.  Hence, per row,
+
+    |sum_s Y   - sum_s Y'  | <= nw T g
+    |sum_s Y^2 - sum_s Y'^2| <= nw 2 max|Y| T g
+
+(the second to first order in T g, which is below 1e-9 in the suite).  The sums
+over the walkers themselves, in whatever order, err by at most nw 2^-53 times
+their largest partial sum, nw max|Y| or nw max|Y|^2: that fits into the factor
+two spared above as long as nw max|Y| <= 2 T N^2 L, which `tolerance` asserts.
 """
 import numpy as np
 
@@ -62,3 +79,14 @@ def cm_diffusion(steps, sc_size):
 def largest_y(steps, sc_size):
     """The largest |Y_t[s]| of the block (for rounding bounds)."""
     return _walk(steps, sc_size)[3]
+
+
+def tolerance(steps, n, sc_size):
+    """tol[T, 2] of the module docstring, for the rows of a block of T =
+    len(steps) steps of N = n particles."""
+    L, T = float(sc_size), len(steps)
+    g = 4.0 * n * n * L * 2.0 ** -53
+    nw = np.array([s[2] for s in steps], dtype=np.float64)
+    max_y = largest_y(steps, L)
+    assert nw.max() * max_y <= 2.0 * T * n * n * L
+    return np.stack([nw * T * g, nw * 2.0 * max_y * T * g], axis=1)

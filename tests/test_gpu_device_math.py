@@ -19,7 +19,8 @@ import os
 import numpy as np
 import pytest
 
-from .test_gpu_parity import RTOL, close, spec_from_golden, worst
+from ._models import spec_from_golden
+from .test_gpu_parity import RTOL, close, worst
 
 mpmath = pytest.importorskip('mpmath')
 mp = mpmath.mp

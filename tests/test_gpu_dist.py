@@ -2,21 +2,13 @@
 two in-process shards): stream sharing with torch, the split-step estimators,
 and the population rebalance (walker records carry the forward-walking rows,
 spare normals are not inherited, everything is stream-ordered)."""
-from math import pi
 
 import numpy as np
 import pytest
 
+from ._models import box
+
 pytestmark = pytest.mark.gpu
-
-
-def box(n=16, **kw):
-    from phd_qmclib_amd import mrbp_qmc
-    args = dict(lattice_depth=5 * pi ** 2, lattice_ratio=1,
-                interaction_strength=2, boson_number=n, supercell_size=n,
-                tbf_contact_cutoff=0.25 * n)
-    args.update(kw)
-    return mrbp_qmc.Spec(**args)
 
 
 def test_engine_launches_on_the_callers_stream():

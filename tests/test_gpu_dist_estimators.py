@@ -10,11 +10,10 @@ per-step `(confs, cloning_ref, num_walkers)` of `get_state()`:
 * g2(r) and the site statistics, both pure: integers until the one division,
   compared with `array_equal` (tests/test_gpu_pairdist_est.py,
   tests/test_gpu_site_est.py);
-* the centre-of-mass diffusion: the bound of tests/test_gpu_superfluid_est.py,
+* the centre-of-mass diffusion: `tolerance` of tests/_cmdiff_restatement.py,
   g = 4 N^2 L 2^-53 per step and walker, T g per walker after T steps,
   (nw T g, nw 2 max|Y| T g) for a row;
-* F(k, tau): `isf_tolerance` below is the bound derived in
-  tests/test_gpu_isf_est.py (its module docstring), restated;
+* F(k, tau): `tolerance` of tests/_isf_restatement.py;
 * g1(s): 2e-11 sum_s max(1, |g1_s|), the definition's bound of
   tests/test_gpu_obdm_est.py.
 
@@ -28,20 +27,22 @@ pos 16 | drift 16 | label 16 | energy | log-weight | S(k) 24 | density 12 |
 g2 10 | centre of mass 1 | F(k, tau) 12 | site 13.
 """
 import types
-from math import pi
+from typing import NamedTuple
 
 import numpy as np
 import pytest
 
 from . import _cmdiff_restatement as cm
+from . import _dmc_walks as walks
 from . import _isf_restatement as isf
 from . import _obdm_restatement as obdm
 from . import _pairdist_fw_restatement as fw
 from . import _site_restatement as sr
+from ._dmc_walks import EST, TIME_STEP, WALKS
+from ._models import model_dict
 
 pytestmark = pytest.mark.gpu
 
-TIME_STEP = 1e-3
 EPS = 2.0 ** -53
 RATIO = 1
 HALF_ZB = sr.half_barrier(RATIO)
@@ -52,52 +53,37 @@ SHIFTS = (0.0, 0.5, 1.25)
 G1_STRIDE = 2
 KEYS = ('pair_dist', 'cm_diffusion', 'isf', 'obdm', 'site')
 
-# tag: (N, L, start walkers, cap, steps, contact cutoff / L, seed, (K, T, q)
-# of F(k, tau)).  `wide`: two label passes per wavefront, N no multiple of 64,
-# and the widest row there is, 16 x (62 + 2) = 1024 doubles per walker.
+
+class Shape(NamedTuple):
+    steps: int
+    ktq: tuple                  # (K, T, q) of F(k, tau)
+
+
+# The walks of the same names.  `wide`: the widest row there is,
+# 16 x (62 + 2) = 1024 doubles per walker.
 SHAPES = {
-    'small': (16, 16, 250, 512, 12, 0.25, 41, (3, 2, 2)),
-    'wide':  (100, 200, 64, 96, 8, 0.1, 42, (16, 62, 1)),
+    'small': Shape(12, (3, 2, 2)),
+    'wide':  Shape(8, (16, 62, 1)),
 }
-
-
-def box(n, sites, cut=0.25):
-    """As tests/test_gpu_site_est.py."""
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    return Spec(lattice_depth=5 * pi ** 2, lattice_ratio=RATIO,
-                interaction_strength=2, boson_number=n, supercell_size=sites,
-                tbf_contact_cutoff=cut * sites)
 
 
 def make_engine(shape):
     import torch
-    from phd_qmclib_amd.engine import ModelEngine
-    n, L, _, _, _, cut, _, _ = SHAPES[shape]
-    return ModelEngine(box(n, L, cut).cfc_spec,
-                       stream=torch.cuda.current_stream().cuda_stream)
+    return walks.engine(WALKS[shape],
+                        stream=torch.cuda.current_stream().cuda_stream)
 
 
 def make_ensemble(eng, shape, **kw):
-    from phd_qmclib_amd.engine import DmcEnsemble
-    n, L, nw0, maxw, _, _, seed, _ = SHAPES[shape]
-    d = DmcEnsemble(eng, TIME_STEP, maxw, nw0, 0.5, rng_seed=seed, **kw)
-    d.set_state(L * np.random.RandomState(seed).random_sample((nw0, n)))
-    return d
+    return walks.ensemble(eng, WALKS[shape], **kw)
 
 
 def set_all(d, ktq, pure=True):
-    d.set_estimators(num_modes=8, ssf_pure=True, ssf_pfw=PFW, num_bins=12,
-                     dens_pure=False)
+    d.set_estimators(**EST)
     d.set_pair_dist_estimator(G2_BINS, pure=pure, pfw=PFW)
     d.set_site_estimator(SITE_P, SITE_D, pure=pure, pfw=PFW)
     d.set_cm_diffusion_estimator(True)
     d.set_isf_estimator(*ktq)
     d.set_obdm_estimator(SHIFTS, G1_STRIDE)
-
-
-def record_state(d):
-    s = d.get_state()
-    return (s.confs[:, 0, :].copy(), s.cloning_ref.copy(), int(s.num_walkers))
 
 
 def export(d, first, count):
@@ -108,29 +94,6 @@ def export(d, first, count):
     d.export_walkers(first, count, buf.data_ptr())
     d.engine.sync()
     return buf, buf.cpu().numpy().reshape(count, rec)
-
-
-def isf_tolerance(n, K, T, num_walkers):
-    """tol[nts, K, T + 2]: the bound of tests/test_gpu_isf_est.py."""
-    m = np.arange(K, dtype=np.float64)
-    delta = (12.0 * pi * m + 243.0) * EPS
-    d = n * delta + 3.0 * n * n * EPS
-    qd = 2.0 * n * d * (1.0 + 1e-6) + 6.0 * n * n * EPS
-    nw = np.asarray(num_walkers, dtype=np.float64)[:, None]
-    tol = np.empty((len(nw), K, T + 2))
-    tol[:, :, :T] = (nw * qd + nw * nw * n * n * EPS)[:, :, None]
-    tol[:, :, T:] = (nw * d + nw * nw * n * EPS)[:, :, None]
-    return tol
-
-
-def cm_tolerance(steps, n, L):
-    """tol[nts, 2]: the bound of tests/test_gpu_superfluid_est.py."""
-    T = len(steps)
-    g = 4.0 * n * n * L * EPS
-    nw = np.array([s[2] for s in steps], dtype=np.float64)
-    max_y = cm.largest_y(steps, L)
-    assert nw.max() * max_y <= 2.0 * T * n * n * L
-    return np.stack([nw * T * g, nw * 2.0 * max_y * T * g], axis=1)
 
 
 def cm_per_walker(steps, L):
@@ -153,8 +116,7 @@ def cm_per_walker(steps, L):
 
 def restate(steps, shape, which=('pair_dist', 'site', 'cm_diffusion', 'isf')):
     """-> dict key: (rows, tolerance or None where they are exact)."""
-    n, L, _, _, _, _, _, ktq = SHAPES[shape]
-    L = float(L)
+    n, L, ktq = WALKS[shape].n, float(WALKS[shape].sites), SHAPES[shape].ktq
     nws = [s[2] for s in steps]
     out = {}
     if 'pair_dist' in which:
@@ -164,10 +126,10 @@ def restate(steps, shape, which=('pair_dist', 'site', 'cm_diffusion', 'isf')):
                                        PFW)[1], None)
     if 'cm_diffusion' in which:
         out['cm_diffusion'] = (cm.cm_diffusion(steps, L)[0],
-                               cm_tolerance(steps, n, L))
+                               cm.tolerance(steps, n, L))
     if 'isf' in which:
         out['isf'] = (isf.isf_rows(steps, L, *ktq),
-                      isf_tolerance(n, ktq[0], ktq[1], nws))
+                      isf.tolerance(n, ktq[0], ktq[1], nws))
     return out
 
 
@@ -231,8 +193,7 @@ def test_record_of_ssf_and_density_alone_does_not_change_with_the_switch():
     from phd_qmclib_amd.dist import DistributedDmc
     eng = make_engine('small')
     d = make_ensemble(eng, 'small', external_reduce=True)
-    d.set_estimators(num_modes=8, ssf_pure=True, ssf_pfw=PFW, num_bins=12,
-                     dens_pure=True, dens_pfw=PFW)
+    d.set_estimators(**dict(EST, dens_pure=True, dens_pfw=PFW))
     dd = DistributedDmc(d, 16, 'cuda', rebalance_every=0)
     d.est_begin_block(4)
     for t in range(3):
@@ -254,7 +215,8 @@ def test_record_of_ssf_and_density_alone_does_not_change_with_the_switch():
 def test_pack_reads_the_rows_of_the_last_estimator_step():
     from phd_qmclib_amd.dist import DistributedDmc
     shape = 'small'
-    n, L, _, _, nts, _, _, (K, T, q) = SHAPES[shape]
+    n, L, nts = WALKS[shape].n, WALKS[shape].sites, SHAPES[shape].steps
+    K, T, q = SHAPES[shape].ktq
     eng = make_engine(shape)
     d = make_ensemble(eng, shape, external_reduce=True)
     set_all(d, (K, T, q))
@@ -268,7 +230,7 @@ def test_pack_reads_the_rows_of_the_last_estimator_step():
     for t in range(nts):
         dd.step()
         d.step_estimators(t)
-        steps.append(record_state(d))
+        steps.append(walks.state_of(d))
         if t in (4, 5):                 # written to rows buffer 0, buffer 1
             recs = export(d, 0, steps[-1][2])[1]
             rows = read_all(d, nts)
@@ -278,7 +240,7 @@ def test_pack_reads_the_rows_of_the_last_estimator_step():
             got = recs[:, o_site:].sum(axis=0) / div
             assert np.array_equal(got, rows['site'][t]) and got.any()
             got = recs[:, o_isf:o_site].sum(axis=0).reshape(K, T + 2)
-            tol = isf_tolerance(n, K, T, [steps[-1][2]])[0]
+            tol = isf.tolerance(n, K, T, [steps[-1][2]])[0]
             assert (np.abs(got - rows['isf'][t]) <= tol).all()
             assert got[:, :2].all() and got[1:].all()
             packed[t] = recs[:, o_cm].copy()
@@ -301,7 +263,8 @@ def swapped_run(shape, when, k, isf_only):
     """-> (steps as recorded, pi, device rows)."""
     import torch
     from phd_qmclib_amd.dist import DistributedDmc
-    n, L, _, maxw, nts, _, _, ktq = SHAPES[shape]
+    n, maxw = WALKS[shape].n, WALKS[shape].maxw
+    nts, ktq = SHAPES[shape].steps, SHAPES[shape].ktq
     eng = make_engine(shape)
     d = make_ensemble(eng, shape, external_reduce=True)
     if isf_only:
@@ -330,7 +293,7 @@ def swapped_run(shape, when, k, isf_only):
             torch.cuda.synchronize()
         dd.step()
         d.step_estimators(t)
-        steps.append(record_state(d))
+        steps.append(walks.state_of(d))
     rows = {'isf': d.read_isf(nts)} if isf_only else read_all(d, nts)
     d.close()
     eng.close()
@@ -363,12 +326,6 @@ def test_imported_rows_follow_the_walker_not_the_slot(shape, when, k):
 
 # ---- 4. two shards, one population -----------------------------------------
 
-def _model_dict(cfc):
-    return {'params': cfc.model_params._asdict(),
-            'obf_params': cfc.obf_params._asdict(),
-            'tbf_params': cfc.tbf_params._asdict()}
-
-
 def test_two_shards_sum_to_the_union():
     """Set up as test_gpu_dist.py::test_two_shards_one_population: 90 and 30
     walkers, one target of 120 and one E_ref; 30 tail walkers go from a to b
@@ -378,8 +335,8 @@ def test_two_shards_sum_to_the_union():
     from phd_qmclib_amd.engine import DmcEnsemble
     from phd_qmclib_amd.qmc_base import dmc_est
     shape = 'small'
-    n, L, _, _, nts, _, _, ktq = SHAPES[shape]
-    L, cap, k = float(L), 160, 30
+    n, nts, ktq = WALKS[shape].n, SHAPES[shape].steps, SHAPES[shape].ktq
+    L, cap, k = float(WALKS[shape].sites), 160, 30
     eng = make_engine(shape)
     pos = [L * np.random.RandomState(s).random_sample((w, n))
            for s, w in ((21, 90), (22, 30))]
@@ -425,7 +382,7 @@ def test_two_shards_sum_to_the_union():
             h.step_finish(part[2].data_ptr())
         for h in shards:
             h.step_estimators(t)
-        (ca, ra, na), (cb, rb, nb) = record_state(a), record_state(b)
+        (ca, ra, na), (cb, rb, nb) = walks.state_of(a), walks.state_of(b)
         ref = perm[np.concatenate([ra[:na], rb[:nb] + shift_b])]
         union.append((np.concatenate([ca[:na], cb[:nb]]), ref, na + nb))
         prev = (na, nb)
@@ -455,7 +412,7 @@ def test_two_shards_sum_to_the_union():
     # both shards took part, and the transfer mattered
     assert min(prev) > 20
     # g1: the definition on the union's configurations of the evaluated steps
-    p, sh = _model_dict(box(n, int(L)).cfc_spec), np.array(SHIFTS)
+    p, sh = model_dict(walks.spec(WALKS[shape]).cfc_spec), np.array(SHIFTS)
     for t in range(nts):
         if t % G1_STRIDE:
             assert not got['obdm'][t].any()
@@ -497,10 +454,9 @@ def _process_group():
 def test_world_of_one_reads_the_single_gpu_rows():
     import torch
     from phd_qmclib_amd.dist import DistributedDmc
-    from phd_qmclib_amd.engine import ModelEngine
     from phd_qmclib_amd.qmc_base import dmc_est
     shape = 'small'
-    n, L, _, _, _, cut, _, ktq = SHAPES[shape]
+    n, ktq = WALKS[shape].n, SHAPES[shape].ktq
     nts = 20
     spec = types.SimpleNamespace(as_pure_est=True, eval_stride=G1_STRIDE)
     table = {e.key: e for e in dmc_est.ESTIMATORS}
@@ -508,8 +464,7 @@ def test_world_of_one_reads_the_single_gpu_rows():
     try:
         side = torch.cuda.Stream()
         with torch.cuda.stream(side):
-            eng = ModelEngine(box(n, L, cut).cfc_spec,
-                              stream=side.cuda_stream)
+            eng = walks.engine(WALKS[shape], stream=side.cuda_stream)
             a = make_ensemble(eng, shape)
             b = make_ensemble(eng, shape, external_reduce=True)
             for h in (a, b):

@@ -24,10 +24,12 @@ TAU was chosen from the linear runs alone, so that the second assertion holds
 with room to spare; DESIGN.md quotes the measured figures, E_quad(4e-3) and
 E_quad(8e-3) (reported by tools/dmc2_timestep.py, not asserted) included.
 """
-from math import pi, sqrt
+from math import sqrt
 
 import numpy as np
 import pytest
+
+from ._models import box
 
 pytestmark = pytest.mark.gpu
 
@@ -37,13 +39,6 @@ SEEDS = (1, 2, 3)
 TAU = 24.0                      # imaginary time of every run
 BLOCK_TAU = 0.032               # ... of a block: 64 steps of 5e-4, 4 of 8e-3
 DISCARD = 1.0 / 6.0
-
-
-def box(n):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    return Spec(lattice_depth=5 * pi ** 2, lattice_ratio=1,
-                interaction_strength=2, boson_number=n, supercell_size=n,
-                tbf_contact_cutoff=0.25 * n)
 
 
 def start(seed, walkers=TARGET, n=N):

@@ -32,25 +32,18 @@ match exactly; energies to the tolerances the suite already uses for
 equal-seed runs (1e-9 relative for the series, 2e-11 max(1, |x|) for walker
 energies, 1e-10 for configurations).
 """
-from math import pi
 
 import numpy as np
 import pytest
 
 from . import _branch_ref as br
+from ._models import box
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 2e-11
 SEED = 7
 KAPPA = 0.5
-
-
-def box(n):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    return Spec(lattice_depth=5 * pi ** 2, lattice_ratio=1,
-                interaction_strength=2, boson_number=n, supercell_size=n,
-                tbf_contact_cutoff=0.25 * n)
 
 
 def close(a, b, rtol=RTOL):

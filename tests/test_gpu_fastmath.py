@@ -30,6 +30,7 @@ import numpy as np
 import pytest
 
 from .conftest import ROOT
+from ._models import spec_from_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -38,11 +39,6 @@ pytestmark = pytest.mark.gpu
 TOL_ENERGY = 2e-5
 TOL_WF = 2e-5
 TOL_DRIFT = 2e-5          # of the largest |drift| in the configuration
-
-
-def spec_from_golden(golden_params, tag):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    return Spec(**golden_params[tag]['spec'])
 
 
 def min_separation(pos, L):

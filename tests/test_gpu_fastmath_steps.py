@@ -35,7 +35,8 @@ import pytest
 
 from .test_gpu_fastmath import (TOL_DRIFT, TOL_ENERGY, TOL_WF, _report,
                                 min_separation)
-from .test_gpu_parity import close, spec_from_golden, worst
+from ._models import spec_from_golden
+from .test_gpu_parity import close, worst
 
 pytestmark = pytest.mark.gpu
 

@@ -8,137 +8,77 @@ they follow the same trajectory (test_gpu_sampling.py::
 test_dmc_split_step_equals_block).  A runs one time step at a time and hands
 out its State after each; B runs one estimator block.
 
-Rounding bound of the comparison, e = 2^-53, positions in [0, L] (asserted).
-
-Per term exp(i k_m z), kernel against restatement, as a complex magnitude:
-  * argument.  The kernel forms u = fl(fl(4 / L) z), relative error 2 e, the
-    angle of mode 1 being (pi / 2) u <= 2 pi: 4 pi e; mode m = 8 a + b is the
-    product of table entries with angles b and 8 a times that (8 u is exact),
-    so its angle is off by m 4 pi e.  The restatement forms
-    fl(fl(fl(2 m fl(pi)) / L) z), relative error 4 e of an angle <= 2 pi m:
-    8 pi m e.  Together 12 pi m e.
-  * sincos_halfpi: 2 ulp of a value <= 1, 4 e per
-    component, 4 sqrt(2) e for the pair; the b-th power of the pair carries b
-    times that, b <= 7: 28 sqrt(2) e per table.
-  * growth of the recurrence.  Every rotation of a table (two products and a
-    sum per component, terms <= 1) adds at most 8 e per component, 8 sqrt(2) e
-    for the pair, seven times: 56 sqrt(2) e per table.
-  * the product of the two table entries inherits the sum of both tables'
-    errors: 2 (28 + 56) sqrt(2) e < 240 e.
-  * NumPy's cos and sin: 1 ulp each, 2 sqrt(2) e < 3 e for the pair.
-  delta_m = (12 pi m + 243) e.
-
-rho_m is a sum of N such terms, each <= 1: N delta_m, plus the roundings of the
-sums.  The j-th addition of any order rounds a partial sum <= j: N^2 e / 2 per
-sum; the kernel's real and imaginary parts are differences of two accumulator
-tiles (N^2 e + N e), the restatement's are one sum each (N^2 e / 2): below
-2 N^2 e per component, 3 N^2 e for the pair.
-  D_m = N delta_m + 3 N^2 e.
-
-Row entries of one walker, |rho| <= N: columns T and T+1 (the origin) are off
-by at most D_m; column 0, |rho|^2, and column l, Re rho conj(rho_0), by
-2 N D_m + D_m^2 plus three roundings of values <= N^2 on each side:
-  Q_m = 2 N D_m (1 + 1e-6) + 6 N^2 e.
-The transport copies.  Sums over nw walkers of entries <= N^2 (N for the
-origin), any order, both sides: nw^2 N^2 e (nw^2 N e).
-  tol[t][m][c] = nw_t Q_m + nw_t^2 N^2 e   (c < T)
-  tol[t][m][c] = nw_t D_m + nw_t^2 N e     (c = T, T+1)
-At the largest value an entry can take, |x| = nw N^2 (nw N), the suite's usual
-2e-11 max(1, |x|) is above these for every shape below (asserted): the worst,
-m = 63 at N = 16, has Q_m / N^2 = 5.9e-13.  Nothing is fitted to what the
-kernel gives.
+The rounding bound of the comparison is `tolerance` of the restatement,
+derived in its docstring.  At the largest value an entry can take, |x| =
+nw N^2 (nw N), the suite's usual 2e-11 max(1, |x|) is above it for every shape
+below (asserted): the worst, m = 63 at N = 16, has Q_m / N^2 = 5.9e-13.
 """
 import functools
 from itertools import islice
-from math import pi
+from typing import NamedTuple
 
 import numpy as np
 import pytest
 
+from . import _dmc_walks as walks
 from . import _isf_restatement as isf
+from ._dmc_walks import EST, G2, TIME_STEP, WALKS
+from ._models import box
 
 pytestmark = pytest.mark.gpu
 
-TIME_STEP = 1e-3
-EPS = 2.0 ** -53
+
+class Shape(NamedTuple):
+    walk: str                   # of _dmc_walks.WALKS
+    steps: int
 
 
-def box(n, cut=0.25, depth=5 * pi ** 2, gint=2):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    return Spec(lattice_depth=depth, lattice_ratio=1,
-                interaction_strength=gint, boson_number=n, supercell_size=n,
-                tbf_contact_cutoff=cut * n)
+class Case(NamedTuple):
+    shape: str
+    K: int
+    T: int
+    q: int
 
 
-# tag: (N, contact cutoff / L, start walkers, max walkers, steps, seed): the
-# shapes of test_gpu_superfluid_est.py.  An odd N below a wavefront; N = 16;
-# N = 64 with more walkers than one pass of a block's wavefronts; N = 100, two
-# chunks of 32 particles and a ragged third plus a tail; a population that
-# starts at its cap; more live walkers than the launch has wavefronts (N = 37:
-# two chunks, the second ragged), so that every wavefront goes round its slot
-# loop again and rewrites its tables, its rho rows and its running sums.
-WAVEFRONTS = 4096               # of an estimator launch: 1024 blocks of 4
+# An odd N below a wavefront; N = 16; N = 64 with more walkers than one pass
+# of a block's wavefronts; N = 100, two chunks of 32 particles and a ragged
+# third plus a tail; a population that starts at its cap; more live walkers
+# than the launch has wavefronts (N = 37: two chunks, the second ragged), so
+# that every wavefront goes round its slot loop again and rewrites its tables,
+# its rho rows and its running sums.
 SHAPES = {
-    'odd':      (5, 0.25, 40, 64, 8, 1100),
-    'mid':      (16, 0.25, 48, 64, 6, 13),
-    'wave':     (64, 0.25, 300, 512, 10, 14),
-    'two_pass': (100, 0.1, 64, 96, 6, 15),
-    'cap':      (16, 0.25, 64, 64, 8, 1600),
-    'second_trip': (37, 0.25, 4500, 5120, 4, 1700),
+    'odd':         Shape('odd', 8),
+    'mid':         Shape('many', 6),
+    'wave':        Shape('wave', 10),
+    'two_pass':    Shape('two_pass', 6),
+    'cap':         Shape('cap', 8),
+    'second_trip': Shape('second_trip', 4),
 }
 KTQ = (8, 4, 2)
-# case: (shape, K, T, q).  Beyond the five shapes: the row limit K (T + 2) =
-# 1024 (sixteen indices per lane, all 64 modes); one mode, one lag (a row of
-# three doubles); a block that ends before lags 2 and 3 are reached.
-CASES = {tag: (tag,) + KTQ for tag in SHAPES}
+# Beyond the six shapes: the row limit K (T + 2) = 1024 (sixteen indices per
+# lane, all 64 modes); one mode, one lag (a row of three doubles); a block
+# that ends before lags 2 and 3 are reached.
+CASES = {tag: Case(tag, *KTQ) for tag in SHAPES}
 CASES.update({
-    'limit': ('mid', 64, 14, 1),
-    'one':   ('mid', 1, 1, 1),
-    'short': ('mid', 8, 4, 3),
+    'limit': Case('mid', 64, 14, 1),
+    'one':   Case('mid', 1, 1, 1),
+    'short': Case('mid', 8, 4, 3),
 })
-EST = dict(num_modes=8, ssf_pure=True, ssf_pfw=3, num_bins=12, dens_pure=False)
-G2 = dict(num_bins=20, pure=True, pfw=3)
 
 
-def start_positions(shape):
-    n, _, nw0, _, _, seed = SHAPES[shape]
-    return n * np.random.RandomState(seed).random_sample((nw0, n))
+def walk_of(shape):
+    return WALKS[SHAPES[shape].walk]
 
 
-def _ensemble(eng, shape, **kw):
-    from phd_qmclib_amd.engine import DmcEnsemble
-    _, _, nw0, maxw, _, seed = SHAPES[shape]
-    d = DmcEnsemble(eng, TIME_STEP, maxw, nw0, 0.5, rng_seed=seed, **kw)
-    d.set_state(start_positions(shape))
-    return d
-
-
-@functools.lru_cache(maxsize=None)
 def reference(shape):
-    """Ensemble A: the per-step states of the block, computed once per shape
-    -> dict."""
-    from phd_qmclib_amd.engine import ModelEngine
-    n, cut, _, _, nts, _ = SHAPES[shape]
-    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
-    a = _ensemble(eng, shape)
-    steps, energy = [], []
-    for _ in range(nts):
-        ser = a.run_block(1)
-        s = a.get_state()
-        confs = s.confs[:, 0, :].copy()
-        confs.setflags(write=False)
-        steps.append((confs, s.cloning_ref.copy(), int(s.num_walkers)))
-        energy.append(ser.energy[0])
-    a.close()
-    eng.close()
-    return dict(steps=steps, energy=np.array(energy),
-                num_walkers=np.array([s[2] for s in steps]))
+    """Ensemble A's states of the block (recorded once per walk) -> dict."""
+    return walks.record(SHAPES[shape].walk, SHAPES[shape].steps)
 
 
 @functools.lru_cache(maxsize=None)
 def restated(shape, K, T, q):
-    n = SHAPES[shape][0]
-    rows = isf.isf_rows(reference(shape)['steps'], float(n), K, T, q)
+    rows = isf.isf_rows(reference(shape)['steps'], float(walk_of(shape).n),
+                        K, T, q)
     rows.setflags(write=False)
     return rows
 
@@ -147,20 +87,15 @@ def run_block_b(shape, ktq=KTQ, eval_estimators=True, others=None, est=EST):
     """Ensemble B: one estimator block -> (series, ssf, dens, g2 rows, cm
     rows, isf rows); ktq None leaves the F(k, tau) slot off; `others` sets the
     other four estimators as well, 'before' or 'after' it."""
-    from phd_qmclib_amd.engine import ModelEngine
-    n, cut, _, _, nts, _ = SHAPES[shape]
-    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
-    b = _ensemble(eng, shape)
+    nts = SHAPES[shape].steps
+    eng = walks.engine(walk_of(shape))
+    b = walks.ensemble(eng, walk_of(shape))
     if others == 'before':
-        b.set_estimators(**est)
-        b.set_pair_dist_estimator(**G2)
-        b.set_cm_diffusion_estimator()
+        walks.set_others(b, est=est, cm=True)
     if ktq is not None:
         b.set_isf_estimator(*ktq)
     if others == 'after':
-        b.set_cm_diffusion_estimator()
-        b.set_pair_dist_estimator(**G2)
-        b.set_estimators(**est)
+        walks.set_others(b, est=est, cm=True, reverse=True)
     ser, ssf, dens = b.run_block_est(nts, eval_estimators)
     g2 = b.read_pair_dist(nts) if others else None
     cmd = b.read_cm_diffusion(nts) if others else None
@@ -170,33 +105,13 @@ def run_block_b(shape, ktq=KTQ, eval_estimators=True, others=None, est=EST):
     return ser, ssf, dens, g2, cmd, rows
 
 
-def tolerance(n, K, T, num_walkers):
-    """tol[nts, K, T + 2] of the module docstring."""
-    m = np.arange(K, dtype=np.float64)
-    delta = (12.0 * pi * m + 243.0) * EPS
-    d = n * delta + 3.0 * n * n * EPS
-    qd = 2.0 * n * d * (1.0 + 1e-6) + 6.0 * n * n * EPS
-    nw = np.asarray(num_walkers, dtype=np.float64)[:, None]
-    tol = np.empty((len(nw), K, T + 2))
-    tol[:, :, :T] = (nw * qd + nw * nw * n * n * EPS)[:, :, None]
-    tol[:, :, T:] = (nw * d + nw * nw * n * EPS)[:, :, None]
-    return tol
-
-
 @pytest.mark.parametrize('case', list(CASES))
 def test_rows_equal_the_restatement(case):
-    shape, K, T, q = CASES[case]
-    n, _, nw0, maxw, nts, _ = SHAPES[shape]
+    c = CASES[case]
+    shape, K, T, q = c.shape, c.K, c.T, c.q
+    n, nts = walk_of(shape).n, SHAPES[shape].steps
     ref = reference(shape)
-    # the transport is exercised: a step whose cloning table is not the
-    # identity, a population that changes
-    assert any(not np.array_equal(r[:nw], np.arange(nw))
-               for _, r, nw in ref['steps'])
-    assert len(set(ref['num_walkers']) | {nw0}) > 1
-    if shape == 'cap':
-        assert nw0 == maxw
-    if shape == 'second_trip':
-        assert maxw >= 5120 and (ref['num_walkers'] > WAVEFRONTS).all()
+    walks.assert_transport_exercised(ref, walk_of(shape), shape)
     for confs, _, nw in ref['steps']:
         assert confs[:nw].min() >= 0.0 and confs[:nw].max() <= n
     ser, _, _, _, _, rows = run_block_b(shape, (K, T, q))
@@ -204,7 +119,7 @@ def test_rows_equal_the_restatement(case):
     assert np.array_equal(ser.energy, ref['energy'])
     want = restated(shape, K, T, q)
     assert rows.shape == (nts, K, T + 2)
-    tol = tolerance(n, K, T, ref['num_walkers'])
+    tol = isf.tolerance(n, K, T, ref['num_walkers'])
     nw = ref['num_walkers'].astype(np.float64)[:, None, None]
     # the derivation gets below the suite's usual bound at full scale
     assert (tol[:, :, :T] <= 2e-11 * nw * n * n).all()
@@ -237,13 +152,13 @@ def test_lag_zero_columns_against_the_ssf_slot(shape):
     S(k) kernel: the bound of the module docstring holds between the two, the
     restatement's share of it to spare; whether they are equal to the bit is
     printed."""
-    n, _, _, _, nts, _ = SHAPES[shape]
+    n, nts = walk_of(shape).n, SHAPES[shape].steps
     K, T, q = KTQ
     est = dict(num_modes=K, ssf_pure=True, ssf_pfw=1, num_bins=0)
     run = run_block_b(shape, KTQ, others='before', est=est)
     ssf, rows = run[1], run[5]
     assert ssf.shape == (nts, K, 3)
-    tol = tolerance(n, K, T, reference(shape)['num_walkers'])
+    tol = isf.tolerance(n, K, T, reference(shape)['num_walkers'])
     got = rows[:, :, [0, T, T + 1]]
     err = np.abs(got - ssf)
     print(shape, 'equal to the bit:', np.array_equal(got, ssf),
@@ -253,7 +168,7 @@ def test_lag_zero_columns_against_the_ssf_slot(shape):
 
 def test_deterministic_and_burn_in():
     shape = 'wave'
-    nts = SHAPES[shape][4]
+    nts = SHAPES[shape].steps
     r1 = run_block_b(shape)
     r2 = run_block_b(shape)
     assert r1[5].tobytes() == r2[5].tobytes()
@@ -261,8 +176,7 @@ def test_deterministic_and_burn_in():
     # a burn-in block propagates the same walkers and leaves the rows zero
     r0 = run_block_b(shape, eval_estimators=False)
     assert r0[5].shape == (nts,) + (KTQ[0], KTQ[1] + 2) and not r0[5].any()
-    for x, y in zip(r0[0], r1[0]):
-        assert x.tobytes() == y.tobytes()
+    walks.assert_same_series(r0[0], r1[0])
 
 
 def test_the_walk_and_the_other_estimators_do_not_notice():
@@ -283,8 +197,7 @@ def test_the_walk_and_the_other_estimators_do_not_notice():
     for run in (alone, off, before, after, without):
         assert run[0].energy.tobytes() == ref['energy'].tobytes()
         assert np.array_equal(run[0].num_walkers, ref['num_walkers'])
-        for x, y in zip(run[0], off[0]):
-            assert x.tobytes() == y.tobytes()
+        walks.assert_same_series(run[0], off[0])
 
 
 def test_resetting_a_live_ensemble_equals_a_fresh_one():
@@ -293,13 +206,14 @@ def test_resetting_a_live_ensemble_equals_a_fresh_one():
     set once, to R's last configuration.  Same seed, same state, one estimator
     block each: every buffer of R was dropped and sized anew, so its rows are
     F's byte for byte."""
-    from phd_qmclib_amd.engine import DmcEnsemble, ModelEngine
+    from phd_qmclib_amd.engine import DmcEnsemble
     shape = 'mid'
-    n, cut, nw0, maxw, nts, seed = SHAPES[shape]
-    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
+    walk, nts = walk_of(shape), SHAPES[shape].steps
+    eng = walks.engine(walk)
     runs = []
     for again in (True, False):                      # R, then F
-        d = DmcEnsemble(eng, TIME_STEP, maxw, nw0, 0.5, rng_seed=seed)
+        d = DmcEnsemble(eng, TIME_STEP, walk.maxw, walk.nw0, 0.5,
+                        rng_seed=walk.seed)
         if again:
             d.set_estimators(num_modes=5, num_bins=0)
             d.set_isf_estimator(64, 14, 1)
@@ -311,15 +225,14 @@ def test_resetting_a_live_ensemble_equals_a_fresh_one():
         d.set_isf_estimator(*KTQ)
         d.set_cm_diffusion_estimator()
         d.set_pair_dist_estimator(**G2)
-        d.set_state(start_positions(shape))
+        d.set_state(walks.start_positions(walk))
         ser, ssf, dens = d.run_block_est(nts)
         runs.append((ser, ssf, dens, d.read_pair_dist(nts),
                      d.read_cm_diffusion(nts), d.read_isf(nts)))
         d.close()
     eng.close()
     r, f = runs
-    for x, y in zip(r[0], f[0]):
-        assert x.tobytes() == y.tobytes()
+    walks.assert_same_series(r[0], f[0])
     for k in (1, 2, 3, 4, 5):
         assert r[k].tobytes() == f[k].tobytes() and r[k].any()
     assert r[5].shape == (nts, KTQ[0], KTQ[1] + 2)
@@ -327,12 +240,11 @@ def test_resetting_a_live_ensemble_equals_a_fresh_one():
 
 
 def test_switching_off_and_errors():
-    from phd_qmclib_amd.engine import ModelEngine
     from phd_qmclib_amd._lib import QmcError
     shape = 'odd'
-    n, cut, _, _, nts, _ = SHAPES[shape]
-    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
-    d = _ensemble(eng, shape)
+    nts = SHAPES[shape].steps
+    eng = walks.engine(walk_of(shape))
+    d = walks.ensemble(eng, walk_of(shape))
     with pytest.raises(QmcError):
         d.read_isf(1)                        # the estimator is off
     for bad, what in (((65, 1, 1), 'num_modes'), ((-1, 1, 1), 'num_modes'),
@@ -369,19 +281,9 @@ def test_switching_off_and_errors():
 
 
 def test_distributed_dmc_refuses_the_estimator():
-    from phd_qmclib_amd.dist import DistributedDmc
-    import torch
-    from phd_qmclib_amd.engine import ModelEngine
-    eng = ModelEngine(box(16).cfc_spec,
-                      stream=torch.cuda.current_stream().cuda_stream)
-    d = _ensemble(eng, 'mid', external_reduce=True)
-    d.set_isf_estimator(*KTQ)
-    with pytest.raises(NotImplementedError, match=r'F\(k, tau\)'):
-        DistributedDmc(d, 16, 'cuda', solo=True)
-    d.set_isf_estimator(0)
-    DistributedDmc(d, 16, 'cuda', solo=True)
-    d.close()
-    eng.close()
+    walks.assert_refused_by_distributed(
+        walk_of('mid'), lambda d: d.set_isf_estimator(*KTQ),
+        lambda d: d.set_isf_estimator(0), r'F\(k, tau\)')
 
 
 # ---- top level ------------------------------------------------------------
@@ -389,7 +291,7 @@ def test_sampling_blocks_fill_iter_isf():
     from phd_qmclib_amd import mrbp_qmc
     spec = box(16)
     confs = np.zeros((48, 2, 16))
-    confs[:, 0, :] = start_positions('mid')
+    confs[:, 0, :] = walks.start_positions(walk_of('mid'))
     kw = dict(max_num_walkers=64, target_num_walkers=48, rng_seed=13)
     plain = mrbp_qmc.dmc.Sampling(spec, TIME_STEP, **kw)
     with_isf = mrbp_qmc.dmc.Sampling(

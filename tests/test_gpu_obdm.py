@@ -32,6 +32,7 @@ import pytest
 
 from ._obdm_restatement import ith_one_body_density
 from .conftest import GOLDEN, ROOT
+from ._models import _dev, spec_from_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -49,11 +50,6 @@ def close(a, b, rtol=RTOL):
 def worst(a, b):
     a, b = np.asarray(a), np.asarray(b)
     return float(np.max(np.abs(a - b) / np.maximum(1.0, np.abs(b))))
-
-
-def spec_from_golden(golden_params, tag):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    return Spec(**golden_params[tag]['spec'])
 
 
 @pytest.fixture(scope='module')
@@ -152,12 +148,6 @@ def test_obdm_order_independent(engines, golden_kernels, golden_obdm, tag):
 
 
 # ---- 4. one path, many doors ---------------------------------------------
-def _dev(eng, a):
-    from phd_qmclib_amd.engine import DeviceBuffer
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    return DeviceBuffer(a.shape, eng.device).upload(a)
-
-
 @pytest.mark.parametrize('tag', ['box16', 'box37', 'box64', 'box100',
                                  'box128'])
 def test_obdm_entry_points_agree(engines, golden_params, golden_kernels,

@@ -23,30 +23,28 @@ import functools
 import math
 from itertools import islice
 from math import pi
+from typing import NamedTuple
 
 import numpy as np
 import pytest
 
+from . import _dmc_walks as walks
 from . import _obdm_restatement as restated
+from ._dmc_walks import TIME_STEP, WALKS
+from ._models import box, model_dict
 
 pytestmark = pytest.mark.gpu
 
-TIME_STEP = 1e-3
 RTOL = 2e-11                    # of tests/test_gpu_obdm.py
-WAVEFRONTS = 4096               # of an estimator launch: 1024 blocks of 4
 
 
-def box(n, cut=0.25):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    return Spec(lattice_depth=5 * pi ** 2, lattice_ratio=1,
-                interaction_strength=2, boson_number=n, supercell_size=n,
-                tbf_contact_cutoff=cut * n)
+class Case(NamedTuple):
+    walk: str                   # of _dmc_walks.WALKS
+    steps: int
+    shifts: tuple               # as multiples of L
 
 
-# tag: (spec source, contact cutoff / L, start walkers, max walkers, steps,
-#       seed, shifts as multiples of L or the string naming a set).
-# The walks of `odd` .. `second_trip` are those of tests/test_gpu_pairdist_est.py
-# (N, cutoff, walkers, cap, seed): they clone, change population and, for
+# The walks `odd` .. `second_trip` clone, change population and, for
 # `second_trip`, stay above 4096 live walkers.
 #   odd_k1:   N = 5, G = 8: eight shift groups per wave, a single one and a
 #             single u-slot live
@@ -68,87 +66,42 @@ def _k256():
 
 
 CASES = {
-    'odd_k1':   (5, 0.25, 40, 64, 8, 1100, (0.3,)),
-    'odd_k19':  (5, 0.25, 40, 64, 8, 1100,
-                 tuple(np.linspace(0.0, 0.5, 19))),
-    'one_bin':  (16, 0.25, 48, 64, 6, 12, _k256()),
-    'many':     (16, 0.25, 48, 64, 6, 13, _k256()),
-    'wave':     (64, 0.25, 300, 512, 10, 14, (0.0, 0.01, 0.03, -0.37, 0.5)),
-    'two_pass': (100, 0.1, 64, 96, 6, 15, (0.0, 0.013)),
-    'cap':      (16, 0.25, 64, 64, 8, 1600, (0.0, 0.1, -0.45)),
-    'second_trip': (37, 0.25, 4500, 5120, 2, 1700, (0.0, 0.02)),
-    'n512':     (512, 0.25, 12, 16, 2, 18, (0.0, 0.002)),
-    'free16':   ('free16', None, 24, 32, 4, 19, (0.0, 0.07, -0.37)),
-    'ideal16':  ('ideal16', None, 24, 32, 4, 20, (0.0, 0.07, -0.37)),
-    'odd24':    ('odd24', None, 24, 32, 4, 21, (0.0, 0.07, 1.0)),
+    'odd_k1':      Case('odd', 8, (0.3,)),
+    'odd_k19':     Case('odd', 8, tuple(np.linspace(0.0, 0.5, 19))),
+    'one_bin':     Case('one_bin', 6, _k256()),
+    'many':        Case('many', 6, _k256()),
+    'wave':        Case('wave', 10, (0.0, 0.01, 0.03, -0.37, 0.5)),
+    'two_pass':    Case('two_pass', 6, (0.0, 0.013)),
+    'cap':         Case('cap', 8, (0.0, 0.1, -0.45)),
+    'second_trip': Case('second_trip', 2, (0.0, 0.02)),
+    'n512':        Case('n512', 2, (0.0, 0.002)),
+    'free16':      Case('free16', 4, (0.0, 0.07, -0.37)),
+    'ideal16':     Case('ideal16', 4, (0.0, 0.07, -0.37)),
+    'odd24':       Case('odd24', 4, (0.0, 0.07, 1.0)),
 }
 PAIRDIST_WALKS = ('odd_k1', 'odd_k19', 'one_bin', 'many', 'wave', 'two_pass',
                   'cap', 'second_trip')
 
 
-@functools.lru_cache(maxsize=None)
-def _golden_params():
-    import json
-    import os
-    here = os.path.dirname(os.path.abspath(__file__))
-    with open(os.path.join(here, 'golden', 'params.json')) as f:
-        return json.load(f)
+def walk_of(tag):
+    return WALKS[CASES[tag].walk]
 
 
-@functools.lru_cache(maxsize=None)
 def spec_of(tag):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    src, cut = CASES[tag][:2]
-    if isinstance(src, str):
-        return Spec(**_golden_params()[src]['spec'])
-    return box(src, cut)
+    return walks.spec(walk_of(tag))
 
 
 def shifts_of(tag):
     L = float(spec_of(tag).supercell_size)
-    return np.array(CASES[tag][6]) * L
-
-
-def start_positions(tag):
-    _, _, nw0, _, _, seed, _ = CASES[tag]
-    spec = spec_of(tag)
-    n, L = spec.boson_number, float(spec.supercell_size)
-    return L * np.random.RandomState(seed).random_sample((nw0, n))
-
-
-def _ensemble(eng, tag):
-    from phd_qmclib_amd.engine import DmcEnsemble
-    _, _, nw0, maxw, _, seed, _ = CASES[tag]
-    d = DmcEnsemble(eng, TIME_STEP, maxw, nw0, 0.5, rng_seed=seed)
-    d.set_state(start_positions(tag))
-    return d
-
-
-def _model_dict(cfc):
-    return {'params': cfc.model_params._asdict(),
-            'obf_params': cfc.obf_params._asdict(),
-            'tbf_params': cfc.tbf_params._asdict()}
+    return np.array(CASES[tag].shifts) * L
 
 
 @functools.lru_cache(maxsize=None)
-def walk(tag, steps=None):
-    """Ensemble A: the per-step states of `steps` single-step blocks (default:
-    the case's) -> dict."""
-    from phd_qmclib_amd.engine import ModelEngine
-    T = CASES[tag][4] if steps is None else steps
-    eng = ModelEngine(spec_of(tag).cfc_spec, device=0)
-    a = _ensemble(eng, tag)
-    out, energy = [], []
-    for _ in range(T):
-        ser = a.run_block(1)
-        s = a.get_state()
-        nw = int(s.num_walkers)
-        out.append((s.confs[:nw, 0, :].copy(), s.cloning_ref[:nw].copy(), nw))
-        energy.append(ser.energy[0])
-    a.close()
-    eng.close()
-    return dict(steps=out, energy=np.array(energy),
-                num_walkers=np.array([s[2] for s in out]))
+def walk(tag):
+    """Ensemble A's states of the case's block, each step cut to its live
+    walkers -> dict."""
+    rec = walks.record(CASES[tag].walk, CASES[tag].steps)
+    return dict(rec, steps=[(c[:nw], r[:nw], nw) for c, r, nw in rec['steps']])
 
 
 @functools.lru_cache(maxsize=None)
@@ -156,11 +109,10 @@ def reference(tag):
     """The two yardsticks on ensemble A's configurations, once per case:
     defn[t], batch[t] = g1[nw_t, K] of the restatement (evaluated once per
     distinct configuration: clones repeat) and of the batch kernel."""
-    from phd_qmclib_amd.engine import ModelEngine
     w = walk(tag)
     cfc = spec_of(tag).cfc_spec
-    p, sh = _model_dict(cfc), shifts_of(tag)
-    eng = ModelEngine(cfc, device=0)
+    p, sh = model_dict(cfc), shifts_of(tag)
+    eng = walks.engine(walk_of(tag))
     defn, batch = [], []
     for pos, _, nw in w['steps']:
         uniq, inv = np.unique(pos, axis=0, return_inverse=True)
@@ -181,28 +133,21 @@ def run_block_b(tag, shifts=None, stride=1, steps=None, eval_estimators=True,
     F(k, tau) are set as well, before (1) or after (2) g1.  `disturb`: the
     batch g1 entry point runs on the same engine, with another number of
     shifts, between the setter and the block and between the blocks."""
-    from phd_qmclib_amd.engine import ModelEngine
-    T = CASES[tag][4] if steps is None else steps
+    T = CASES[tag].steps if steps is None else steps
     sh = shifts_of(tag) if shifts is None else np.asarray(shifts)
-    eng = ModelEngine(spec_of(tag).cfc_spec, device=0)
-    b = _ensemble(eng, tag)
-
-    def set_others():
-        b.set_estimators(num_modes=8, ssf_pure=True, ssf_pfw=3, num_bins=12,
-                         dens_pure=False)
-        b.set_pair_dist_estimator(20, pure=True, pfw=3)
-        b.set_isf_estimator(4, 2, 2)
+    eng = walks.engine(walk_of(tag))
+    b = walks.ensemble(eng, walk_of(tag))
 
     def disturb_engine():
-        other = start_positions(tag)[:5] * 0.9
+        other = walks.start_positions(walk_of(tag))[:5] * 0.9
         eng.one_body_density(other, np.linspace(-1.0, 2.0, 7))
 
     if others == 1:
-        set_others()
+        walks.set_others(b, isf=(4, 2, 2))
     if with_g1:
         b.set_obdm_estimator(sh, stride)
     if others == 2:
-        set_others()
+        walks.set_others(b, isf=(4, 2, 2))
     out = []
     for _ in range(blocks):
         if disturb:
@@ -219,19 +164,13 @@ def run_block_b(tag, shifts=None, stride=1, steps=None, eval_estimators=True,
 
 @pytest.mark.parametrize('tag', list(CASES))
 def test_rows_against_the_definition_and_the_batch_kernel(tag):
-    _, _, nw0, maxw, T, _, _ = CASES[tag]
+    T = CASES[tag].steps
     ref = reference(tag)
     sh = shifts_of(tag)
     K = sh.size
     if tag in PAIRDIST_WALKS:
         # the walk clones and the population changes
-        assert any(not np.array_equal(r, np.arange(nw))
-                   for _, r, nw in ref['steps'])
-        assert len(set(ref['num_walkers']) | {nw0}) > 1
-    if tag == 'cap':
-        assert nw0 == maxw
-    if tag == 'second_trip':
-        assert maxw >= 5120 and (ref['num_walkers'] > WAVEFRONTS).all()
+        walks.assert_transport_exercised(ref, walk_of(tag), tag)
     (ser, _, _, _, _, rows), = run_block_b(tag)
     print(tag, 'walkers', ref['num_walkers'])
     # the estimator does not touch the walk
@@ -326,7 +265,7 @@ def test_stride_evaluates_every_third_step():
 
 def test_deterministic_and_burn_in():
     tag = 'wave'
-    T, K = CASES[tag][4], len(CASES[tag][6])
+    T, K = CASES[tag].steps, len(CASES[tag].shifts)
     (s1, _, _, _, _, r1), = run_block_b(tag)
     (s2, _, _, _, _, r2), = run_block_b(tag)
     assert r1.tobytes() == r2.tobytes()
@@ -370,21 +309,21 @@ def test_shift_table_survives_other_calls_on_the_engine():
 
 
 def test_resetting_a_live_ensemble_equals_a_fresh_one():
-    from phd_qmclib_amd.engine import DmcEnsemble, ModelEngine
+    from phd_qmclib_amd.engine import DmcEnsemble
     from phd_qmclib_amd._lib import QmcError
     tag = 'many'
-    _, _, nw0, maxw, T, seed, _ = CASES[tag]
+    w, T = walk_of(tag), CASES[tag].steps
     wide = shifts_of(tag)
     narrow = np.array([0.0, 1.7, -3.3])
     assert wide.size == 256
-    eng = ModelEngine(spec_of(tag).cfc_spec, device=0)
+    eng = walks.engine(w)
     runs = []
     for todo in ([(wide, 2), (narrow, 1)], [(narrow, 1)]):   # R, then F
-        d = DmcEnsemble(eng, TIME_STEP, maxw, nw0, 0.5, rng_seed=seed)
+        d = DmcEnsemble(eng, TIME_STEP, w.maxw, w.nw0, 0.5, rng_seed=w.seed)
         for sh, q in todo:
             d.set_obdm_estimator(sh, q)
         assert np.array_equal(d.obdm_shifts, narrow)
-        d.set_state(start_positions(tag))
+        d.set_state(walks.start_positions(w))
         ser, _, _ = d.run_block_est(T)
         runs.append((ser, d.read_obdm(T)))
         if len(todo) == 2:
@@ -402,18 +341,16 @@ def test_resetting_a_live_ensemble_equals_a_fresh_one():
         d.close()
     eng.close()
     (ser_r, g1_r), (ser_f, g1_f) = runs
-    for x, y in zip(ser_r, ser_f):
-        assert x.tobytes() == y.tobytes()
+    walks.assert_same_series(ser_r, ser_f)
     assert g1_r.shape == (T, 3) and g1_r.all()
     assert g1_r.tobytes() == g1_f.tobytes()
     assert np.array_equal(g1_r[:, 0], ser_r.num_walkers.astype(np.float64))
 
 
 def test_bad_arguments_name_the_entry_point():
-    from phd_qmclib_amd.engine import ModelEngine
     tag = 'odd_k1'
-    eng = ModelEngine(spec_of(tag).cfc_spec, device=0)
-    d = _ensemble(eng, tag)
+    eng = walks.engine(walk_of(tag))
+    d = walks.ensemble(eng, walk_of(tag))
     lib, dp = d._lib, C.POINTER(C.c_double)
     good = np.array([0.0, 0.5])
 
@@ -455,21 +392,9 @@ def test_bad_arguments_name_the_entry_point():
 
 
 def test_distributed_dmc_refuses_the_estimator():
-    from phd_qmclib_amd.dist import DistributedDmc
-    import torch
-    from phd_qmclib_amd.engine import DmcEnsemble, ModelEngine
-    eng = ModelEngine(box(16).cfc_spec,
-                      stream=torch.cuda.current_stream().cuda_stream)
-    d = DmcEnsemble(eng, TIME_STEP, 64, 48, 0.5, rng_seed=2,
-                    external_reduce=True)
-    d.set_state(start_positions('many'))
-    d.set_obdm_estimator([0.0, 1.0])
-    with pytest.raises(NotImplementedError, match='one-body density'):
-        DistributedDmc(d, 16, 'cuda', solo=True)
-    d.set_obdm_estimator(None)
-    DistributedDmc(d, 16, 'cuda', solo=True)
-    d.close()
-    eng.close()
+    walks.assert_refused_by_distributed(
+        WALKS['many'], lambda d: d.set_obdm_estimator([0.0, 1.0]),
+        lambda d: d.set_obdm_estimator(None), 'one-body density', rng_seed=2)
 
 
 # ---- top level ------------------------------------------------------------
@@ -477,7 +402,7 @@ def test_sampling_blocks_fill_iter_obdm():
     from phd_qmclib_amd import mrbp_qmc
     spec = box(16)
     confs = np.zeros((48, 2, 16))
-    confs[:, 0, :] = start_positions('many')
+    confs[:, 0, :] = walks.start_positions(WALKS['many'])
     kw = dict(max_num_walkers=64, target_num_walkers=48, rng_seed=13)
     sh = (0.0, 0.5, 2.0, 8.0)
     plain = mrbp_qmc.dmc.Sampling(spec, TIME_STEP, **kw)

@@ -30,6 +30,7 @@ import pytest
 
 from . import _pairdist_restatement as rs
 from .conftest import ROOT
+from ._models import _dev, spec_from_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -43,11 +44,6 @@ ALL_TAGS = ['box8', 'box16', 'box64', 'box128', 'box512', 'free16', 'deep100',
 def close(a, b, rtol=RTOL):
     a, b = np.asarray(a), np.asarray(b)
     return np.all(np.abs(a - b) <= rtol * np.maximum(1.0, np.abs(b)))
-
-
-def spec_from_golden(golden_params, tag):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    return Spec(**golden_params[tag]['spec'])
 
 
 @pytest.fixture(scope='module')
@@ -83,12 +79,6 @@ def check_counts(dev, ref, amb, n, widened=False):
             slack = rs.edge_slack(amb[c], ref.shape[1])
             assert np.all(np.abs(dev[c] - ref[c]) <= slack), c
     return namb
-
-
-def _dev(eng, a):
-    from phd_qmclib_amd.engine import DeviceBuffer
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    return DeviceBuffer(a.shape, eng.device).upload(a)
 
 
 def counts_dev(eng, dpos, W, B):

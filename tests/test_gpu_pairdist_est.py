@@ -13,82 +13,56 @@ below were picked so that no pair of any case sits within 1e-9 of one.
 """
 import functools
 from itertools import islice
-from math import pi
+from typing import NamedTuple
 
 import numpy as np
 import pytest
 
+from . import _dmc_walks as walks
 from . import _pairdist_fw_restatement as fw
+from ._dmc_walks import EST, TIME_STEP, WALKS
+from ._models import box
 
 pytestmark = pytest.mark.gpu
 
-TIME_STEP = 1e-3
+
+class Case(NamedTuple):
+    walk: str                   # of _dmc_walks.WALKS
+    bins: int
+    steps: int
+    pfw: int
 
 
-def box(n, cut=0.25):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    return Spec(lattice_depth=5 * pi ** 2, lattice_ratio=1,
-                interaction_strength=2, boson_number=n, supercell_size=n,
-                tbf_contact_cutoff=cut * n)
-
-
-# tag: (N, contact cutoff / L, bins, start walkers, max walkers, steps, pfw,
-#       seed).  The smallest shapes that still reach every path of the kernel:
-# an odd N with fewer bins than lanes; a single bin; more than 64 bins (the
-# lane = bin chunks); N = 64, one particle per lane, with pfw inside the block
-# (both divisors); N = 100, two passes over the own particles, at the largest
-# bin count; a population that starts at the cap; more live walkers than the
+# The smallest shapes that still reach every path of the kernel: an odd N with
+# fewer bins than lanes; a single bin; more than 64 bins (the lane = bin
+# chunks); N = 64, one particle per lane, with pfw inside the block (both
+# divisors); N = 100, two passes over the own particles, at the largest bin
+# count; a population that starts at the cap; more live walkers than the
 # launch has wavefronts (N = 37, bins in two lane chunks, pfw inside the block),
 # so that every wavefront goes round its slot loop again and rewrites its
 # positions and its histogram.
-WAVEFRONTS = 4096               # of an estimator launch: 1024 blocks of 4
 CASES = {
-    'odd':      (5, 0.25, 7, 40, 64, 8, 3, 1100),
-    'one_bin':  (16, 0.25, 1, 48, 64, 6, 3, 12),
-    'many':     (16, 0.25, 200, 48, 64, 6, 3, 13),
-    'wave':     (64, 0.25, 64, 300, 512, 10, 4, 14),
-    'two_pass': (100, 0.1, 256, 64, 96, 6, 3, 15),
-    'cap':      (16, 0.25, 16, 64, 64, 8, 3, 1600),
-    'second_trip': (37, 0.25, 70, 4500, 5120, 4, 2, 1700),
+    'odd':         Case('odd', 7, 8, 3),
+    'one_bin':     Case('one_bin', 1, 6, 3),
+    'many':        Case('many', 200, 6, 3),
+    'wave':        Case('wave', 64, 10, 4),
+    'two_pass':    Case('two_pass', 256, 6, 3),
+    'cap':         Case('cap', 16, 8, 3),
+    'second_trip': Case('second_trip', 70, 4, 2),
 }
-
-
-def start_positions(tag):
-    n, _, _, nw0, _, _, _, seed = CASES[tag]
-    return n * np.random.RandomState(seed).random_sample((nw0, n))
-
-
-def _ensemble(eng, tag):
-    from phd_qmclib_amd.engine import DmcEnsemble
-    _, _, _, nw0, maxw, _, _, seed = CASES[tag]
-    d = DmcEnsemble(eng, TIME_STEP, maxw, nw0, 0.5, rng_seed=seed)
-    d.set_state(start_positions(tag))
-    return d
 
 
 @functools.lru_cache(maxsize=None)
 def reference(tag):
-    """Ensemble A: the per-step states of the block and the restatement's rows
-    on them, computed once per case -> dict."""
-    from phd_qmclib_amd.engine import ModelEngine
-    n, cut, B, _, _, T, pfw, _ = CASES[tag]
-    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
-    a = _ensemble(eng, tag)
-    steps, energy = [], []
-    for _ in range(T):
-        ser = a.run_block(1)
-        s = a.get_state()
-        steps.append((s.confs[:, 0, :].copy(), s.cloning_ref.copy(),
-                      int(s.num_walkers)))
-        energy.append(ser.energy[0])
-    a.close()
-    eng.close()
-    mixed, pure, amb = fw.forward_walk(steps, float(n), B, pfw)
+    """Ensemble A's states of the block and the restatement's rows on them,
+    computed once per case -> dict."""
+    case = CASES[tag]
+    rec = walks.record(case.walk, case.steps)
+    mixed, pure, amb = fw.forward_walk(
+        rec['steps'], float(WALKS[case.walk].n), case.bins, case.pfw)
     for arr in (mixed, pure):
         arr.setflags(write=False)
-    return dict(steps=steps, mixed=mixed, pure=pure, ambiguous=amb,
-                energy=np.array(energy),
-                num_walkers=np.array([s[2] for s in steps]))
+    return dict(rec, mixed=mixed, pure=pure, ambiguous=amb)
 
 
 def run_block_b(tag, pure, eval_estimators=True, others=False, order=0,
@@ -96,13 +70,12 @@ def run_block_b(tag, pure, eval_estimators=True, others=False, order=0,
     """Ensemble B: one estimator block -> (series, ssf, dens, g2 rows);
     `others` sets S(k) and the density as well, before (order 0) or after
     (order 1) the pair distribution."""
-    from phd_qmclib_amd.engine import ModelEngine
-    n, cut, B, _, _, T, pfw, _ = CASES[tag]
-    B = B if with_g2 else 0
-    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
-    b = _ensemble(eng, tag)
-    est = dict(num_modes=8, ssf_pure=True, ssf_pfw=pfw, num_bins=12,
-               dens_pure=False)
+    case = CASES[tag]
+    T, pfw = case.steps, case.pfw
+    B = case.bins if with_g2 else 0
+    eng = walks.engine(WALKS[case.walk])
+    b = walks.ensemble(eng, WALKS[case.walk])
+    est = dict(EST, ssf_pfw=pfw)
     if others and order == 0:
         b.set_estimators(**est)
     if B:
@@ -119,20 +92,13 @@ def run_block_b(tag, pure, eval_estimators=True, others=False, order=0,
 @pytest.mark.parametrize('pure', [False, True], ids=['mixed', 'pure'])
 @pytest.mark.parametrize('tag', list(CASES))
 def test_rows_equal_the_forward_walking(tag, pure):
-    n, _, B, nw0, maxw, T, pfw, _ = CASES[tag]
+    case = CASES[tag]
+    n, B, T, pfw = WALKS[case.walk].n, case.bins, case.steps, case.pfw
     ref = reference(tag)
     assert ref['ambiguous'] == [], \
         'a pair sits on a bin edge: choose another seed ' + \
         repr(ref['ambiguous'][:4])
-    # the transport is exercised: a step whose cloning table is not the
-    # identity, and a population that changes
-    assert any(not np.array_equal(r[:nw], np.arange(nw))
-               for _, r, nw in ref['steps'])
-    assert len(set(ref['num_walkers']) | {nw0}) > 1
-    if tag == 'cap':
-        assert nw0 == maxw
-    if tag == 'second_trip':
-        assert maxw >= 5120 and (ref['num_walkers'] > WAVEFRONTS).all()
+    walks.assert_transport_exercised(ref, WALKS[case.walk], tag)
     if pure:
         assert 1 < pfw < T          # both divisors, min(t + 1, pfw)
     ser, _, _, rows = run_block_b(tag, pure)
@@ -142,14 +108,9 @@ def test_rows_equal_the_forward_walking(tag, pure):
     want = ref['pure'] if pure else ref['mixed']
     assert rows.shape == (T, B)
     assert np.array_equal(rows, want), np.argwhere(rows != want)[:8]
-    # every walker holds N (N - 1) / 2 pairs, at every step, mixed and pure.
-    # A pure entry is the rounded quotient of an integer by min(t + 1, pfw)
-    # (thirds, say), and a float sum of such quotients is not exact: the
-    # invariant is checked on the integer numerators, which each entry must
-    # give back bit for bit.
-    div = np.minimum(np.arange(T) + 1, pfw if pure else 1)[:, None]
-    counts = np.rint(rows * div)
-    assert np.array_equal(counts / div, rows)
+    # every walker holds N (N - 1) / 2 pairs, at every step, mixed and pure:
+    # checked on the integer numerators
+    counts, div = walks.numerators(rows, T, pfw, pure)
     assert np.array_equal(counts.sum(axis=1),
                           ref['num_walkers'] * div[:, 0] * (n * (n - 1) // 2))
 
@@ -157,7 +118,7 @@ def test_rows_equal_the_forward_walking(tag, pure):
 @pytest.mark.parametrize('pure', [False, True], ids=['mixed', 'pure'])
 def test_deterministic_and_burn_in(pure):
     tag = 'wave'
-    _, _, B, _, _, T, _, _ = CASES[tag]
+    B, T = CASES[tag].bins, CASES[tag].steps
     s1, _, _, r1 = run_block_b(tag, pure)
     s2, _, _, r2 = run_block_b(tag, pure)
     assert r1.tobytes() == r2.tobytes()
@@ -172,7 +133,6 @@ def test_deterministic_and_burn_in(pure):
 @pytest.mark.parametrize('pure', [False, True], ids=['mixed', 'pure'])
 def test_independent_of_the_other_estimators(pure):
     tag = 'many'
-    n, cut, B, _, _, T, _, _ = CASES[tag]
     alone = run_block_b(tag, pure)
     first = run_block_b(tag, pure, others=True, order=0)
     second = run_block_b(tag, pure, others=True, order=1)
@@ -199,30 +159,31 @@ def test_resetting_a_live_ensemble_equals_a_fresh_one(second_pure):
     off in the narrow configuration (`dens is None` in R and in F); where the
     second configuration is the wide one it has 12 bins, and the density rows
     are compared like the others: equal byte for byte, none of them zero."""
-    from phd_qmclib_amd.engine import DmcEnsemble, ModelEngine
+    from phd_qmclib_amd.engine import DmcEnsemble
     tag = 'many'
-    n, cut, B, nw0, maxw, T, pfw, seed = CASES[tag]
+    case, walk = CASES[tag], WALKS[CASES[tag].walk]
+    n, nw0, maxw, seed = walk.n, walk.nw0, walk.maxw, walk.seed
+    B, T, pfw = case.bins, case.steps, case.pfw
     B2 = B // 4          # its bin edges are edges of the B bins as well
     assert (n, nw0, maxw) == (16, 48, 64) and 0 < B2 < B
     wide = (dict(num_modes=8, ssf_pure=True, ssf_pfw=pfw, num_bins=12),
             dict(num_bins=B, pure=True, pfw=pfw))
     narrow = (dict(num_modes=5, num_bins=0), dict(num_bins=B2, pure=False))
     configs = [narrow, wide] if second_pure else [wide, narrow]
-    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
+    eng = walks.engine(walk)
     runs = []
     for todo in (configs, configs[1:]):              # R, then F
         d = DmcEnsemble(eng, TIME_STEP, maxw, nw0, 0.5, rng_seed=seed)
         for est, g2 in todo:
             d.set_estimators(**est)
             d.set_pair_dist_estimator(**g2)
-        d.set_state(start_positions(tag))
+        d.set_state(walks.start_positions(walk))
         ser, ssf, dens = d.run_block_est(T)
         runs.append((ser, ssf, dens, d.read_pair_dist(T)))
         d.close()
     eng.close()
     (ser_r, ssf_r, dens_r, g2_r), (ser_f, ssf_f, dens_f, g2_f) = runs
-    for x, y in zip(ser_r, ser_f):
-        assert x.tobytes() == y.tobytes()
+    walks.assert_same_series(ser_r, ser_f)
     assert ssf_r.tobytes() == ssf_f.tobytes()
     assert g2_r.tobytes() == g2_f.tobytes()
     assert ssf_r.shape == (T, 8 if second_pure else 5, 3)
@@ -245,12 +206,11 @@ def test_resetting_a_live_ensemble_equals_a_fresh_one(second_pure):
 
 
 def test_switching_off_and_errors():
-    from phd_qmclib_amd.engine import ModelEngine
     from phd_qmclib_amd._lib import QmcError
-    tag = 'odd'
-    n, cut, B, _, _, T, pfw, _ = CASES[tag]
-    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
-    d = _ensemble(eng, tag)
+    case = CASES['odd']
+    B, T, pfw = case.bins, case.steps, case.pfw
+    eng = walks.engine(WALKS[case.walk])
+    d = walks.ensemble(eng, WALKS[case.walk])
     with pytest.raises(QmcError):
         d.set_pair_dist_estimator(257)
     with pytest.raises(QmcError):
@@ -274,21 +234,10 @@ def test_switching_off_and_errors():
 
 
 def test_distributed_dmc_refuses_the_estimator():
-    from phd_qmclib_amd.dist import DistributedDmc
-    import torch
-    from phd_qmclib_amd.engine import DmcEnsemble, ModelEngine
-    eng = ModelEngine(box(16).cfc_spec,
-                      stream=torch.cuda.current_stream().cuda_stream)
-    d = DmcEnsemble(eng, TIME_STEP, 64, 48, 0.5, rng_seed=2,
-                    external_reduce=True)
-    d.set_state(start_positions('many'))
-    d.set_pair_dist_estimator(16)
-    with pytest.raises(NotImplementedError, match='pair distribution'):
-        DistributedDmc(d, 16, 'cuda', solo=True)
-    d.set_pair_dist_estimator(0)
-    DistributedDmc(d, 16, 'cuda', solo=True)
-    d.close()
-    eng.close()
+    walks.assert_refused_by_distributed(
+        WALKS['many'], lambda d: d.set_pair_dist_estimator(16),
+        lambda d: d.set_pair_dist_estimator(0), 'pair distribution',
+        rng_seed=2)
 
 
 # ---- top level ------------------------------------------------------------
@@ -296,7 +245,7 @@ def test_sampling_blocks_fill_iter_pair_dist():
     from phd_qmclib_amd import mrbp_qmc
     spec = box(16)
     confs = np.zeros((48, 2, 16))
-    confs[:, 0, :] = start_positions('many')
+    confs[:, 0, :] = walks.start_positions(WALKS['many'])
     kw = dict(max_num_walkers=64, target_num_walkers=48, rng_seed=13)
     plain = mrbp_qmc.dmc.Sampling(spec, TIME_STEP, **kw)
     with_pd = mrbp_qmc.dmc.Sampling(
@@ -313,10 +262,7 @@ def test_sampling_blocks_fill_iter_pair_dist():
         assert np.array_equal(p.iter_props.energy, q.iter_props.energy)
     assert not b1[0].iter_pair_dist.any()            # the burn-in block
     nw = b1[1].iter_props.num_walkers.astype(np.int64)
-    # (the integer numerators: a float sum of thirds is not exact)
-    div = np.minimum(np.arange(6) + 1, 3)[:, None]
-    counts = np.rint(b1[1].iter_pair_dist * div)
-    assert np.array_equal(counts / div, b1[1].iter_pair_dist)
+    counts, div = walks.numerators(b1[1].iter_pair_dist, 6, 3, True)
     assert np.array_equal(counts.sum(axis=1), nw * div[:, 0] * 120)
 
 

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from .conftest import oracle_model
+from ._models import spec_from_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -30,11 +31,6 @@ def close(a, b, rtol=RTOL):
 def worst(a, b):
     a, b = np.asarray(a), np.asarray(b)
     return float(np.max(np.abs(a - b) / np.maximum(1.0, np.abs(b))))
-
-
-def spec_from_golden(golden_params, tag):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    return Spec(**golden_params[tag]['spec'])
 
 
 @pytest.fixture(scope='module')

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from . import _partent_restatement as pe
+from ._models import _dev
 
 pytestmark = pytest.mark.gpu
 
@@ -80,12 +81,6 @@ def references(models):
             cache[n] = out
         return cache[n]
     return get
-
-
-def _dev(eng, a):
-    from phd_qmclib_amd.engine import DeviceBuffer
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    return DeviceBuffer(a.shape, eng.device).upload(a)
 
 
 def reduce_dev(eng, dpos, W):

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 from . import _renyi_restatement as rs
+from ._models import _dev
 
 pytestmark = pytest.mark.gpu
 
@@ -94,12 +95,6 @@ def check_parity(eng, ref, pos, lengths, origin, label):
           % (label, int(np.isfinite(lr_ref).sum()), worst))
     assert ok
     return n_a, lr
-
-
-def _dev(eng, a):
-    from phd_qmclib_amd.engine import DeviceBuffer
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    return DeviceBuffer(a.shape, eng.device).upload(a)
 
 
 def swap_of(log_ratio):

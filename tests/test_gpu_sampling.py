@@ -9,16 +9,9 @@ from math import pi
 import numpy as np
 import pytest
 
+from ._models import box
+
 pytestmark = pytest.mark.gpu
-
-
-def box(n=16, **kw):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    d = dict(lattice_depth=5 * pi ** 2, lattice_ratio=1,
-             interaction_strength=2, boson_number=n, supercell_size=n,
-             tbf_contact_cutoff=0.25 * n)
-    d.update(kw)
-    return Spec(**d)
 
 
 def test_core_funcs_surface():

@@ -3,21 +3,13 @@ CPU oracle is too slow to be the checker: determinism, independence of a
 chain's trajectory from the ensemble size (counter RNG keyed by chain), exact
 bookkeeping identities of the DMC step, and the symmetries of the model
 (particle permutation, translation by a lattice period)."""
-from math import pi
 
 import numpy as np
 import pytest
 
+from ._models import box
+
 pytestmark = pytest.mark.gpu
-
-
-def box(n, **kw):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    d = dict(lattice_depth=5 * pi ** 2, lattice_ratio=1,
-             interaction_strength=2, boson_number=n, supercell_size=n,
-             tbf_contact_cutoff=0.25 * n)
-    d.update(kw)
-    return Spec(**d)
 
 
 @pytest.fixture(scope='module')

@@ -33,12 +33,12 @@ second normal) and a -> b again before an odd step.  The oracle side asserts
 that the case fits: no count reaches its cap or drops to zero, every k is at
 most the source's count.
 """
-from math import pi
 
 import numpy as np
 import pytest
 
 from ._dist_worker import OracleShard
+from ._models import box
 
 pytestmark = pytest.mark.gpu
 
@@ -77,13 +77,6 @@ CASES = {
 }
 SORTED_ROW_CASES = ('n37_64x1_ring', 'n64_64x1', 'n100_64x2_ring',
                     'n128_64x2')
-
-
-def box(n):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    return Spec(lattice_depth=5 * pi ** 2, lattice_ratio=1,
-                interaction_strength=2, boson_number=n, supercell_size=n,
-                tbf_contact_cutoff=0.25 * n)
 
 
 def start_positions(name):

@@ -13,97 +13,61 @@ one.
 """
 import functools
 from itertools import islice
-from math import comb, pi
+from math import comb
+from typing import NamedTuple
 
 import numpy as np
 import pytest
 
+from . import _dmc_walks as walks
 from . import _site_restatement as sr
+from ._dmc_walks import TIME_STEP, WALKS
+from ._models import box
 
 pytestmark = pytest.mark.gpu
 
-TIME_STEP = 1e-3
 RATIO = 1
 HALF_ZB = sr.half_barrier(RATIO)
 
 
-def box(n, sites, cut=0.25):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    return Spec(lattice_depth=5 * pi ** 2, lattice_ratio=RATIO,
-                interaction_strength=2, boson_number=n, supercell_size=sites,
-                tbf_contact_cutoff=cut * sites)
+class Case(NamedTuple):
+    walk: str                   # of _dmc_walks.WALKS
+    P: int                      # occupation bins
+    D: int                      # distances
+    steps: int
+    pfw: int
 
 
-# tag: (N, S, P, D, start walkers, max walkers, steps, pfw, contact cutoff / L,
-#       seed).  `Spec` accepts every shape as the cases were set.
-WAVEFRONTS = 4096               # of an estimator launch: 1024 blocks of 4
+# `Spec` accepts every shape as the cases were set.
 CASES = {
-    'odd':         (5, 5, 3, 5, 40, 64, 8, 3, 0.25, 2100),
-    'occ_only':    (16, 16, 1, 0, 48, 64, 6, 3, 0.25, 22),
-    'many':        (16, 16, 17, 16, 48, 64, 6, 3, 0.25, 23),
-    'dilute':      (8, 32, 4, 17, 48, 64, 6, 3, 0.25, 24),
-    'dense':       (64, 16, 4, 9, 100, 160, 6, 3, 0.25, 25),
-    'wave':        (64, 64, 8, 33, 300, 512, 10, 4, 0.25, 26),
-    'two_pass':    (100, 200, 56, 200, 64, 96, 6, 3, 0.1, 27),
-    'cap':         (16, 16, 5, 9, 64, 64, 8, 3, 0.25, 2600),
-    'second_trip': (37, 37, 5, 19, 4500, 5120, 4, 2, 0.25, 2700),
+    'odd':         Case('site_odd', 3, 5, 8, 3),
+    'occ_only':    Case('site_occ_only', 1, 0, 6, 3),
+    'many':        Case('site_many', 17, 16, 6, 3),
+    'dilute':      Case('site_dilute', 4, 17, 6, 3),
+    'dense':       Case('site_dense', 4, 9, 6, 3),
+    'wave':        Case('site_wave', 8, 33, 10, 4),
+    'two_pass':    Case('site_two_pass', 56, 200, 6, 3),
+    'cap':         Case('site_cap', 5, 9, 8, 3),
+    'second_trip': Case('site_second_trip', 5, 19, 4, 2),
 }
 
 
-def start_positions(tag):
-    n, S, _, _, nw0, _, _, _, _, seed = CASES[tag]
-    return S * np.random.RandomState(seed).random_sample((nw0, n))
-
-
-def _ensemble(eng, tag):
-    from phd_qmclib_amd.engine import DmcEnsemble
-    _, _, _, _, nw0, maxw, _, _, _, seed = CASES[tag]
-    d = DmcEnsemble(eng, TIME_STEP, maxw, nw0, 0.5, rng_seed=seed)
-    d.set_state(start_positions(tag))
-    return d
-
-
-def _engine(tag):
-    from phd_qmclib_amd.engine import ModelEngine
-    n, S, _, _, _, _, _, _, cut, _ = CASES[tag]
-    return ModelEngine(box(n, S, cut).cfc_spec, device=0)
+def walk_of(tag):
+    return WALKS[CASES[tag].walk]
 
 
 @functools.lru_cache(maxsize=None)
 def reference(tag):
-    """Ensemble A: the per-step states of the block and the restatement's rows
-    on them, computed once per case -> dict."""
-    n, S, P, D, _, _, T, pfw, _, _ = CASES[tag]
-    eng = _engine(tag)
-    a = _ensemble(eng, tag)
-    steps, energy = [], []
-    for _ in range(T):
-        ser = a.run_block(1)
-        s = a.get_state()
-        steps.append((s.confs[:, 0, :].copy(), s.cloning_ref.copy(),
-                      int(s.num_walkers)))
-        energy.append(ser.energy[0])
-    a.close()
-    eng.close()
-    mixed, pure, amb = sr.forward_walk(steps, float(S), HALF_ZB, P, D, pfw)
+    """Ensemble A's states of the block and the restatement's rows on them,
+    computed once per case -> dict."""
+    case = CASES[tag]
+    rec = walks.record(case.walk, case.steps)
+    mixed, pure, amb = sr.forward_walk(
+        rec['steps'], float(walk_of(tag).sites), HALF_ZB, case.P, case.D,
+        case.pfw)
     for arr in (mixed, pure):
         arr.setflags(write=False)
-    return dict(steps=steps, mixed=mixed, pure=pure, ambiguous=amb,
-                energy=np.array(energy),
-                num_walkers=np.array([s[2] for s in steps]))
-
-
-OTHERS = dict(num_modes=8, ssf_pure=True, ssf_pfw=3, num_bins=12,
-              dens_pure=False)
-
-
-def _set_others(b):
-    """Every other estimator of the ensemble."""
-    b.set_estimators(**OTHERS)
-    b.set_pair_dist_estimator(10, pure=True, pfw=3)
-    b.set_cm_diffusion_estimator(True)
-    b.set_isf_estimator(3, 2, 2)
-    b.set_obdm_estimator([0.0, 0.5, 1.25], 2)
+    return dict(rec, mixed=mixed, pure=pure, ambiguous=amb)
 
 
 def _read_others(b, T):
@@ -116,16 +80,17 @@ def run_block_b(tag, pure, eval_estimators=True, others=False, order=0,
     """Ensemble B: one estimator block -> (series, site rows, rows of the
     other estimators); `others` sets all the other estimators as well, before
     (order 0) or after (order 1) the site estimator."""
-    _, _, P, D, _, _, T, pfw, _, _ = CASES[tag]
-    eng = _engine(tag)
-    b = _ensemble(eng, tag)
+    case = CASES[tag]
+    P, D, T, pfw = case.P, case.D, case.steps, case.pfw
+    eng = walks.engine(walk_of(tag))
+    b = walks.ensemble(eng, walk_of(tag))
     if others and order == 0:
-        _set_others(b)
+        walks.set_others(b, **walks.ALL_SLOTS)
     if with_site:
         b.set_site_estimator(P, D, pure=pure, pfw=pfw)
         assert b.site_shape == (P, D)
     if others and order == 1:
-        _set_others(b)
+        walks.set_others(b, **walks.ALL_SLOTS)
     ser, ssf, dens = b.run_block_est(T, eval_estimators)
     rows = b.read_site(T) if with_site else None
     rest = (ssf, dens) + _read_others(b, T) if others else ()
@@ -134,33 +99,17 @@ def run_block_b(tag, pure, eval_estimators=True, others=False, order=0,
     return ser, rows, rest
 
 
-def _numerators(rows, T, pfw, pure):
-    """The integers behind the rows: a pure entry is the rounded quotient of
-    an integer by min(t + 1, pfw), which each entry must give back bit for
-    bit -> (counts[T, K], div[T, 1])."""
-    div = np.minimum(np.arange(T) + 1, pfw if pure else 1)[:, None]
-    counts = np.rint(rows * div)
-    assert np.array_equal(counts / div, rows)
-    return counts, div
-
-
 @pytest.mark.parametrize('pure', [False, True], ids=['mixed', 'pure'])
 @pytest.mark.parametrize('tag', list(CASES))
 def test_rows_equal_the_forward_walking(tag, pure):
-    n, S, P, D, nw0, maxw, T, pfw, _, _ = CASES[tag]
+    case = CASES[tag]
+    n, S = walk_of(tag).n, walk_of(tag).sites
+    P, D, T, pfw = case.P, case.D, case.steps, case.pfw
     ref = reference(tag)
     assert ref['ambiguous'] == [], \
         'a particle sits on a site boundary: choose another seed ' + \
         repr(ref['ambiguous'][:4])
-    # the transport is exercised: a step whose cloning table is not the
-    # identity, and a population that changes
-    assert any(not np.array_equal(r[:nw], np.arange(nw))
-               for _, r, nw in ref['steps'])
-    assert len(set(ref['num_walkers']) | {nw0}) > 1
-    if tag == 'cap':
-        assert nw0 == maxw
-    if tag == 'second_trip':
-        assert maxw >= 5120 and (ref['num_walkers'] > WAVEFRONTS).all()
+    walks.assert_transport_exercised(ref, walk_of(tag), tag)
     if tag == 'two_pass':
         assert P + D == 256 and n > 64 and S > 64 and D > 64
     if pure:
@@ -173,7 +122,7 @@ def test_rows_equal_the_forward_walking(tag, pure):
     assert rows.shape == (T, P + D)
     assert np.array_equal(rows, want), np.argwhere(rows != want)[:8]
     # the identities of a row, on the integer numerators
-    counts, div = _numerators(rows, T, pfw, pure)
+    counts, div = walks.numerators(rows, T, pfw, pure)
     # (the row of a pure walker holds the min(t + 1, pfw) steps of its
     # lineage, so the identities hold for both with the walkers times steps)
     steps_in = ref['num_walkers'] * div[:, 0]
@@ -196,7 +145,7 @@ def test_rows_equal_the_forward_walking(tag, pure):
 @pytest.mark.parametrize('pure', [False, True], ids=['mixed', 'pure'])
 def test_deterministic_and_burn_in(pure):
     tag = 'wave'
-    _, _, P, D, _, _, T, _, _, _ = CASES[tag]
+    P, D, T = CASES[tag].P, CASES[tag].D, CASES[tag].steps
     s1, r1, _ = run_block_b(tag, pure)
     s2, r2, _ = run_block_b(tag, pure)
     assert r1.tobytes() == r2.tobytes()
@@ -224,8 +173,7 @@ def test_independent_of_the_other_estimators(pure):
     # the walk itself does not know about the estimator
     ref = reference(tag)
     for run in (alone, first, second, without):
-        for x, y in zip(run[0], alone[0]):
-            assert x.tobytes() == y.tobytes()
+        walks.assert_same_series(run[0], alone[0])
         assert np.array_equal(run[0].energy, ref['energy'])
         assert np.array_equal(run[0].num_walkers, ref['num_walkers'])
 
@@ -238,24 +186,25 @@ def test_resetting_a_live_ensemble_equals_a_fresh_one(second_pure):
     seed, same state, one estimator block each."""
     from phd_qmclib_amd.engine import DmcEnsemble
     tag = 'many'
-    n, S, P, D, nw0, maxw, T, pfw, _, seed = CASES[tag]
+    case, walk = CASES[tag], walk_of(tag)
+    S, P, D, T, pfw = walk.sites, case.P, case.D, case.steps, case.pfw
     wide = dict(num_occ=P, num_dist=D, pure=True, pfw=pfw)
     narrow = dict(num_occ=3, num_dist=4, pure=False)
     configs = [narrow, wide] if second_pure else [wide, narrow]
-    eng = _engine(tag)
+    eng = walks.engine(walk)
     runs = []
     for todo in (configs, configs[1:]):              # R, then F
-        d = DmcEnsemble(eng, TIME_STEP, maxw, nw0, 0.5, rng_seed=seed)
+        d = DmcEnsemble(eng, TIME_STEP, walk.maxw, walk.nw0, 0.5,
+                        rng_seed=walk.seed)
         for cfg in todo:
             d.set_site_estimator(**cfg)
-        d.set_state(start_positions(tag))
+        d.set_state(walks.start_positions(walk))
         ser, _, _ = d.run_block_est(T)
         runs.append((ser, d.read_site(T)))
         d.close()
     eng.close()
     (ser_r, rows_r), (ser_f, rows_f) = runs
-    for x, y in zip(ser_r, ser_f):
-        assert x.tobytes() == y.tobytes()
+    walks.assert_same_series(ser_r, ser_f)
     assert rows_r.tobytes() == rows_f.tobytes()
     assert rows_r.shape == (T, P + D if second_pure else 7)
     assert rows_r.any(axis=1).all()
@@ -274,9 +223,10 @@ def test_switching_off_and_errors():
     from phd_qmclib_amd.engine import DmcEnsemble, ModelEngine
     from phd_qmclib_amd._lib import QmcError
     tag = 'odd'
-    n, S, P, D, _, _, T, pfw, _, _ = CASES[tag]
-    eng = _engine(tag)
-    d = _ensemble(eng, tag)
+    case, S = CASES[tag], walk_of(tag).sites
+    P, D, T, pfw = case.P, case.D, case.steps, case.pfw
+    eng = walks.engine(walk_of(tag))
+    d = walks.ensemble(eng, walk_of(tag))
     who = 'qmc_dmc_set_site_estimator'
     for bad in (dict(num_occ=-1), dict(num_occ=2, num_dist=-1),
                 dict(num_occ=2, num_dist=S + 1), dict(num_occ=257),
@@ -304,10 +254,7 @@ def test_switching_off_and_errors():
     eng.close()
     # the sites are the periods of the lattice: a supercell that does not
     # hold a whole number of them has none
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    spec = Spec(lattice_depth=5 * pi ** 2, lattice_ratio=RATIO,
-                interaction_strength=2, boson_number=5, supercell_size=5.5,
-                tbf_contact_cutoff=1.25)
+    spec = box(5, supercell_size=5.5)
     eng = ModelEngine(spec.cfc_spec, device=0)
     d = DmcEnsemble(eng, TIME_STEP, 64, 40, 0.5, rng_seed=1)
     with pytest.raises(QmcError, match=who + '.*supercell_size'):
@@ -318,29 +265,17 @@ def test_switching_off_and_errors():
 
 
 def test_distributed_dmc_refuses_the_estimator():
-    from phd_qmclib_amd.dist import DistributedDmc
-    import torch
-    from phd_qmclib_amd.engine import DmcEnsemble, ModelEngine
-    eng = ModelEngine(box(16, 16).cfc_spec,
-                      stream=torch.cuda.current_stream().cuda_stream)
-    d = DmcEnsemble(eng, TIME_STEP, 64, 48, 0.5, rng_seed=2,
-                    external_reduce=True)
-    d.set_state(start_positions('many'))
-    d.set_site_estimator(4, 3)
-    with pytest.raises(NotImplementedError, match='site occupation'):
-        DistributedDmc(d, 16, 'cuda', solo=True)
-    d.set_site_estimator(0)
-    DistributedDmc(d, 16, 'cuda', solo=True)
-    d.close()
-    eng.close()
+    walks.assert_refused_by_distributed(
+        walk_of('many'), lambda d: d.set_site_estimator(4, 3),
+        lambda d: d.set_site_estimator(0), 'site occupation', rng_seed=2)
 
 
 # ---- top level ------------------------------------------------------------
 def test_sampling_blocks_fill_iter_site():
     from phd_qmclib_amd import mrbp_qmc
-    spec = box(16, 16)
+    spec = box(16)
     confs = np.zeros((48, 2, 16))
-    confs[:, 0, :] = start_positions('many')
+    confs[:, 0, :] = walks.start_positions(walk_of('many'))
     kw = dict(max_num_walkers=64, target_num_walkers=48, rng_seed=13)
     plain = mrbp_qmc.dmc.Sampling(spec, TIME_STEP, **kw)
     with_site = mrbp_qmc.dmc.Sampling(
@@ -356,7 +291,7 @@ def test_sampling_blocks_fill_iter_site():
         assert np.array_equal(p.iter_props.energy, q.iter_props.energy)
     assert not b1[0].iter_site.any()                 # the burn-in block
     nw = b1[1].iter_props.num_walkers.astype(np.int64)
-    counts, div = _numerators(b1[1].iter_site, 6, 3, True)
+    counts, div = walks.numerators(b1[1].iter_site, 6, 3, True)
     assert np.array_equal(counts[:, :5].sum(axis=1), nw * div[:, 0] * 16)
 
 
@@ -365,7 +300,7 @@ def test_proc_exec_yields_site_blocks(tmp_path):
     from phd_qmclib_amd.engine import site_statistics
     from phd_qmclib_amd.qmc_exec.data import dmc as dd
     dx = mrbp_qmc.dmc_exec
-    spec = box(16, 16)
+    spec = box(16)
     P, D = 6, 9
     np.random.seed(5)
     kw = dict(max_num_walkers=512, target_num_walkers=480, rng_seed=7,
@@ -433,11 +368,9 @@ def test_free_particles_follow_the_multinomial_law():
     of the seeds exceed 4, so the blocks must not be shortened."""
     from phd_qmclib_amd.engine import (DmcEnsemble, ModelEngine,
                                        site_statistics)
-    from phd_qmclib_amd.mrbp_qmc import Spec
     N = S = 8
     P, D, W, T, NB = 6, 5, 2048, 64, 16
-    spec = Spec(lattice_depth=0, lattice_ratio=RATIO, interaction_strength=0,
-                boson_number=N, supercell_size=S, tbf_contact_cutoff=2)
+    spec = box(N, depth=0, gint=0)
     eng = ModelEngine(spec.cfc_spec, device=0)
     d = DmcEnsemble(eng, 5e-2, 2560, W, 0.5, rng_seed=31)
     d.set_state(S * np.random.RandomState(32).random_sample((W, N)))

@@ -24,7 +24,8 @@ must stay 0: the values compared here did come from it."""
 import numpy as np
 import pytest
 
-from .test_gpu_parity import RTOL, close, spec_from_golden, worst
+from ._models import spec_from_golden
+from .test_gpu_parity import RTOL, close, worst
 
 pytestmark = pytest.mark.gpu
 

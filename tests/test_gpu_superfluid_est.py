@@ -5,120 +5,74 @@ twin ensemble, and against its exact rule in a translation invariant system.
 Ensemble A and ensemble B start from the same positions with the same seed, so
 they follow the same trajectory (test_gpu_sampling.py::
 test_dmc_split_step_equals_block).  A runs one time step at a time and hands
-out its State after each; B runs one estimator block.
-
-Rounding bound of the comparison.  The kernel sums the N differences
-c_i - p_i of two rows, the restatement subtracts the sums of two yielded rows;
-every term is below L in magnitude and every partial sum below N L, so any
-order of either sum errs by at most g = 4 N^2 L 2^-53 (N additions, each off by
-at most half an ulp of N L, on both sides, with a factor two to spare), and as
-long as both pick the same image (max |d| < L / 4 is asserted) the minimum
-image step does not add to it.  Y_t is a sum of at most T such steps:
-|Y - Y'| <= T g.  Hence, per row,
-
-    |sum_s Y   - sum_s Y'  | <= nw T g
-    |sum_s Y^2 - sum_s Y'^2| <= nw 2 max|Y| T g
-
-(the second to first order in T g, which is below 1e-9 here).  The sums over
-the walkers themselves, in whatever order, err by at most nw 2^-53 times their
-largest partial sum, nw max|Y| or nw max|Y|^2: that fits into the factor two
-spared above as long as nw max|Y| <= 2 T N^2 L, which is asserted.  The
-tolerances are computed from these in the test; nothing is fitted to what the
-kernel gives.
+out its State after each; B runs one estimator block.  The rounding bound of
+the comparison is `tolerance` of the restatement, derived in its docstring;
+nothing is fitted to what the kernel gives.
 """
 import functools
 from itertools import islice
-from math import pi
+from typing import NamedTuple
 
 import numpy as np
 import pytest
 
 from . import _cmdiff_restatement as cm
+from . import _dmc_walks as walks
+from ._dmc_walks import EST, G2, TIME_STEP, WALKS
+from ._models import box
 
 pytestmark = pytest.mark.gpu
 
-TIME_STEP = 1e-3
+
+class Case(NamedTuple):
+    walk: str                   # of _dmc_walks.WALKS
+    steps: int
 
 
-def box(n, cut=0.25, depth=5 * pi ** 2, gint=2):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    return Spec(lattice_depth=depth, lattice_ratio=1,
-                interaction_strength=gint, boson_number=n, supercell_size=n,
-                tbf_contact_cutoff=cut * n)
-
-
-# tag: (N, contact cutoff / L, start walkers, max walkers, steps, seed): the
-# shapes of test_gpu_pairdist_est.py.  An odd N below a wavefront; N = 16; N =
-# 64, one index per lane, with more walkers than one pass of a block's
-# wavefronts; N = 100, two passes over the indices; a population that starts
-# at its cap; more live walkers than the launch has wavefronts, so that every
-# wavefront goes round its slot loop again.
-WAVEFRONTS = 4096               # of an estimator launch: 1024 blocks of 4
+# An odd N below a wavefront; N = 16; N = 64, one index per lane, with more
+# walkers than one pass of a block's wavefronts; N = 100, two passes over the
+# indices; a population that starts at its cap; more live walkers than the
+# launch has wavefronts, so that every wavefront goes round its slot loop
+# again.
 CASES = {
-    'odd':      (5, 0.25, 40, 64, 8, 1100),
-    'mid':      (16, 0.25, 48, 64, 6, 13),
-    'wave':     (64, 0.25, 300, 512, 10, 14),
-    'two_pass': (100, 0.1, 64, 96, 6, 15),
-    'cap':      (16, 0.25, 64, 64, 8, 1600),
-    'second_trip': (37, 0.25, 4500, 5120, 4, 1700),
+    'odd':         Case('odd', 8),
+    'mid':         Case('many', 6),
+    'wave':        Case('wave', 10),
+    'two_pass':    Case('two_pass', 6),
+    'cap':         Case('cap', 8),
+    'second_trip': Case('second_trip', 4),
 }
-EST = dict(num_modes=8, ssf_pure=True, ssf_pfw=3, num_bins=12, dens_pure=False)
-G2 = dict(num_bins=20, pure=True, pfw=3)
 
 
-def start_positions(tag):
-    n, _, nw0, _, _, seed = CASES[tag]
-    return n * np.random.RandomState(seed).random_sample((nw0, n))
-
-
-def _ensemble(eng, tag, **kw):
-    from phd_qmclib_amd.engine import DmcEnsemble
-    _, _, nw0, maxw, _, seed = CASES[tag]
-    d = DmcEnsemble(eng, TIME_STEP, maxw, nw0, 0.5, rng_seed=seed, **kw)
-    d.set_state(start_positions(tag))
-    return d
+def walk_of(tag):
+    return WALKS[CASES[tag].walk]
 
 
 @functools.lru_cache(maxsize=None)
 def reference(tag):
-    """Ensemble A: the per-step states of the block and the restatement's rows
-    on them, computed once per case -> dict."""
-    from phd_qmclib_amd.engine import ModelEngine
-    n, cut, _, _, T, _ = CASES[tag]
-    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
-    a = _ensemble(eng, tag)
-    steps, energy = [], []
-    for _ in range(T):
-        ser = a.run_block(1)
-        s = a.get_state()
-        steps.append((s.confs[:, 0, :].copy(), s.cloning_ref.copy(),
-                      int(s.num_walkers)))
-        energy.append(ser.energy[0])
-    a.close()
-    eng.close()
-    rows, wrapped, max_d = cm.cm_diffusion(steps, float(n))
+    """Ensemble A's states of the block and the restatement's rows on them,
+    computed once per case -> dict."""
+    rec = walks.record(CASES[tag].walk, CASES[tag].steps)
+    L = float(walk_of(tag).n)
+    rows, wrapped, max_d = cm.cm_diffusion(rec['steps'], L)
     rows.setflags(write=False)
-    return dict(steps=steps, rows=rows, wrapped=wrapped, max_d=max_d,
-                max_y=cm.largest_y(steps, float(n)), energy=np.array(energy),
-                num_walkers=np.array([s[2] for s in steps]))
+    return dict(rec, rows=rows, wrapped=wrapped, max_d=max_d,
+                max_y=cm.largest_y(rec['steps'], L))
 
 
 def run_block_b(tag, on=True, eval_estimators=True, others=None):
     """Ensemble B: one estimator block -> (series, ssf, dens, g2 rows, cm
     rows); `others` sets S(k), the density and g2 as well, 'before' or 'after'
     the centre-of-mass diffusion."""
-    from phd_qmclib_amd.engine import ModelEngine
-    n, cut, _, _, T, _ = CASES[tag]
-    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
-    b = _ensemble(eng, tag)
+    T = CASES[tag].steps
+    eng = walks.engine(walk_of(tag))
+    b = walks.ensemble(eng, walk_of(tag))
     if others == 'before':
-        b.set_estimators(**EST)
-        b.set_pair_dist_estimator(**G2)
+        walks.set_others(b)
     if on:
         b.set_cm_diffusion_estimator()
     if others == 'after':
-        b.set_pair_dist_estimator(**G2)
-        b.set_estimators(**EST)
+        walks.set_others(b, reverse=True)
     ser, ssf, dens = b.run_block_est(T, eval_estimators)
     g2 = b.read_pair_dist(T) if others else None
     rows = b.read_cm_diffusion(T) if on else None
@@ -129,30 +83,20 @@ def run_block_b(tag, on=True, eval_estimators=True, others=None):
 
 @pytest.mark.parametrize('tag', list(CASES))
 def test_rows_equal_the_restatement(tag):
-    n, _, nw0, maxw, T, _ = CASES[tag]
+    n, T = walk_of(tag).n, CASES[tag].steps
     L = float(n)
     ref = reference(tag)
-    # the transport is exercised: a step whose cloning table is not the
-    # identity, a population that changes, a walker carried over the box edge;
-    # and the minimum image is never in doubt
-    assert any(not np.array_equal(r[:nw], np.arange(nw))
-               for _, r, nw in ref['steps'])
-    assert len(set(ref['num_walkers']) | {nw0}) > 1
+    # the transport is exercised, a walker is carried over the box edge, and
+    # the minimum image is never in doubt
+    walks.assert_transport_exercised(ref, walk_of(tag), tag)
     assert ref['wrapped'] > 0, 'no walker-step wrapped: choose another seed'
     assert ref['max_d'] < L / 4
-    if tag == 'cap':
-        assert nw0 == maxw
-    if tag == 'second_trip':
-        assert maxw >= 5120 and (ref['num_walkers'] > WAVEFRONTS).all()
     ser, _, _, _, rows = run_block_b(tag)
     assert np.array_equal(ser.num_walkers, ref['num_walkers'])
     assert np.array_equal(ser.energy, ref['energy'])
     want = ref['rows']
     assert rows.shape == (T, 2)
-    g = 4.0 * n * n * L * 2.0 ** -53
-    nw = ref['num_walkers'].astype(np.float64)
-    tol = np.stack([nw * T * g, nw * 2.0 * ref['max_y'] * T * g], axis=1)
-    assert nw.max() * ref['max_y'] <= 2.0 * T * n * n * L
+    tol = cm.tolerance(ref['steps'], n, L)     # (asserts its precondition)
     err = np.abs(rows - want)
     print(tag, 'walkers', ref['num_walkers'], 'wrapped', ref['wrapped'],
           'max|d|', ref['max_d'], 'max|Y|', ref['max_y'])
@@ -164,7 +108,7 @@ def test_rows_equal_the_restatement(tag):
 
 def test_deterministic_and_burn_in():
     tag = 'wave'
-    T = CASES[tag][4]
+    T = CASES[tag].steps
     s1, _, _, _, r1 = run_block_b(tag)
     s2, _, _, _, r2 = run_block_b(tag)
     assert r1.tobytes() == r2.tobytes()
@@ -172,8 +116,7 @@ def test_deterministic_and_burn_in():
     # a burn-in block propagates the same walkers and leaves the rows zero
     s0, _, _, _, r0 = run_block_b(tag, eval_estimators=False)
     assert r0.shape == (T, 2) and not r0.any()
-    for x, y in zip(s0, s1):
-        assert x.tobytes() == y.tobytes()
+    walks.assert_same_series(s0, s1)
 
 
 def test_the_walk_and_the_other_estimators_do_not_notice():
@@ -194,8 +137,7 @@ def test_the_walk_and_the_other_estimators_do_not_notice():
     for run in (alone, off, before, after, without):
         assert run[0].energy.tobytes() == ref['energy'].tobytes()
         assert np.array_equal(run[0].num_walkers, ref['num_walkers'])
-        for x, y in zip(run[0], off[0]):
-            assert x.tobytes() == y.tobytes()
+        walks.assert_same_series(run[0], off[0])
 
 
 def test_resetting_a_live_ensemble_equals_a_fresh_one():
@@ -204,13 +146,14 @@ def test_resetting_a_live_ensemble_equals_a_fresh_one():
     set once, to R's last configuration.  Same seed, same state, one estimator
     block each: every buffer of R was dropped and sized anew, so its rows are
     F's byte for byte."""
-    from phd_qmclib_amd.engine import DmcEnsemble, ModelEngine
+    from phd_qmclib_amd.engine import DmcEnsemble
     tag = 'mid'
-    n, cut, nw0, maxw, T, seed = CASES[tag]
-    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
+    walk, T = walk_of(tag), CASES[tag].steps
+    eng = walks.engine(walk)
     runs = []
     for again in (True, False):                      # R, then F
-        d = DmcEnsemble(eng, TIME_STEP, maxw, nw0, 0.5, rng_seed=seed)
+        d = DmcEnsemble(eng, TIME_STEP, walk.maxw, walk.nw0, 0.5,
+                        rng_seed=walk.seed)
         if again:
             d.set_estimators(num_modes=5, num_bins=0)
             d.set_cm_diffusion_estimator()
@@ -219,27 +162,25 @@ def test_resetting_a_live_ensemble_equals_a_fresh_one():
         d.set_estimators(**EST)
         d.set_cm_diffusion_estimator()
         d.set_pair_dist_estimator(**G2)
-        d.set_state(start_positions(tag))
+        d.set_state(walks.start_positions(walk))
         ser, ssf, dens = d.run_block_est(T)
         runs.append((ser, ssf, dens, d.read_pair_dist(T),
                      d.read_cm_diffusion(T)))
         d.close()
     eng.close()
     r, f = runs
-    for x, y in zip(r[0], f[0]):
-        assert x.tobytes() == y.tobytes()
+    walks.assert_same_series(r[0], f[0])
     for k in (1, 2, 3, 4):
         assert r[k].tobytes() == f[k].tobytes() and r[k].any()
     assert r[4].shape == (T, 2)
 
 
 def test_switching_off_and_errors():
-    from phd_qmclib_amd.engine import ModelEngine
     from phd_qmclib_amd._lib import QmcError
     tag = 'odd'
-    n, cut, _, _, T, _ = CASES[tag]
-    eng = ModelEngine(box(n, cut).cfc_spec, device=0)
-    d = _ensemble(eng, tag)
+    T = CASES[tag].steps
+    eng = walks.engine(walk_of(tag))
+    d = walks.ensemble(eng, walk_of(tag))
     with pytest.raises(QmcError):
         d.read_cm_diffusion(1)               # the estimator is off
     d.set_cm_diffusion_estimator()
@@ -264,19 +205,10 @@ def test_switching_off_and_errors():
 
 
 def test_distributed_dmc_refuses_the_estimator():
-    from phd_qmclib_amd.dist import DistributedDmc
-    import torch
-    from phd_qmclib_amd.engine import ModelEngine
-    eng = ModelEngine(box(16).cfc_spec,
-                      stream=torch.cuda.current_stream().cuda_stream)
-    d = _ensemble(eng, 'mid', external_reduce=True)
-    d.set_cm_diffusion_estimator()
-    with pytest.raises(NotImplementedError, match='centre-of-mass diffusion'):
-        DistributedDmc(d, 16, 'cuda', solo=True)
-    d.set_cm_diffusion_estimator(False)
-    DistributedDmc(d, 16, 'cuda', solo=True)
-    d.close()
-    eng.close()
+    walks.assert_refused_by_distributed(
+        walk_of('mid'), lambda d: d.set_cm_diffusion_estimator(),
+        lambda d: d.set_cm_diffusion_estimator(False),
+        'centre-of-mass diffusion')
 
 
 # ---- top level ------------------------------------------------------------
@@ -284,7 +216,7 @@ def test_sampling_blocks_fill_iter_cm_diffusion():
     from phd_qmclib_amd import mrbp_qmc
     spec = box(16)
     confs = np.zeros((48, 2, 16))
-    confs[:, 0, :] = start_positions('mid')
+    confs[:, 0, :] = walks.start_positions(walk_of('mid'))
     kw = dict(max_num_walkers=64, target_num_walkers=48, rng_seed=13)
     plain = mrbp_qmc.dmc.Sampling(spec, TIME_STEP, **kw)
     with_cm = mrbp_qmc.dmc.Sampling(

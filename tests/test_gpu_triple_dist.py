@@ -20,6 +20,7 @@ import pytest
 
 from . import _pairdist_restatement as pd
 from . import _tripledist_restatement as rs
+from ._models import _dev
 
 pytestmark = pytest.mark.gpu
 
@@ -63,12 +64,6 @@ def check_counts(dev, ref, n):
     assert np.all(dev.sum(axis=1, dtype=np.int64) == (comb(n, 3) if n >= 3
                                                       else 0))
     assert np.array_equal(dev.astype(np.int64), ref)
-
-
-def _dev(eng, a):
-    from phd_qmclib_amd.engine import DeviceBuffer
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    return DeviceBuffer(a.shape, eng.device).upload(a)
 
 
 def counts_dev(eng, dpos, W, B, D):

@@ -8,22 +8,16 @@ general-path counter; and a DMC ensemble built from a fused block.  The move
 spread here is exactly 0.125 (a quarter of the well width), at which the
 product vmc_move_unit * move_spread is exact; the spreads at which it rounds
 are in tests/test_gpu_generic_steps.py."""
-from math import pi
 
 import numpy as np
 import pytest
+
+from ._models import box
 
 pytestmark = pytest.mark.gpu
 
 # 200 chains: not a multiple of the 128-workgroup rounding of the grid
 W = 200
-
-
-def box(n):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    return Spec(lattice_depth=5 * pi ** 2, lattice_ratio=1,
-                interaction_strength=2, boson_number=n, supercell_size=n,
-                tbf_contact_cutoff=0.25 * n)
 
 
 def lattice(n, seed):

@@ -4,19 +4,13 @@ compact arrays of get_state / block_sums_dev and the sums of run_block, after
 blocks of several yields -- the first yield of a block runs the general LEAN
 kernel, the later ones its steady-state variant -- compared bit for bit with
 the per-step series of the non-LEAN kernel on the same stream."""
-from math import pi
 
 import numpy as np
 import pytest
 
+from ._models import box
+
 pytestmark = pytest.mark.gpu
-
-
-def box(n):
-    from phd_qmclib_amd.mrbp_qmc import Spec
-    return Spec(lattice_depth=5 * pi ** 2, lattice_ratio=1,
-                interaction_strength=2, boson_number=n, supercell_size=n,
-                tbf_contact_cutoff=0.25 * n)
 
 
 def device_sums(ens, W):
