@@ -137,6 +137,16 @@ static constexpr int LB_VMC_P2 = 4;
 // (Round 6: the fused steady kernel of the N <= 64 shape takes 67 registers --
 // 7 waves, no scratch; held to 8 waves it spills 12 bytes per lane, and the
 // two measure the same, profiles/r06_ab_variants.txt.)
+// (Round 12: that does not go on below 7.  The fused steady kernels of this
+// shape were given a bound of their own, 6 and 5 waves, to buy registers for
+// values kept across the yields.  The padded kernel takes 76 at either bound
+// -- 6 waves -- and its step is 2.5-2.9 % SLOWER with nothing else changed;
+// with the lane constants kept in registers as well, 80, it is still 1.0 %
+// slower than at 7 waves.  The unpadded kernel takes 71, 7 waves all the same,
+// and is 2.3 % slower for the other allocation alone; at 79 with the lane
+// constants kept, 6 waves, 0.5 % slower.  The fused kernels keep the bound of
+// the shape, and what they keep across the yields has to fit 72 registers:
+// profiles/r12_ab_variants.txt.)
 // The minimum waves per SIMD of a kernel on shape (G, P, ZC); `p2` is the
 // kernel's figure for the sorted-row N <= 128 shape (1: none).
 constexpr int lb_waves(int G, int P, bool ZC, int p2)
@@ -329,7 +339,8 @@ struct VmcArgs {
 // N <= 64 takes 67 -- 7 waves instead of 8, no scratch -- and the 66 <= N <= 128
 // shape 115 (4 waves, as its per-yield kernel).  Measured against the per-yield
 // launches, profiles/r06_ab_variants.txt: -9.5 % per step at N = 64, -8.8 % at
-// N = 48, -8.5 % at N = 128.
+// N = 48, -8.5 % at N = 128.  (Round 12: the unpadded N = 64 kernel hoists them
+// after all, at 72 registers -- the comment at the yield loop.)
 template <int G, int P, bool ZC>
 struct VmcFused {
     static constexpr bool ON = G == 64 && !ZC && (P == 1 || P == 2);
@@ -413,10 +424,18 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
     [[maybe_unused]] const int gl_top = gl;
     for (unsigned int s = 0; s < nst; ++s) {
     const unsigned int step = a.step + s;
-    // (FUSED: what the sort and the pair sums derive from the lane index is
-    // derived again on every trip instead of being hoisted out of the loop and
-    // held in registers across it)
-    const int gl = FUSED ? qmc_opaque(gl_top) : gl_top;
+    // (FUSED: what the sort and the pair sums derive from the lane index --
+    // partner addresses and flip masks of the sort, LDS row pointers of both
+    // pair passes, parity and half-wave flags -- is loop-invariant.  The
+    // unpadded one-particle-per-lane kernel holds it in registers across the
+    // yields: 72 registers, the last of the 7-wave budget, no scratch, 1.5 %
+    // off the step.  The padded kernel spills 20 bytes per lane if it does the
+    // same, and the two-particles-per-lane kernels were not part of that trial
+    // (statically 125 registers instead of 119, 4 waves): there it is derived
+    // again on every trip, from a lane index the compiler cannot see through.
+    // profiles/r12_ab_variants.txt.)
+    constexpr bool REDERIVE = FUSED && (P != 1 || PAD);
+    const int gl = REDERIVE ? qmc_opaque(gl_top) : gl_top;
     if constexpr (FUSED) {
         // (a block longer than 64 yields refills every 64 trips)
         if ((s & 63u) == 0u)
