@@ -429,6 +429,45 @@ int qmc_particle_swap_dev(qmc_engine *eng, int64_t nconf,
 int qmc_particle_swap_reduce_dev(qmc_engine *eng, int64_t nconf,
                                  const double *pos_dev, double *sums_dev);
 
+/* One-body density matrix rho1(x, x') on a grid (no counterpart in the
+ * reference): what g1(s) integrates away in a lattice.  num_points = M uniform
+ * cells of [0, L), delta = L / M, centres x_c = (c + 1/2) L / M (rounded in
+ * that order: the product, then the quotient).  For one
+ * configuration, z_i the image of particle i in [0, L) and
+ * a(i) = min(floor(z_i / delta), M - 1) its row bin (a particle on the edge
+ * a delta counts in bin a),
+ *   R_conf[a][c] = sum_{i : a(i) = a} psi(z_1 .. z_i -> x_c .. z_N) / psi(R),
+ * the ratio being that of qmc_obdm at the shift x_c - z_i (the argument of exp
+ * clamped to +-700): the row follows the particle's actual position, the
+ * column is the cell centre, so that the average over |psi|^2 is
+ * int_{bin a} rho1(x, x_c) dx ~ delta rho1(x_a, x_c).  The symmetrised mean
+ * has the occupations of the natural orbitals as eigenvalues (sum ~ N; the
+ * largest over N is the condensate fraction).  The call reduces over the
+ * configurations itself, into num_groups = G independent sums
+ *   sums[G][M][M]: sums[g][a][c] = sum_{conf = g (mod G)} w_conf R_conf[a][c]
+ *   wsum[G]:       wsum[g]       = sum_{conf = g (mod G)} w_conf
+ * (w NULL: unit weights; wsum may be NULL).  Summation order: a group is cut
+ * into S interleaved partial sums (member q of the group goes to q mod S; S a
+ * function of nconf, M, G and N alone), each adds its configurations in rising
+ * index and the particles of a configuration in the order of the row, and the
+ * partial sums are added in rising order; wsum by 256 strided partial sums and
+ * a fixed tree.  No floating-point atomics: two calls give the same bits.
+ * The particles of a row may come in any order.  Always fp64:
+ * qmc_engine_set_fast_math does not apply (csrc/qmc_obdm_grid.h).
+ * Limits: N <= 512, M in [1, 512], G in [1, 1024] and G <= nconf, nconf > 0;
+ * anything else, or a NULL pos or sums, is an error and leaves the outputs
+ * untouched.
+ * qmc_obdm_grid: host buffers, synchronous. */
+int qmc_obdm_grid(qmc_engine *eng, int64_t nconf, const double *pos,
+                  const double *w, int32_t num_points, int32_t num_groups,
+                  double *sums, double *wsum);
+/* Same on device-resident buffers, asynchronous on the engine's stream; the
+ * partial sums live in an engine-owned scratch of at most 128 MB (S = 1:
+ * in sums_dev itself). */
+int qmc_obdm_grid_dev(qmc_engine *eng, int64_t nconf, const double *pos_dev,
+                      const double *w_dev, int32_t num_points,
+                      int32_t num_groups, double *sums_dev, double *wsum_dev);
+
 /* Plain device buffers, so that a configuration set can stay resident across
  * many qmc_evaluate_dev calls with different engines: the correlated-sampling
  * optimiser re-evaluates wf_abs_log / energy of one fixed set for every trial
@@ -505,6 +544,13 @@ int qmc_vmc_renyi_swap(qmc_vmc *v, int32_t nlen, const double *lengths,
  * the device and the chain state is not touched.  An odd num_chains is an
  * error.  Host buffer; synchronous. */
 int qmc_vmc_particle_swap(qmc_vmc *v, double *out);
+/* Density-matrix sums on a grid of the CURRENT configurations, group = chain
+ * index mod num_groups, unit weights: sums[num_groups][M][M] as sums of
+ * qmc_obdm_grid, on the resident rows, after either move type (nothing depends
+ * on the order of a row); no position leaves the device and the chain state
+ * is not touched.  num_groups <= num_chains.  Host buffer; synchronous. */
+int qmc_vmc_obdm_grid(qmc_vmc *v, int32_t num_points, int32_t num_groups,
+                      double *sums);
 /* Device addresses of the per-chain block sums of the last block
  * (sum_e[W], sum_e2[W], n_acc[W]) for on-device reductions / collectives. */
 int qmc_vmc_block_sums_dev(qmc_vmc *v, double **sum_e, double **sum_e2,

@@ -122,6 +122,10 @@ SIGNATURES = {
     'qmc_particle_swap': (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp]),
     'qmc_particle_swap_dev': (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp]),
     'qmc_particle_swap_reduce_dev': (C.c_int, [_vp, C.c_int64, _vp, _vp]),
+    'qmc_obdm_grid': (C.c_int, [_vp, C.c_int64, _dp, _dp, C.c_int32,
+                                C.c_int32, _dp, _dp]),
+    'qmc_obdm_grid_dev': (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int32,
+                                    C.c_int32, _vp, _vp]),
     'qmc_buffer_alloc': (C.c_int, [C.c_int, C.c_size_t, C.POINTER(_vp)]),
     'qmc_buffer_free': (C.c_int, [_vp]),
     'qmc_buffer_upload': (C.c_int, [_vp, _vp, C.c_size_t]),
@@ -136,6 +140,7 @@ SIGNATURES = {
     'qmc_vmc_triple_dist': (C.c_int, [_vp, C.c_int32, C.c_double, _dp]),
     'qmc_vmc_renyi_swap': (C.c_int, [_vp, C.c_int32, _dp, C.c_double, _dp]),
     'qmc_vmc_particle_swap': (C.c_int, [_vp, _dp]),
+    'qmc_vmc_obdm_grid': (C.c_int, [_vp, C.c_int32, C.c_int32, _dp]),
     'qmc_vmc_run_block': (C.c_int, [_vp, C.c_int64, _dp, _dp, _i64p, _dp, _dp,
                                     _u8p, _dp]),
     'qmc_vmc_state_dev': (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),

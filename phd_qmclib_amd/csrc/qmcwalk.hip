@@ -14,6 +14,7 @@
 #include "qmc_tripledist.h"
 #include "qmc_renyi.h"
 #include "qmc_partent.h"
+#include "qmc_obdm_grid.h"
 #include "qmc_cmdiff.h"
 #include "qmc_isf.h"
 #include "qmc_site.h"
@@ -130,6 +131,9 @@ struct qmc_engine {
     // one-particle swap scratch (qmc_particle_swap*): the per-pair tile of
     // means and the sums of qmc_vmc_particle_swap
     DevBuf<double> pe_mean, pe_vmc;
+    // density matrix on a grid (qmc_obdm_grid*): the partial matrices that
+    // obdm_grid_fold_kernel adds up and the sums of qmc_vmc_obdm_grid
+    DevBuf<double> og_part, og_vmc;
 
     qmc_engine() = default;
     qmc_engine(const qmc_engine &) = delete;
@@ -2119,6 +2123,188 @@ extern "C" int qmc_vmc_particle_swap(qmc_vmc *v, double *out)
     if (e->pe_vmc.reserve(3)) return 1;
     int rc = qmc_particle_swap_reduce_dev(e, v->W, v->pos, e->pe_vmc);
     return rc ? rc : read_doubles(e, out, e->pe_vmc, 3);
+}
+
+
+// ---- one-body density matrix on a grid (csrc/qmc_obdm_grid.h) -------------
+// Doubles of partial matrices the engine keeps (128 MB): with the wavefronts
+// wanted below, what bounds the number S of partial matrices of a group.
+static constexpr long long OGRID_SCRATCH_ELEMS = 1ll << 24;
+// Wavefronts a launch aims at: a few to every SIMD of a device of this class
+// (the bound is a constant of the decomposition, so that the summation order
+// is the same on every device).
+static constexpr long long OGRID_WAVES = 4096;
+
+struct ObdmGridPlan {
+    int M, G, S, rows, nrt, nct;
+    double *part;          // the partial matrices: scratch, or sums at S = 1
+};
+
+static int obdm_grid_check(const char *who, const qmc_engine *e, int64_t nconf,
+                           const void *pos, int32_t M, int32_t G,
+                           const void *sums)
+{
+    const std::string w(who);
+    if (!e || !pos || !sums) return fail(w + ": null argument");
+    if (nconf <= 0) return fail(w + ": nconf must be positive");
+    if (M < 1 || M > OGRID_MAX_POINTS)
+        return fail(w + ": num_points must be in [1, 512]");
+    if (G < 1 || G > OGRID_MAX_GROUPS || G > nconf)
+        return fail(w + ": num_groups must be in [1, min(1024, nconf)]");
+    return 0;
+}
+
+// The decomposition of nconf configurations (a function of nconf, M, G and N
+// alone), the scratch it needs, and the partial matrices zeroed on the stream.
+static int obdm_grid_plan(qmc_engine *e, long long nconf, int M, int G,
+                          double *sums_dev, ObdmGridPlan &pl)
+{
+    const int n = e->dm.n;
+    const long long mm = (long long)M * M;
+    pl.M = M; pl.G = G;
+    pl.nct = (M + 63) / 64;
+    // about 32 particles of a configuration to a row tile: the tables and
+    // the denominators, which every wavefront of a configuration computes for
+    // itself (N pair factors to a lane and 64 particles), stay a few percent
+    // of its work (N to a lane and particle)
+    pl.nrt = std::max(1, std::min({ n / 32, M, 32 }));
+    pl.rows = (M + pl.nrt - 1) / pl.nrt;
+    pl.nrt = (M + pl.rows - 1) / pl.rows;
+    const long long per = (long long)G * pl.nct * pl.nrt;
+    long long S = (OGRID_WAVES + per - 1) / per;
+    S = std::min(S, (nconf + G - 1) / G);
+    S = std::min(S, OGRID_SCRATCH_ELEMS / (G * mm));
+    pl.S = (int)std::max(1ll, S);
+    if (pl.S > 1) {
+        if (e->og_part.reserve((size_t)pl.S * G * mm)) return 1;
+        pl.part = e->og_part;
+    } else {
+        pl.part = sums_dev;
+    }
+    HIP_TRY(hipMemsetAsync(pl.part, 0, (size_t)pl.S * G * mm * sizeof(double),
+                           e->stream));
+    return 0;
+}
+
+// the configurations c_base .. c_base + nc of the batch into the partial
+// matrices (tiles of a batch arrive in order)
+static int obdm_grid_launch(qmc_engine *e, const ObdmGridPlan &pl,
+                            long long c_base, long long nc,
+                            const double *pos_dev, const double *w_dev)
+{
+    const size_t lds = obdm_grid_lds_bytes(e->dm.n);
+    allow_lds(obdm_grid_kernel, lds);           // 32 KB at N = 512
+    ObdmGridArgs a{ pos_dev, w_dev, pl.part, c_base, nc, pl.M, pl.G, pl.S,
+                    pl.rows, pl.nrt, pl.nct };
+    const long long blocks = (long long)pl.S * pl.G * pl.nrt * pl.nct;
+    hipLaunchKernelGGL(obdm_grid_kernel, dim3((unsigned)blocks), dim3(64), lds,
+                       e->stream, e->dm_dev, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// partial matrices -> sums, and wsum from the whole batch's weights
+static int obdm_grid_finish(qmc_engine *e, const ObdmGridPlan &pl,
+                            long long nconf, const double *w_dev,
+                            double *sums_dev, double *wsum_dev)
+{
+    const long long mm = (long long)pl.M * pl.M;
+    if (pl.S > 1) {
+        const long long total = (long long)pl.G * mm;
+        hipLaunchKernelGGL(obdm_grid_fold_kernel,
+                           dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                           e->stream, pl.part, pl.G, pl.S, mm, sums_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    if (wsum_dev) {
+        hipLaunchKernelGGL(obdm_grid_wsum_kernel, dim3((unsigned)pl.G),
+                           dim3(256), 0, e->stream, w_dev, nconf, pl.G,
+                           wsum_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int qmc_obdm_grid_dev(qmc_engine *e, int64_t nconf,
+                                 const double *pos, const double *w,
+                                 int32_t num_points, int32_t num_groups,
+                                 double *sums, double *wsum)
+{
+    if (obdm_grid_check("qmc_obdm_grid_dev", e, nconf, pos, num_points,
+                        num_groups, sums))
+        return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    ObdmGridPlan pl;
+    if (obdm_grid_plan(e, nconf, num_points, num_groups, sums, pl) ||
+        obdm_grid_launch(e, pl, 0, nconf, pos, w))
+        return 1;
+    return obdm_grid_finish(e, pl, nconf, w, sums, wsum);
+}
+
+extern "C" int qmc_obdm_grid(qmc_engine *e, int64_t nconf, const double *pos,
+                             const double *w, int32_t num_points,
+                             int32_t num_groups, double *sums, double *wsum)
+{
+    if (obdm_grid_check("qmc_obdm_grid", e, nconf, pos, num_points, num_groups,
+                        sums))
+        return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n = (size_t)e->dm.n;
+    const size_t G = (size_t)num_groups, mm = (size_t)num_points * num_points;
+    const long long tile = std::max<long long>(
+        1, std::min<long long>(nconf, PD_SCRATCH_ELEMS / (long long)n));
+    DevBuf<double> dpos, dw, dsums, dwsum;
+    if (dpos.alloc((size_t)tile * n) || (w && dw.alloc((size_t)nconf)) ||
+        dsums.alloc(G * mm) || (wsum && dwsum.alloc(G)))
+        return 1;
+    if (w)
+        HIP_TRY(hipMemcpyAsync(dw, w, (size_t)nconf * sizeof(double),
+                               hipMemcpyHostToDevice, e->stream));
+    ObdmGridPlan pl;
+    if (obdm_grid_plan(e, nconf, num_points, num_groups, dsums, pl)) return 1;
+    long long c0 = 0;
+    if (run_host_tiles(e, nconf, tile, pos, dpos, {}, [&](long long nc) {
+            const int rc = obdm_grid_launch(e, pl, c0, nc, dpos,
+                                            w ? dw.get() + c0 : nullptr);
+            c0 += nc;
+            return rc;
+        }))
+        return 1;
+    if (obdm_grid_finish(e, pl, nconf, w ? dw.get() : nullptr, dsums,
+                         wsum ? dwsum.get() : nullptr))
+        return 1;
+    // into a host copy first: the outputs are left untouched by a failure
+    std::vector<double> hs(G * mm), hw(wsum ? G : 0);
+    if (read_doubles(e, hs.data(), dsums, G * mm) ||
+        (wsum && read_doubles(e, hw.data(), dwsum, G)))
+        return 1;
+    std::copy(hs.begin(), hs.end(), sums);
+    if (wsum) std::copy(hw.begin(), hw.end(), wsum);
+    return 0;
+}
+
+// The matrix sums of the CURRENT configurations of the chains, group = chain
+// index mod num_groups, on the resident rows (nothing depends on the order of
+// a row: position-sorted after move = 'all', by label after 'particle'); the
+// chain state is only read.
+extern "C" int qmc_vmc_obdm_grid(qmc_vmc *v, int32_t num_points,
+                                 int32_t num_groups, double *sums)
+{
+    if (!v) return fail("qmc_vmc_obdm_grid: null argument");
+    qmc_engine *e = v->eng;
+    if (obdm_grid_check("qmc_vmc_obdm_grid", e, v->W, v->pos, num_points,
+                        num_groups, sums))
+        return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t count = (size_t)num_groups * num_points * num_points;
+    if (e->og_vmc.reserve(count)) return 1;
+    if (qmc_obdm_grid_dev(e, v->W, v->pos, nullptr, num_points, num_groups,
+                          e->og_vmc, nullptr))
+        return 1;
+    std::vector<double> hs(count);
+    if (read_doubles(e, hs.data(), e->og_vmc, count)) return 1;
+    std::copy(hs.begin(), hs.end(), sums);
+    return 0;
 }
 
 

@@ -283,6 +283,147 @@ def momentum_distribution(shifts, g1, momenta, density):
     return 2.0 * float(density) * (g1 @ kern)
 
 
+#: limits of `ModelEngine.one_body_matrix` (qmc_obdm_grid)
+MAX_OBDM_GRID_POINTS = 512
+MAX_OBDM_GRID_GROUPS = 1024
+
+
+def _obdm_grid_args(num_points, num_groups, nconf):
+    """(M, G) of a density-matrix grid as integers, checked against the
+    limits of qmc_obdm_grid: M in [1, 512], G in [1, min(1024, nconf)]."""
+    m, g, nc = int(num_points), int(num_groups), int(nconf)
+    if m != num_points or not 1 <= m <= MAX_OBDM_GRID_POINTS:
+        raise ValueError('num_points must be an integer in [1, %d]'
+                         % MAX_OBDM_GRID_POINTS)
+    if nc < 1:
+        raise ValueError('at least one configuration is needed')
+    if g != num_groups or not 1 <= g <= min(MAX_OBDM_GRID_GROUPS, nc):
+        raise ValueError('num_groups must be an integer in [1, min(%d, '
+                         'number of configurations)]' % MAX_OBDM_GRID_GROUPS)
+    return m, g
+
+
+def one_body_matrix_points(supercell_size, num_points):
+    """Cell centres x_c = (c + 1/2) L / M of the `num_points` = M uniform
+    cells of [0, L): the columns of `ModelEngine.one_body_matrix` (its rows
+    are the cells themselves) -> x[M]."""
+    m = int(num_points)
+    if m != num_points or not 1 <= m <= MAX_OBDM_GRID_POINTS:
+        raise ValueError('num_points must be an integer in [1, %d]'
+                         % MAX_OBDM_GRID_POINTS)
+    return (np.arange(m) + 0.5) * float(supercell_size) / m
+
+
+class NaturalOrbitals(t.NamedTuple):
+    """Result of `natural_orbitals`."""
+    matrix: np.ndarray              # K[M, M], symmetrised
+    occupations: np.ndarray         # lambda_k, descending
+    occupations_err: np.ndarray
+    orbitals: np.ndarray            # [M, M], column k belongs to lambda_k
+    condensate_fraction: float      # lambda_0 / N
+    condensate_fraction_err: float
+    purity: float                   # sum_k lambda_k^2 / N^2
+    purity_err: float
+    trace: float                    # ~ N
+
+
+def _cross_purity(kg, boson_number):
+    """Purity from the group matrices kg[G, M, M]: the mean of <K_g, K_h>_F
+    over the ordered pairs g != h, over N^2; one group: |K|_F^2 / N^2."""
+    g = kg.shape[0]
+    n2 = float(boson_number) ** 2
+    if g == 1:
+        return float(np.sum(kg[0] ** 2)) / n2
+    tot = kg.sum(axis=0)
+    cross = np.sum(tot ** 2) - np.sum(kg ** 2)
+    return float(cross) / (g * (g - 1) * n2)
+
+
+def natural_orbitals(sums, wsum, boson_number, supercell_size=None):
+    """Natural orbitals from the group sums of `ModelEngine.one_body_matrix`,
+    sums[G, M, M] and wsum[G] -> NaturalOrbitals:
+
+    matrix       K = (A + A^T) / 2 with A = sum_g sums / sum_g wsum, the
+                 estimate of int_{bin a} rho1(x, x_c) dx
+    occupations  the eigenvalues of K (`eigvalsh`), descending; they add up to
+                 `trace` ~ N
+    occupations_err  delete-one-group jackknife of every sorted eigenvalue
+                 (zeros for G = 1)
+    orbitals     column k is the eigenvector of occupations[k], normalised to
+                 sum_a |phi_a|^2 delta = 1 on the grid with delta = L / M
+                 (`supercell_size` None: delta = 1)
+    condensate_fraction, condensate_fraction_err  occupations[0] / N
+    purity       Tr rho1^2 (rho1 of trace 1) as the CROSS-GROUP estimate
+                 sum_{g != h} <K_g, K_h>_F / (G (G - 1) N^2), K_g the
+                 symmetrised matrix of group g alone.  The noise of two
+                 different groups is independent, so this is unbiased by the
+                 noise; the plain |K|_F^2 / N^2 is biased upwards by the
+                 variance of every cell.  For G = 1 there is only the plain
+                 |K|_F^2 / N^2, and that is what is returned.
+    purity_err   delete-one-group jackknife (zero for G = 1)
+    trace        Tr K
+
+    The largest eigenvalue of a noisy symmetric matrix is biased UPWARDS at
+    second order in the noise (level repulsion), so condensate_fraction
+    overestimates n0 / N by a term that falls like 1 / (number of
+    configurations); the jackknife error does not contain it.  Extrapolate a
+    DMC mixed estimate as 2 K_DMC - K_VMC on `matrix` before diagonalising."""
+    sums = np.asarray(sums, dtype=np.float64)
+    wsum = np.atleast_1d(np.asarray(wsum, dtype=np.float64))
+    if sums.ndim == 2:
+        sums = sums[None]
+    if (sums.ndim != 3 or sums.shape[1] != sums.shape[2] or
+            wsum.shape != sums.shape[:1]):
+        raise ValueError('sums[G, M, M] and wsum[G] expected')
+    if not np.all(wsum > 0):
+        raise ValueError('every group needs a positive weight sum')
+    n = float(boson_number)
+    if not n > 0:
+        raise ValueError('boson_number must be positive')
+    g, m = sums.shape[0], sums.shape[1]
+    delta = 1.0 if supercell_size is None else float(supercell_size) / m
+
+    def sym(a):
+        return 0.5 * (a + np.swapaxes(a, -1, -2))
+
+    def eig(a):
+        return np.linalg.eigvalsh(a)[::-1]
+
+    tot, wtot = sums.sum(axis=0), wsum.sum()
+    k = sym(tot / wtot)
+    lam, vec = np.linalg.eigh(k)
+    lam, vec = lam[::-1], vec[:, ::-1] / np.sqrt(delta)
+    kg = sym(sums / wsum[:, None, None])
+    purity = _cross_purity(kg, n)
+    lam_err, purity_err = np.zeros(m), 0.0
+    if g > 1:
+        jl = np.array([eig(sym((tot - sums[i]) / (wtot - wsum[i])))
+                       for i in range(g)])
+        jp = np.array([_cross_purity(np.delete(kg, i, axis=0), n)
+                       for i in range(g)])
+        f = (g - 1.0) / g
+        lam_err = np.sqrt(f * np.sum((jl - jl.mean(axis=0)) ** 2, axis=0))
+        purity_err = float(np.sqrt(f * np.sum((jp - jp.mean()) ** 2)))
+    return NaturalOrbitals(k, lam, lam_err, vec, float(lam[0] / n),
+                           float(lam_err[0] / n), purity, purity_err,
+                           float(np.trace(k)))
+
+
+def momentum_from_matrix(matrix, momenta, supercell_size):
+    """Momentum distribution of a grid matrix K[M, M]
+    (`natural_orbitals(...).matrix`): n(k) = (1 / M) v^dagger K v with
+    v_a = exp(-i k x_a) on the cell centres x_a -> n[len(momenta)].  Over the M
+    momenta 2 pi m / L, m = 0 .. M - 1, the values add up to Tr K."""
+    k = np.asarray(matrix, dtype=np.float64)
+    if k.ndim != 2 or k.shape[0] != k.shape[1]:
+        raise ValueError('a square matrix K[M, M] expected')
+    m = k.shape[0]
+    q = np.atleast_1d(np.asarray(momenta, dtype=np.float64))
+    x = one_body_matrix_points(supercell_size, m)
+    v = np.exp(-1j * q[:, None] * x[None, :])                  # [Q, M]
+    return np.real(np.einsum('qa,ab,qb->q', np.conj(v), k, v)) / m
+
+
 def _pos2d(pos, num_particles,
            expected='pos must have shape (W, boson_number)'):
     """pos as a contiguous fp64 [rows, num_particles] array."""
@@ -754,6 +895,45 @@ class ModelEngine:
             self._h, self._num_replicas(nconf), pos_ptr, sums_ptr))
 
 
+    def one_body_matrix(self, pos, num_points, num_groups=1, weights=None):
+        """The one-body density matrix on a grid, summed over the
+        configurations pos[W, N] in `num_groups` = G independent groups
+        (configuration index mod G) -> (sums[G, M, M], wsum[G]), M =
+        `num_points`:
+
+            sums[g, a, c] = sum_{conf in g} w_conf sum_{i in cell a}
+                            psi(.. z_i -> x_c ..) / psi(R)
+
+        with the cells and centres of `one_body_matrix_points` (a particle
+        counts in the cell that holds its image in [0, L)) and unit weights
+        for `weights` None; wsum[g] is the sum of the weights of the group.
+        sum_g sums / sum_g wsum estimates int_{cell a} rho1(x, x_c) dx;
+        `natural_orbitals` diagonalises it.  M in [1, 512], G in
+        [1, min(1024, W)]; the particles of a row may come in any order; two
+        calls give the same bits."""
+        pos = _pos2d(pos, self.num_particles)
+        m, g = _obdm_grid_args(num_points, num_groups, pos.shape[0])
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            if w.shape != (pos.shape[0],):
+                raise ValueError('weights must have one entry per '
+                                 'configuration')
+        sums, wsum = np.zeros((g, m, m)), np.zeros(g)
+        check(self._lib.qmc_obdm_grid(self._h, pos.shape[0], ptr(pos), ptr(w),
+                                      m, g, ptr(sums), ptr(wsum)))
+        return sums, wsum
+
+    def one_body_matrix_dev(self, nconf, pos_ptr, w_ptr, num_points,
+                            num_groups, sums_ptr, wsum_ptr=0):
+        """Asynchronous `one_body_matrix` on device-resident buffers (raw
+        pointers): pos[nconf, N], w[nconf] (0: unit weights) ->
+        sums[G, M, M] and wsum[G] (0: not wanted)."""
+        check(self._lib.qmc_obdm_grid_dev(self._h, int(nconf), pos_ptr, w_ptr,
+                                          int(num_points), int(num_groups),
+                                          sums_ptr, wsum_ptr))
+
+
 #: VmcEnsemble(move=...) -> qmc_vmc_params.gaussian (the proposal code;
 #: 1 is the Gaussian all-particle proposal, `gaussian=True`)
 VMC_MOVES = {'all': 0, 'particle': 2}
@@ -873,6 +1053,16 @@ class VmcEnsemble:
         ModelEngine._num_replicas(self.num_chains)
         out = np.zeros(3)
         check(self._lib.qmc_vmc_particle_swap(self._h, ptr(out)))
+        return out
+
+    def obdm_grid_parts(self, num_points, num_groups) -> np.ndarray:
+        """Density-matrix sums on a grid of the current configurations, group
+        = chain index mod `num_groups`, unit weights -> sums[G, M, M]
+        (`ModelEngine.one_body_matrix`; every group's weight sum is its number
+        of chains); computed on the resident rows, which are only read."""
+        m, g = _obdm_grid_args(num_points, num_groups, self.num_chains)
+        out = np.zeros((g, m, m))
+        check(self._lib.qmc_vmc_obdm_grid(self._h, m, g, ptr(out)))
         return out
 
     def get_state(self):

@@ -27,6 +27,7 @@ import numpy as np
 
 from .. import utils
 from ..engine import (DmcEnsemble, ModelEngine, dmc_propagator_code,
+                      natural_orbitals, one_body_matrix_points,
                       pair_distribution_bins, pair_distribution_norm,
                       triple_distribution_bins, triple_distribution_norm)
 from ..qmc_base import dmc as dmc_base, dmc_est
@@ -553,6 +554,28 @@ class Sampling:
                 triple_distribution_norm(hist, spec.boson_number,
                                          spec.supercell_size, max_span))
 
+    def one_body_matrix(self, state: State, num_points, num_groups=32):
+        """Mixed estimate of the one-body density matrix rho1(x, x') on a grid
+        of `num_points` = M uniform cells over the live walkers of a State
+        with their weights -> (x[M], `engine.NaturalOrbitals`): the cell
+        centres and K[a, c] = sum_w W_w R_w[a, c] / sum_w W_w with its
+        natural-orbital occupations, condensate fraction, purity and their
+        jackknife errors over `num_groups` groups of walkers (walker index mod
+        `num_groups`; at most `num_walkers`).  Slots beyond `num_walkers` do
+        not count.  The positions are uploaded once; the weighted sums run on
+        the device.  A mixed estimate: extrapolate as 2 K_DMC - K_VMC on
+        `matrix`, with `vmc.EnsembleSampling.one_body_matrix`, BEFORE
+        diagonalising (the eigenvalues are not linear in the matrix)."""
+        nw = int(state.num_walkers)
+        confs = np.asarray(state.confs, dtype=np.float64)
+        pos = confs[:nw, model.SysConfSlot.pos, :]
+        weight = np.asarray(state.props.weight, dtype=np.float64)[:nw]
+        eng = model.core_funcs._engine(*self.model_spec.cfc_spec)
+        spec = self.model_spec
+        sums, wsum = eng.one_body_matrix(pos, num_points, num_groups, weight)
+        return (one_body_matrix_points(spec.supercell_size, num_points),
+                natural_orbitals(sums, wsum, spec.boson_number,
+                                 spec.supercell_size))
 
     @property
     def ssf_momenta(self):

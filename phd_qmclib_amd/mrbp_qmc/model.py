@@ -374,6 +374,7 @@ class PhysicalFuncs:
         triple_distribution(num_bins, sys_conf)  (ns,nop)->(B)
         renyi_swap(lengths, sys_conf)     (2,ns,nop)->(K)
         particle_swap(sys_conf)           (2,ns,nop)->()
+        one_body_matrix(num_points, sys_conf)  (ns,nop)->(M,M)
         fourier_density(kz_set, sys_conf) (nkz),(ns,nop)->(nkz)   complex
 
     The loop dimensions broadcast as NumPy's; the whole broadcast batch goes to
@@ -504,6 +505,26 @@ class PhysicalFuncs:
         loop, pos = self._conf_batch(sys_conf)
         mean = self._engine().particle_swap(pos)
         return mean.reshape(loop[:-1])[()]
+
+    def one_body_matrix(self, num_points, sys_conf):
+        """The one-body density matrix of every configuration on the grid of
+        `num_points` = M uniform cells of [0, L): element [a, c] is the sum
+        over the particles in cell a of psi(.. z_i -> x_c ..) / psi(R), x_c
+        the centre of cell c (`engine.one_body_matrix_points`).  Its average
+        over |psi|^2 is int_{cell a} rho1(x, x_c) dx, whose eigenvalues are the
+        occupations of the natural orbitals (`engine.natural_orbitals`).
+        `num_points` is a scalar; the loop dimensions of sys_conf broadcast.
+        Every configuration is a group of its own here (1024 of them to a
+        call of the engine); `ModelEngine.one_body_matrix` sums a batch on the
+        device."""
+        from ..engine import MAX_OBDM_GRID_GROUPS as step
+        loop, pos = self._conf_batch(sys_conf)
+        eng = self._engine()
+        sums = np.concatenate([
+            eng.one_body_matrix(pos[c0:c0 + step], num_points,
+                                num_groups=len(pos[c0:c0 + step]))[0]
+            for c0 in range(0, max(len(pos), 1), step)])
+        return sums.reshape(loop + sums.shape[-2:])
 
     def fourier_density(self, kz_set, sys_conf):
         """Fourier density component with momentum k: sum_i exp(i k z_i)."""

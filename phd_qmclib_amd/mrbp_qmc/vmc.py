@@ -17,7 +17,8 @@ import attr
 import numpy as np
 
 from .. import utils
-from ..engine import (ModelEngine, VmcEnsemble, pair_distribution_bins,
+from ..engine import (ModelEngine, VmcEnsemble, natural_orbitals,
+                      one_body_matrix_points, pair_distribution_bins,
                       pair_distribution_norm, particle_entropy, renyi_entropy,
                       renyi_lengths,
                       triple_distribution_bins, triple_distribution_norm)
@@ -389,6 +390,27 @@ class EnsembleSampling:
         state."""
         parts = self.ensemble.particle_swap_parts()
         return particle_entropy(parts, self.num_chains // 2)
+
+    def one_body_matrix(self, num_points, num_groups=32):
+        """The one-body density matrix rho1(x, x') on a grid of `num_points`
+        = M uniform cells over the chains' current configurations ->
+        (x[M], `engine.NaturalOrbitals`): the cell centres and the matrix
+        K[a, c] ~ int_{cell a} rho1(x, x_c) dx with its natural-orbital
+        occupations, the condensate fraction lambda_0 / N, the purity and
+        their jackknife errors over `num_groups` groups of chains (chain index
+        mod `num_groups`; at most `num_chains`).  Computed on the rows resident
+        on the device after either move type; the chains are not touched.  The
+        chains sample the trial wave function, so this is the variational
+        matrix of the Bijl-Jastrow state; `engine.momentum_from_matrix` gives
+        n(k) of it."""
+        spec = self.model_spec
+        sums = self.ensemble.obdm_grid_parts(num_points, num_groups)
+        g = sums.shape[0]
+        wsum = np.array([len(range(i, self.num_chains, g)) for i in range(g)],
+                        dtype=np.float64)
+        return (one_body_matrix_points(spec.supercell_size, num_points),
+                natural_orbitals(sums, wsum, spec.boson_number,
+                                 spec.supercell_size))
 
     def close(self):
         self.ensemble.close()
