@@ -351,6 +351,51 @@ int qmc_triple_dist_reduce_dev(qmc_engine *eng, int64_t nconf,
                                int32_t num_bins, double max_span,
                                double *sums_dev, double *wsum_dev);
 
+/* Energy components and Tan's contact.  The local energy of
+ * qmc_base/jastrow/model.py:681-743 leaves the contact term g sum_{i<j}
+ * delta(z_ij) of the Hamiltonian out: the cusp of the two-body factor accounts
+ * for it.  Per configuration a row of 4 + nrange doubles:
+ *   [0] E  the local energy, as qmc_evaluate returns it
+ *   [1] T  = sum_i F_i^2, F the drift as qmc_evaluate returns it; its mean
+ *          over |psi|^2 is the kinetic energy
+ *   [2] V  = sum_i V(z_i), the lattice potential of mrbp_qmc/model.py:533-551
+ *          exactly as the local energy contains it: a barrier where
+ *          z_a < z - floor(z) on the position as given, of height
+ *          defect_magnitude where floor(z) % defects_sep == 0 and
+ *          lattice_depth elsewhere; 0 for is_free
+ *   [3] I  = (E - T) - V; its mean is the interaction energy
+ *          g <sum_{i<j} delta(z_ij)>, g = 4 k2 tan(k2 r_off)
+ *   [4 + k] C_k = 1 / (2 r_k) sum_{i<j, d_ij < r_k}
+ *          [cos(k2 r_off) / cos(k2 (d_ij - r_off))]^2, the windowed contact at
+ *          range r_k = ranges[k]: d_ij the minimum-image distance, the compare
+ *          strict, the weight f2(0)^2 / f2(d)^2 (1 on an ideal model).  g C_k
+ *          estimates the interaction energy with a bias of order r_k^2.
+ * 0 <= nrange <= 16; every range finite, in (0, L/2] and, unless the model is
+ * ideal, at most |tbf_contact_cutoff| (the cosine form holds only there).
+ * `ranges` is a HOST array in all four calls.  Any real position is accepted,
+ * as by qmc_evaluate; pairs use the image inside the box.  N = 1: C_k = 0.
+ * Always fp64: qmc_engine_set_fast_math does not apply
+ * (csrc/qmc_energy_parts.h).
+ * qmc_energy_parts: host buffers, synchronous, parts[nconf][4 + nrange]; a
+ * NULL pos / parts (or ranges with nrange > 0) or a range outside the limits
+ * is an error. */
+int qmc_energy_parts(qmc_engine *eng, int64_t nconf, const double *pos,
+                     int32_t nrange, const double *ranges, double *parts);
+/* Same on device-resident pos / parts, asynchronous on the engine's stream. */
+int qmc_energy_parts_dev(qmc_engine *eng, int64_t nconf, const double *pos_dev,
+                         int32_t nrange, const double *ranges,
+                         double *parts_dev);
+/* Weighted sums over the configurations, device buffers, asynchronous:
+ * sums_dev[4 + nrange][2] = sum_c w_c x_c, sum_c w_c x_c^2 of every column x
+ * and (unless NULL) wsum_dev[0] = sum_c w_c; w_dev = NULL means unit weights.
+ * Fixed summation order, as qmc_pair_dist_reduce_dev; the per-configuration
+ * rows live in an engine-owned scratch filled in tiles of at most 2^16
+ * configurations. */
+int qmc_energy_parts_reduce_dev(qmc_engine *eng, int64_t nconf,
+                                const double *pos_dev, const double *w_dev,
+                                int32_t nrange, const double *ranges,
+                                double *sums_dev, double *wsum_dev);
+
 /* Renyi-2 entanglement entropy of a segment by replica swap (no counterpart
  * in the reference).  The configurations 2p and 2p + 1 of pos[nconf][N]
  * (nconf even) are the replicas R1, R2 of pair p; nlen segments
@@ -529,6 +574,13 @@ int qmc_vmc_pair_dist(qmc_vmc *v, int32_t num_bins, double *out);
  * synchronous; num_bins and max_span checked as by qmc_triple_dist. */
 int qmc_vmc_triple_dist(qmc_vmc *v, int32_t num_bins, double max_span,
                         double *out);
+/* Energy parts of the CURRENT configurations summed over the chains:
+ * out[4 + nrange][2] = sum_w x_w, sum_w x_w^2 of every column x of
+ * qmc_energy_parts, on the resident rows, after either move type; no position
+ * leaves the device and the chain state is not touched.  Host buffers;
+ * synchronous; nrange and ranges checked as by qmc_energy_parts. */
+int qmc_vmc_energy_parts(qmc_vmc *v, int32_t nrange, const double *ranges,
+                         double *out);
 /* Replica-swap sums of the CURRENT configurations, the chains 2p and 2p + 1
  * being the replicas of pair p: out[nlen][3] as sums_dev of
  * qmc_renyi_swap_reduce_dev, on the resident rows, after either move type; no

@@ -126,6 +126,11 @@ SIGNATURES = {
                                 C.c_int32, _dp, _dp]),
     'qmc_obdm_grid_dev': (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int32,
                                     C.c_int32, _vp, _vp]),
+    'qmc_energy_parts': (C.c_int, [_vp, C.c_int64, _dp, C.c_int32, _dp, _dp]),
+    'qmc_energy_parts_dev': (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, _dp,
+                                       _vp]),
+    'qmc_energy_parts_reduce_dev': (C.c_int, [_vp, C.c_int64, _vp, _vp,
+                                              C.c_int32, _dp, _vp, _vp]),
     'qmc_buffer_alloc': (C.c_int, [C.c_int, C.c_size_t, C.POINTER(_vp)]),
     'qmc_buffer_free': (C.c_int, [_vp]),
     'qmc_buffer_upload': (C.c_int, [_vp, _vp, C.c_size_t]),
@@ -138,6 +143,7 @@ SIGNATURES = {
     'qmc_vmc_obdm': (C.c_int, [_vp, C.c_int32, _dp, _dp]),
     'qmc_vmc_pair_dist': (C.c_int, [_vp, C.c_int32, _dp]),
     'qmc_vmc_triple_dist': (C.c_int, [_vp, C.c_int32, C.c_double, _dp]),
+    'qmc_vmc_energy_parts': (C.c_int, [_vp, C.c_int32, _dp, _dp]),
     'qmc_vmc_renyi_swap': (C.c_int, [_vp, C.c_int32, _dp, C.c_double, _dp]),
     'qmc_vmc_particle_swap': (C.c_int, [_vp, _dp]),
     'qmc_vmc_obdm_grid': (C.c_int, [_vp, C.c_int32, C.c_int32, _dp]),

@@ -12,6 +12,7 @@
 #include "qmc_obdm.h"
 #include "qmc_pairdist.h"
 #include "qmc_tripledist.h"
+#include "qmc_energy_parts.h"
 #include "qmc_renyi.h"
 #include "qmc_partent.h"
 #include "qmc_obdm_grid.h"
@@ -124,6 +125,9 @@ struct qmc_engine {
     DevBuf<double> pd_hist, pd_sums;
     // three-body distribution scratch (qmc_triple_dist*), as the pair one
     DevBuf<double> td_hist, td_sums;
+    // energy parts scratch (qmc_energy_parts*): the per-configuration tile of
+    // rows and the sums of qmc_vmc_energy_parts
+    DevBuf<double> ep_rows, ep_sums;
     // replica-swap scratch (qmc_renyi_swap*): the per-pair tile of rows
     // (swap, matched), their column sums, and the lengths and sums of
     // qmc_vmc_renyi_swap
@@ -201,6 +205,8 @@ QMC_FOR_ALL_TUS(QMC_EXTERN_TU)
 #undef QMC_EXTERN_TU
 // (the single-particle sweeps, qmc_vmc_sweep.h: inst_SWEEP.hip)
 QMC_TU_SWEEP(extern)
+// (the energy parts, qmc_energy_parts.h: inst_EPARTS.hip)
+QMC_TU_EPARTS(extern)
 
 // ------------------------------------------------------------ dispatch ----
 // The masked variant is also the leaner one in registers (its per-pair guards
@@ -1852,6 +1858,142 @@ extern "C" int qmc_vmc_triple_dist(qmc_vmc *v, int32_t num_bins,
     return rc ? rc : read_doubles(e, out, e->td_sums, 2 * K);
 }
 
+
+// ---- energy parts and the windowed contact (csrc/qmc_energy_parts.h) -----
+// The windows are a host array in every entry point: they travel in the
+// kernel's argument block.  Tiles as for g2 (PD_TILE, PD_SCRATCH_ELEMS), on
+// rows of EP_COLS + nrange.
+static int energy_parts_args(const char *who, const qmc_engine *e,
+                             int64_t nconf, int32_t nrange,
+                             const double *ranges, EnergyPartsArgs &a)
+{
+    if (nrange < 0 || nrange > EP_MAX_RANGES)
+        return fail(std::string(who) + ": nrange outside [0, " +
+                    std::to_string(EP_MAX_RANGES) + "]");
+    if (nrange > 0 && !ranges)
+        return fail(std::string(who) + ": null argument");
+    if (nconf < 0) return fail(std::string(who) + ": nconf < 0");
+    memset(&a, 0, sizeof(a));
+    a.K = nrange;
+    for (int k = 0; k < nrange; ++k) {
+        const double r = ranges[k];
+        if (!std::isfinite(r) || !(r > 0.0) || !(r <= 0.5 * e->dm.L))
+            return fail(std::string(who) + ": range outside (0, L/2]");
+        // (the cosine form of the pair factor holds inside the cutoff only)
+        if (!e->dm.is_ideal && !(r <= e->dm.rm))
+            return fail(std::string(who) +
+                        ": range beyond |tbf_contact_cutoff|");
+        a.r[k] = r;
+        a.rmax = std::max(a.rmax, r);
+    }
+    return 0;
+}
+
+template <int G, int P, bool PAD, bool ZC>
+struct LaunchEnergyParts {
+    static int run(const qmc_engine *e, const EnergyPartsArgs &a)
+    {
+        return launch_walkers<G>(e, energy_parts_kernel<G, P, PAD, ZC>,
+                                 lds_bytes<G, P, ZC>(), a.nconf, a);
+    }
+};
+
+// rows of nconf device-resident configurations -> parts[nconf][EP_COLS + K],
+// at most 2^24 configurations to a launch (a multiple of the runs of
+// walker_of_block)
+static int energy_parts_launch(const qmc_engine *e, EnergyPartsArgs a,
+                               long long nconf, const double *pos_dev,
+                               double *parts_dev)
+{
+    const size_t n = (size_t)e->dm.n, cols = (size_t)(EP_COLS + a.K);
+    const long long chunk = 1ll << 24;
+    for (long long c0 = 0; c0 < nconf; c0 += chunk) {
+        a.pos = pos_dev + (size_t)c0 * n;
+        a.parts = parts_dev + (size_t)c0 * cols;
+        a.nconf = std::min(chunk, nconf - c0);
+        if (dispatch_shape<LaunchEnergyParts>(e, a)) return 1;
+    }
+    return 0;
+}
+
+extern "C" int qmc_energy_parts_dev(qmc_engine *e, int64_t nconf,
+                                    const double *pos, int32_t nrange,
+                                    const double *ranges, double *parts)
+{
+    if (!e || !pos || !parts)
+        return fail("qmc_energy_parts_dev: null argument");
+    EnergyPartsArgs a;
+    if (energy_parts_args("qmc_energy_parts_dev", e, nconf, nrange, ranges, a))
+        return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    return energy_parts_launch(e, a, nconf, pos, parts);
+}
+
+extern "C" int qmc_energy_parts_reduce_dev(qmc_engine *e, int64_t nconf,
+                                           const double *pos, const double *w,
+                                           int32_t nrange, const double *ranges,
+                                           double *sums, double *wsum)
+{
+    if (!e || !pos || !sums)
+        return fail("qmc_energy_parts_reduce_dev: null argument");
+    EnergyPartsArgs a;
+    if (energy_parts_args("qmc_energy_parts_reduce_dev", e, nconf, nrange,
+                          ranges, a))
+        return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n = (size_t)e->dm.n;
+    const int cols = EP_COLS + nrange;
+    const long long tile = std::min<long long>(
+        std::max<long long>(nconf, 1),
+        std::min(PD_TILE, PD_SCRATCH_ELEMS / cols));
+    if (e->ep_rows.reserve((size_t)tile * cols)) return 1;
+    return reduce_tiles(e, nconf, tile, e->ep_rows, w, cols, sums, wsum,
+                        [&](long long c0, long long nc) {
+        return energy_parts_launch(e, a, nc, pos + (size_t)c0 * n,
+                                   e->ep_rows.get());
+    });
+}
+
+extern "C" int qmc_energy_parts(qmc_engine *e, int64_t nconf, const double *pos,
+                                int32_t nrange, const double *ranges,
+                                double *parts)
+{
+    if (!e || !pos || !parts) return fail("qmc_energy_parts: null argument");
+    EnergyPartsArgs a;
+    if (energy_parts_args("qmc_energy_parts", e, nconf, nrange, ranges, a))
+        return 1;
+    if (nconf == 0) return 0;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n = (size_t)e->dm.n, cols = (size_t)(EP_COLS + nrange);
+    const long long tile = std::max<long long>(
+        1, std::min<long long>(nconf,
+                               PD_SCRATCH_ELEMS / (long long)std::max(n, cols)));
+    DevBuf<double> dpos, drows;
+    if (dpos.alloc((size_t)tile * n) || drows.alloc((size_t)tile * cols))
+        return 1;
+    return run_host_tiles(e, nconf, tile, pos, dpos,
+                          { { parts, drows.get(), cols * sizeof(double) } },
+                          [&](long long nc) {
+        return energy_parts_launch(e, a, nc, dpos, drows.get());
+    });
+}
+
+// Sums of the rows of the CURRENT configurations of the chains, on the
+// resident rows (every column is a sum over particles or over pairs, so
+// neither the position order of the 'all' rows nor the label order of the
+// 'particle' rows matters); the chain state is only read.
+extern "C" int qmc_vmc_energy_parts(qmc_vmc *v, int32_t nrange,
+                                    const double *ranges, double *out)
+{
+    if (!v || !out) return fail("qmc_vmc_energy_parts: null argument");
+    qmc_engine *e = v->eng;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t cols = (size_t)EP_COLS + (size_t)std::max(nrange, 0);
+    if (e->ep_sums.reserve(2 * cols)) return 1;
+    int rc = qmc_energy_parts_reduce_dev(e, v->W, v->pos, nullptr, nrange,
+                                         ranges, e->ep_sums, nullptr);
+    return rc ? rc : read_doubles(e, out, e->ep_sums, 2 * cols);
+}
 
 // ---- Renyi-2 replica swap (csrc/qmc_renyi.h) -----------------------------
 // Tiles as for g2 (PD_TILE, PD_SCRATCH_ELEMS), on rows of 2 nlen per pair.

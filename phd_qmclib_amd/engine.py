@@ -14,7 +14,8 @@ from ._lib import (DmcEstParams, DmcParams, ModelParams, QmcError, VmcParams,
 
 __all__ = ['ModelEngine', 'VmcEnsemble', 'DmcEnsemble', 'EvalResult',
            'vmc_move_code', 'DeviceBuffer', 'momentum_distribution',
-           'site_statistics',
+           'site_statistics', 'EnergyComponents', 'energy_components',
+           'contact_extrapolate', 'contact_coupling', 'contact_ranges_array',
            'model_params_struct', 'QmcError']
 
 
@@ -182,6 +183,115 @@ def particle_entropy(sums, num_pairs):
     with np.errstate(divide='ignore', invalid='ignore'):
         return (float(-np.log(mean)), float(stderr / mean), float(mean),
                 float(stderr))
+
+
+MAX_CONTACT_RANGES = 16        # EP_MAX_RANGES of csrc/qmc_energy_parts.h
+ENERGY_PARTS_COLS = 4          # E, T, V, I in front of the windows
+
+
+def contact_ranges_array(cfc_spec, contact_ranges):
+    """The windows of the contact estimator as a contiguous fp64 array, checked
+    against the limits of qmc_energy_parts: at most 16 of them (None or () is
+    none), each finite and in (0, L/2], and on a model with interactions at
+    most |tbf_contact_cutoff| -- the cosine form of the two-body factor, whose
+    cusp the estimator divides out, holds only there."""
+    rg = np.ascontiguousarray(() if contact_ranges is None else contact_ranges,
+                              dtype=np.float64)
+    if rg.ndim != 1 or rg.size > MAX_CONTACT_RANGES:
+        raise ValueError('contact_ranges must be a 1-d sequence of at most %d '
+                         'windows' % MAX_CONTACT_RANGES)
+    mp = cfc_spec.model_params
+    if not np.all(np.isfinite(rg)) or not np.all(rg > 0.0):
+        raise ValueError('contact_ranges must be finite and positive')
+    if np.any(rg > 0.5 * float(mp.supercell_size)):
+        raise ValueError('contact_ranges must be in (0, supercell_size / 2]')
+    if not mp.is_ideal and np.any(rg > abs(float(mp.tbf_contact_cutoff))):
+        raise ValueError('contact_ranges must not exceed |tbf_contact_cutoff| '
+                         'on a model with interactions')
+    return rg
+
+
+def contact_coupling(cfc_spec):
+    """g = 4 kappa, kappa = f2'(0+) / f2(0) = k2 tan(k2 r_off): the strength of
+    the contact term the cusp of the two-body factor stands for, computed from
+    the two-body parameters (0 on an ideal model).  `Spec.tbf_params` sets
+    k2 r_off = atan(1 / (k2 a1d)), which makes it interaction_strength L / N:
+    interaction_strength itself at one boson per lattice period."""
+    tb = cfc_spec.tbf_params
+    k2 = float(tb.param_k2)
+    if cfc_spec.model_params.is_ideal or k2 == 0.0:
+        return 0.0
+    return 4.0 * k2 * float(np.tan(k2 * float(tb.param_r_off)))
+
+
+class EnergyComponents(t.NamedTuple):
+    """Result of `energy_components`: means over the configurations and the
+    standard errors of those means."""
+    total: float                    # <E_L>
+    total_err: float
+    kinetic: float                  # <sum_i F_i^2>
+    kinetic_err: float
+    lattice: float                  # <sum_i V(z_i)>
+    lattice_err: float
+    interaction: float              # <E_L - T - V>, the remainder
+    interaction_err: float
+    contact: np.ndarray             # [K] <sum_{i<j} delta(z_ij)> per window
+    contact_err: np.ndarray
+    contact_ranges: np.ndarray      # [K]
+    coupling: float                 # g = 4 kappa: g * contact ~ interaction
+
+
+def energy_components(sums, wsum, cfc_spec, contact_ranges=None,
+                      num_confs=None):
+    """EnergyComponents from the sums of `ModelEngine.energy_parts_weighted`
+    (or `VmcEnsemble.energy_parts_parts` with wsum = number of chains):
+    sums[4 + K, 2] = sum_c w_c x_c, sum_c w_c x_c^2 over the columns
+    E, T, V, I, C_0 .. C_{K-1} and wsum = sum_c w_c.  Every mean is
+    sum w x / sum w.  The errors are those of the mean over the configurations,
+    sqrt(var / (n - 1)) with the weighted variance and n = `num_confs`
+    configurations (None: unit weights, n = wsum); with unequal weights that
+    is exact only as far as the weights are alike, and configurations of one
+    run are correlated in time: treat it as a lower bound there."""
+    rg = contact_ranges_array(cfc_spec, contact_ranges)
+    sums = np.asarray(sums, dtype=np.float64)
+    if sums.shape != (ENERGY_PARTS_COLS + rg.size, 2):
+        raise ValueError('sums[4 + len(contact_ranges), 2] expected')
+    wsum = float(wsum)
+    if not wsum > 0.0:
+        raise ValueError('a positive weight sum is needed')
+    n = wsum if num_confs is None else float(num_confs)
+    mean = sums[:, 0] / wsum
+    var = np.maximum(sums[:, 1] / wsum - mean ** 2, 0.0)
+    err = np.sqrt(var / max(n - 1.0, 1.0))
+    c = ENERGY_PARTS_COLS
+    return EnergyComponents(
+        float(mean[0]), float(err[0]), float(mean[1]), float(err[1]),
+        float(mean[2]), float(err[2]), float(mean[3]), float(err[3]),
+        mean[c:].copy(), err[c:].copy(), rg.copy(), contact_coupling(cfc_spec))
+
+
+def contact_extrapolate(ranges, values, errors):
+    """The windowed contact at zero range: a weighted least-squares fit
+    C(r) = C_0 + b r^2 to `values` with `errors` at the windows `ranges`
+    (at least two different ones) -> (C_0, its error).  The bias of a window
+    is of order r^2.  The windows share pairs -- every pair inside a window is
+    inside all the larger ones -- so their values are positively correlated;
+    the fit treats them as independent, which is an approximation: the
+    returned error is indicative, not a confidence interval."""
+    r = np.asarray(ranges, dtype=np.float64)
+    y = np.asarray(values, dtype=np.float64)
+    sig = np.asarray(errors, dtype=np.float64)
+    if r.ndim != 1 or r.shape != y.shape or r.shape != sig.shape:
+        raise ValueError('ranges, values and errors must be 1-d and alike')
+    if np.unique(r).size < 2:
+        raise ValueError('at least two different windows are needed')
+    if not np.all(np.isfinite(sig)) or not np.all(sig > 0.0):
+        raise ValueError('errors must be finite and positive')
+    x = np.stack([np.ones_like(r), r ** 2], axis=1)            # [K, 2]
+    wgt = 1.0 / sig ** 2
+    cov = np.linalg.inv(x.T @ (wgt[:, None] * x))
+    coef = cov @ (x.T @ (wgt * y))
+    return float(coef[0]), float(np.sqrt(cov[0, 0]))
 
 
 def superfluid_ratio(iter_cm, num_walkers, boson_number, time_step):
@@ -812,6 +922,71 @@ class ModelEngine:
             self.triple_distribution_reduce_dev(nconf, pos_ptr, w_ptr, nb,
                                                 span, sums_ptr, wsum_ptr))
 
+    def _ranges(self, contact_ranges):
+        rg = contact_ranges_array(self.cfc_spec, contact_ranges)
+        return rg, (ptr(rg) if rg.size else None)
+
+    def energy_parts(self, pos, contact_ranges=()):
+        """The local energy of every configuration in pos[W, N] in parts
+        -> parts[W, 4 + K]: E (as `evaluate`), T = sum_i F_i^2 (F the drift),
+        V = sum_i V(z_i) (the lattice potential the energy contains),
+        I = (E - T) - V, and the windowed contact C_k of every window in
+        `contact_ranges` (K <= 16, `contact_ranges_array`):
+        1 / (2 r_k) sum_{i<j, d_ij < r_k} f2(0)^2 / f2(d_ij)^2.  Over |psi|^2,
+        <T> is the kinetic energy and <I> = g <C_k> + O(r_k^2) the interaction
+        energy, g = `contact_coupling`.  Always fp64."""
+        pos = _pos2d(pos, self.num_particles)
+        rg, rg_ptr = self._ranges(contact_ranges)
+        parts = np.zeros((pos.shape[0], ENERGY_PARTS_COLS + rg.size))
+        check(self._lib.qmc_energy_parts(self._h, pos.shape[0], ptr(pos),
+                                         rg.size, rg_ptr, ptr(parts)))
+        return parts
+
+    def energy_parts_dev(self, nconf, pos_ptr, contact_ranges, parts_ptr):
+        """Asynchronous rows on device-resident buffers (raw pointers):
+        pos[nconf, N] -> parts[nconf, 4 + K]; `contact_ranges` is a host
+        sequence."""
+        rg, rg_ptr = self._ranges(contact_ranges)
+        check(self._lib.qmc_energy_parts_dev(self._h, int(nconf), pos_ptr,
+                                             rg.size, rg_ptr, parts_ptr))
+
+    def energy_parts_reduce_dev(self, nconf, pos_ptr, w_ptr, contact_ranges,
+                                sums_ptr, wsum_ptr=0):
+        """Asynchronous weighted sums over the configurations, device buffers:
+        sums[4 + K, 2] = sum_c w_c x_c, sum_c w_c x_c^2 of every column and
+        wsum[0] = sum_c w_c (w_ptr = 0: unit weights), in a fixed summation
+        order; `contact_ranges` is a host sequence."""
+        rg, rg_ptr = self._ranges(contact_ranges)
+        check(self._lib.qmc_energy_parts_reduce_dev(
+            self._h, int(nconf), pos_ptr, w_ptr, rg.size, rg_ptr, sums_ptr,
+            wsum_ptr))
+
+    def energy_parts_weighted(self, pos, weights, contact_ranges=()):
+        """Weighted sums of the rows of `energy_parts` over the configurations
+        pos[W, N] with weights[W] (one upload of the positions, the reduction
+        on the device) -> (sums[4 + K, 2], wsum): what `energy_components`
+        takes."""
+        expected = 'pos[W, boson_number] and weights[W] expected'
+        pos = _pos2d(pos, self.num_particles, expected)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (pos.shape[0],):
+            raise ValueError(expected)
+        rg, _ = self._ranges(contact_ranges)
+        bufs = [DeviceBuffer(pos.shape, self.device).upload(pos),
+                DeviceBuffer(w.shape, self.device).upload(w),
+                DeviceBuffer((ENERGY_PARTS_COLS + rg.size, 2), self.device),
+                DeviceBuffer((1,), self.device)]
+        try:
+            self.energy_parts_reduce_dev(pos.shape[0], bufs[0].ptr,
+                                         bufs[1].ptr, rg, bufs[2].ptr,
+                                         bufs[3].ptr)
+            self.sync()
+            sums, wsum = bufs[2].download(), bufs[3].download()
+        finally:
+            for b in bufs:
+                b.close()
+        return sums, float(wsum[0])
+
     def _lengths(self, lengths):
         return renyi_lengths(self.cfc_spec.model_params.supercell_size,
                              lengths)
@@ -1063,6 +1238,16 @@ class VmcEnsemble:
         m, g = _obdm_grid_args(num_points, num_groups, self.num_chains)
         out = np.zeros((g, m, m))
         check(self._lib.qmc_vmc_obdm_grid(self._h, m, g, ptr(out)))
+        return out
+
+    def energy_parts_parts(self, contact_ranges=()) -> np.ndarray:
+        """Sums over the chains of every column of `ModelEngine.energy_parts`
+        and of its square for the current configurations -> [4 + K, 2];
+        computed on the resident rows, which are only read."""
+        rg, rg_ptr = self.engine._ranges(contact_ranges)
+        out = np.zeros((ENERGY_PARTS_COLS + rg.size, 2))
+        check(self._lib.qmc_vmc_energy_parts(self._h, rg.size, rg_ptr,
+                                             ptr(out)))
         return out
 
     def get_state(self):

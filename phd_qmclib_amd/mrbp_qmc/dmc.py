@@ -27,6 +27,7 @@ import numpy as np
 
 from .. import utils
 from ..engine import (DmcEnsemble, ModelEngine, dmc_propagator_code,
+                      energy_components,
                       natural_orbitals, one_body_matrix_points,
                       pair_distribution_bins, pair_distribution_norm,
                       triple_distribution_bins, triple_distribution_norm)
@@ -532,6 +533,39 @@ class Sampling:
         return (pair_distribution_bins(spec.supercell_size, num_bins),
                 pair_distribution_norm(hist, spec.boson_number,
                                        spec.supercell_size))
+
+    def energy_components(self, state: State, contact_ranges=None):
+        """Mixed estimate of the energy in parts over the live walkers of a
+        State -> `engine.EnergyComponents`: every entry is
+        sum_w W_w x_w / sum_w W_w with the weights `state.props.weight`; slots
+        at or beyond `num_walkers` do not count.  The positions are uploaded
+        once; the weighted reduction runs on the device.  `contact_ranges`
+        None: no contact window.
+
+        What is exact and what is not:
+          total        the DMC energy: the mixed estimate of H is exact for the
+                       ground state.
+          lattice      a mixed estimate of a local operator, biased at first
+                       order in the error of the trial function.  The pure
+                       value is already available from the pure density
+                       histogram: sum over bins of n(x) V(x), with bins aligned
+                       to the barrier edges.
+          kinetic, interaction, contact   mixed estimates; extrapolate them
+                       with the VMC values of
+                       `vmc.EnsembleSampling.energy_components`: 2 DMC - VMC.
+        The errors are those of the weighted mean over the walkers of this one
+        State, taken as independent: walkers share ancestors, so they are a
+        lower bound."""
+        nw = int(state.num_walkers)
+        confs = np.asarray(state.confs, dtype=np.float64)
+        pos = confs[:nw, model.SysConfSlot.pos, :]
+        weight = np.asarray(state.props.weight, dtype=np.float64)[:nw]
+        cfc = self.model_spec.cfc_spec
+        eng = model.core_funcs._engine(*cfc)
+        rg = () if contact_ranges is None else contact_ranges
+        sums, wsum = eng.energy_parts_weighted(pos, weight, rg)
+        return energy_components(sums, wsum, cfc, contact_ranges,
+                                 num_confs=nw)
 
     def triple_distribution(self, state: State, num_bins, max_span=None):
         """Mixed estimate of the three-body distribution over the live

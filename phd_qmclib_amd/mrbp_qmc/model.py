@@ -372,6 +372,7 @@ class PhysicalFuncs:
         one_body_density(sz, sys_conf)    (),(ns,nop)->()
         pair_distribution(num_bins, sys_conf)  (ns,nop)->(B)
         triple_distribution(num_bins, sys_conf)  (ns,nop)->(B)
+        energy_parts(sys_conf, contact_ranges)   (ns,nop)->(4+K)
         renyi_swap(lengths, sys_conf)     (2,ns,nop)->(K)
         particle_swap(sys_conf)           (2,ns,nop)->()
         one_body_matrix(num_points, sys_conf)  (ns,nop)->(M,M)
@@ -525,6 +526,17 @@ class PhysicalFuncs:
                                 num_groups=len(pos[c0:c0 + step]))[0]
             for c0 in range(0, max(len(pos), 1), step)])
         return sums.reshape(loop + sums.shape[-2:])
+
+    def energy_parts(self, sys_conf, contact_ranges=()):
+        """The local energy of every configuration in parts -> [..., 4 + K]:
+        E, T = sum_i F_i^2 (F the drift), V = sum_i V(z_i), the remainder
+        I = E - T - V, and the windowed contact C_k of every window in
+        `contact_ranges` (`ModelEngine.energy_parts`).  `contact_ranges` is a
+        sequence of at most 16 windows (it fixes the core dimension); the loop
+        dimensions of sys_conf broadcast."""
+        loop, pos = self._conf_batch(sys_conf)
+        parts = self._engine().energy_parts(pos, contact_ranges)
+        return parts.reshape(loop + parts.shape[-1:])
 
     def fourier_density(self, kz_set, sys_conf):
         """Fourier density component with momentum k: sum_i exp(i k z_i)."""

@@ -17,7 +17,8 @@ import attr
 import numpy as np
 
 from .. import utils
-from ..engine import (ModelEngine, VmcEnsemble, natural_orbitals,
+from ..engine import (ModelEngine, VmcEnsemble, energy_components,
+                      natural_orbitals,
                       one_body_matrix_points, pair_distribution_bins,
                       pair_distribution_norm, particle_entropy, renyi_entropy,
                       renyi_lengths,
@@ -356,6 +357,22 @@ class EnsembleSampling:
         return (triple_distribution_bins(L, num_bins, max_span),
                 triple_distribution_norm(mean, n, L, max_span),
                 triple_distribution_norm(stderr, n, L, max_span))
+
+    def energy_components(self, contact_ranges=None):
+        """The energy of the chains' current configurations in parts
+        -> `engine.EnergyComponents`: total, kinetic <sum_i F_i^2>, lattice
+        <sum_i V(z_i)>, the remainder interaction = <E_L - T - V>, and for
+        every window of `contact_ranges` (None: none) the contact
+        <sum_{i<j} delta(z_ij)>, with coupling * contact a second, more
+        precise estimate of the interaction energy that carries a bias of order
+        range^2 (`engine.contact_extrapolate`).  Computed on the rows resident
+        on the device after either move type (no position is copied to the
+        host, the chains are not touched).  The errors are those of the mean
+        over the chains."""
+        parts = self.ensemble.energy_parts_parts(
+            () if contact_ranges is None else contact_ranges)
+        return energy_components(parts, self.num_chains,
+                                 self.model_spec.cfc_spec, contact_ranges)
 
     def renyi_entropy(self, lengths, origin=0.0):
         """Renyi-2 entanglement entropy of the segments
