@@ -438,6 +438,56 @@ int qmc_renyi_swap_reduce_dev(qmc_engine *eng, int64_t nconf,
                               const double *lengths_dev, double origin,
                               double *sums_dev);
 
+/* Renyi-2 replica swap of regions made of up to two disjoint segments, with
+ * the particle number of the region resolved in the reduction (no counterpart
+ * in the reference).  Replicas, origin and t as for qmc_renyi_swap.  Entry k
+ * of regions[nreg][3] is a region X_k = (l1, g, l2): particle z is in X_k when
+ *   t < l1  or  (m1 <= t && t < m2),   m1 = l1 + g,  m2 = m1 + l2,
+ * the marks formed in fp64 in exactly this order; Y_k is the complement.
+ * Limits: l1 > 0, g >= 0, l2 >= 0, m2 < L, all finite; l2 = 0 is a single
+ * segment (its g is not used but must obey the limits); 1 <= nreg <= 4096.
+ * n_x[nconf][nreg] is the number of particles of every configuration in X_k
+ * (exact).  A pair is matched at k when its two replicas hold the same TOTAL
+ * number in X_k; then, with R1' = X(R2) u Y(R1), R2' = X(R1) u Y(R2),
+ *   log_ratio[nconf / 2][nreg] =
+ *       ln|psi(R1')| + ln|psi(R2')| - ln|psi(R1)| - ln|psi(R2)|,
+ * formed from the pair factors across the cut alone,
+ * S(X2,Y1) + S(X1,Y2) - S(X1,Y1) - S(X2,Y2): exactly 0 without interactions
+ * and where either side is empty in both replicas; -inf where the pair is
+ * not matched.  With S2(X) = -ln <swap>, the Renyi-2 mutual information of two
+ * segments A, C is I2 = S2(A) + S2(C) - S2(A u C).  Always fp64:
+ * qmc_engine_set_fast_math does not apply (csrc/qmc_renyi_region.h).
+ * qmc_renyi_region_swap: host buffers, synchronous; either output may be
+ * NULL, not both.  An odd or non-positive nconf, nreg outside [1, 4096], a
+ * region outside the limits or not finite, an origin that is not finite, a
+ * NULL pos / regions is an error. */
+int qmc_renyi_region_swap(qmc_engine *eng, int64_t nconf, const double *pos,
+                          int32_t nreg, const double *regions, double origin,
+                          int32_t *n_x, double *log_ratio);
+/* Same on device-resident buffers, asynchronous on the engine's stream (the
+ * values of regions_dev are not checked: the host does not see them). */
+int qmc_renyi_region_swap_dev(qmc_engine *eng, int64_t nconf,
+                              const double *pos_dev, int32_t nreg,
+                              const double *regions_dev, double origin,
+                              int32_t *n_x_dev, double *log_ratio_dev);
+/* Sums over the P = nconf / 2 pairs, device buffers, asynchronous:
+ * sums_dev[nreg][3 + 2 Q], Q = num_charges in [0, N + 1].  Columns 0, 1, 2 =
+ * sum_p swap, sum_p swap^2, number of matched pairs (the argument of exp
+ * clamped to +-700), as qmc_renyi_swap_reduce_dev.  Column 3 + 2n =
+ * sum_p swap [n_X(R1) = n] and column 4 + 2n = sum_p ([n_X(R1) = n] +
+ * [n_X(R2) = n]), n = 0 ... Q - 1, the latter over every configuration,
+ * matched or not (an exact integer in a double): p(n) = column(4 + 2n) / 2P
+ * is the counting statistics of X, <swap delta_n> = column(3 + 2n) / P =
+ * p(n)^2 Tr rho_n^2, and S2(n) = -ln(<swap delta_n> / p(n)^2) the
+ * charge-resolved entropy.  Charges >= Q are not collected.
+ * nreg (3 + 2 Q) > 2^20 is an error.  Fixed summation order, no
+ * floating-point atomics: two calls give the same bits; the per-pair rows
+ * live in an engine-owned scratch filled in tiles of at most 2^16 pairs. */
+int qmc_renyi_region_swap_reduce_dev(qmc_engine *eng, int64_t nconf,
+                                     const double *pos_dev, int32_t nreg,
+                                     const double *regions_dev, double origin,
+                                     int32_t num_charges, double *sums_dev);
+
 /* Purity of the one-body density matrix by a one-particle replica swap (no
  * counterpart in the reference).  The configurations 2p and 2p + 1 of
  * pos[nconf][N] (nconf even, N <= 512) are the replicas R1 = x1, R2 = x2 of
@@ -589,6 +639,15 @@ int qmc_vmc_energy_parts(qmc_vmc *v, int32_t nrange, const double *ranges,
  * checked as by qmc_renyi_swap. */
 int qmc_vmc_renyi_swap(qmc_vmc *v, int32_t nlen, const double *lengths,
                        double origin, double *out);
+/* Region swap sums of the CURRENT configurations, the chains 2p and 2p + 1
+ * being the replicas of pair p: out[nreg][3 + 2 num_charges] as sums_dev of
+ * qmc_renyi_region_swap_reduce_dev (no counterpart in the reference), on the
+ * resident rows, after either move type; no position leaves the device and
+ * the chain state is not touched.  An odd num_chains is an error.  Host
+ * buffers; synchronous; nreg, regions and origin checked as by
+ * qmc_renyi_region_swap, num_charges as by the reduction. */
+int qmc_vmc_renyi_region_swap(qmc_vmc *v, int32_t nreg, const double *regions,
+                              double origin, int32_t num_charges, double *out);
 /* One-particle swap sums of the CURRENT configurations, the chains 2p and
  * 2p + 1 being the replicas of pair p: out[3] as sums_dev of
  * qmc_particle_swap_reduce_dev, on the resident rows, after either move type

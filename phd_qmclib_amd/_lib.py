@@ -119,6 +119,13 @@ SIGNATURES = {
                                      C.c_double, _vp, _vp]),
     'qmc_renyi_swap_reduce_dev': (C.c_int, [_vp, C.c_int64, _vp, C.c_int32,
                                             _vp, C.c_double, _vp]),
+    'qmc_renyi_region_swap': (C.c_int, [_vp, C.c_int64, _dp, C.c_int32, _dp,
+                                        C.c_double, _i32p, _dp]),
+    'qmc_renyi_region_swap_dev': (C.c_int, [_vp, C.c_int64, _vp, C.c_int32,
+                                            _vp, C.c_double, _vp, _vp]),
+    'qmc_renyi_region_swap_reduce_dev': (C.c_int, [_vp, C.c_int64, _vp,
+                                                   C.c_int32, _vp, C.c_double,
+                                                   C.c_int32, _vp]),
     'qmc_particle_swap': (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp]),
     'qmc_particle_swap_dev': (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp]),
     'qmc_particle_swap_reduce_dev': (C.c_int, [_vp, C.c_int64, _vp, _vp]),
@@ -145,6 +152,8 @@ SIGNATURES = {
     'qmc_vmc_triple_dist': (C.c_int, [_vp, C.c_int32, C.c_double, _dp]),
     'qmc_vmc_energy_parts': (C.c_int, [_vp, C.c_int32, _dp, _dp]),
     'qmc_vmc_renyi_swap': (C.c_int, [_vp, C.c_int32, _dp, C.c_double, _dp]),
+    'qmc_vmc_renyi_region_swap': (C.c_int, [_vp, C.c_int32, _dp, C.c_double,
+                                            C.c_int32, _dp]),
     'qmc_vmc_particle_swap': (C.c_int, [_vp, _dp]),
     'qmc_vmc_obdm_grid': (C.c_int, [_vp, C.c_int32, C.c_int32, _dp]),
     'qmc_vmc_run_block': (C.c_int, [_vp, C.c_int64, _dp, _dp, _i64p, _dp, _dp,

@@ -90,23 +90,16 @@ struct RenyiArgs {
     double origin;
 };
 
-__global__ void __launch_bounds__(64)
-renyi_swap_kernel(const DevModel *__restrict__ mp, RenyiArgs a)
+// Stage 1 of a wavefront's replica pair `row` (2N positions): t as given into
+// traw, then every entry to its rank inside its replica, its table entry to
+// tab and its t to ts.  Ends on a barrier: traw is free from there.
+__device__ __forceinline__ void renyi_order_replicas(
+    const DevModel &m, const double *__restrict__ row, double origin,
+    double *tab, double *ts, double *traw, int lane)
 {
-    const DevModel &m = *mp;
-    extern __shared__ double smem[];
-    const int n = m.n, n2 = 2 * n, K = a.K;
-    double *tab = smem;                          // [2N][4], replicas by t
-    double *ts = smem + 4 * n2;                  // [2N] t in that order
-    double *traw = smem + RENYI_LDS_PER_ENTRY * n2;   // [2N] t as given
-    int *mk = (int *)traw;                       // [K] matched lengths (later)
-    const long long p = blockIdx.x;
-    const int lane = threadIdx.x;
+    const int n = m.n, n2 = 2 * n;
     const int npass = (n2 + 63) / 64;
-    const double *__restrict__ row = a.pos + (size_t)p * n2;
-
-    // Stage 1: t as given, then every entry to its rank inside its replica.
-    const double a0w = wrap_box(a.origin, m.L);
+    const double a0w = wrap_box(origin, m.L);
     for (int pp = 0; pp < npass; ++pp) {
         const int q = lane + 64 * pp;
         const double z = wrap_box((q < n2) ? row[q] : 0.0, m.L);
@@ -136,7 +129,26 @@ renyi_swap_kernel(const DevModel *__restrict__ mp, RenyiArgs a)
             ts[dst] = tq;
         }
     }
-    __syncthreads();                             // traw is the list from here
+    __syncthreads();
+}
+
+__global__ void __launch_bounds__(64)
+renyi_swap_kernel(const DevModel *__restrict__ mp, RenyiArgs a)
+{
+    const DevModel &m = *mp;
+    extern __shared__ double smem[];
+    const int n = m.n, n2 = 2 * n, K = a.K;
+    double *tab = smem;                          // [2N][4], replicas by t
+    double *ts = smem + 4 * n2;                  // [2N] t in that order
+    double *traw = smem + RENYI_LDS_PER_ENTRY * n2;   // [2N] t as given
+    int *mk = (int *)traw;                       // [K] matched lengths (later)
+    const long long p = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int npass = (n2 + 63) / 64;
+
+    // Stage 1: t as given, then every entry to its rank inside its replica.
+    renyi_order_replicas(m, a.pos + (size_t)p * n2, a.origin, tab, ts, traw,
+                         lane);                  // traw is the list from here
 
     // Stage 2: the occupation of A per replica and length; the unmatched and
     // the trivial lengths are finished here.

@@ -14,6 +14,7 @@
 #include "qmc_tripledist.h"
 #include "qmc_energy_parts.h"
 #include "qmc_renyi.h"
+#include "qmc_renyi_region.h"
 #include "qmc_partent.h"
 #include "qmc_obdm_grid.h"
 #include "qmc_cmdiff.h"
@@ -132,6 +133,10 @@ struct qmc_engine {
     // (swap, matched), their column sums, and the lengths and sums of
     // qmc_vmc_renyi_swap
     DevBuf<double> ry_rows, ry_colsum, ry_vmc;
+    // two-segment replica-swap scratch (qmc_renyi_region_swap*): the per-pair
+    // tile of rows (swap, occupations), column by column, and the regions
+    // and sums of qmc_vmc_renyi_region_swap
+    DevBuf<double> rg_rows, rg_vmc;
     // one-particle swap scratch (qmc_particle_swap*): the per-pair tile of
     // means and the sums of qmc_vmc_particle_swap
     DevBuf<double> pe_mean, pe_vmc;
@@ -1998,10 +2003,10 @@ extern "C" int qmc_vmc_energy_parts(qmc_vmc *v, int32_t nrange,
 // ---- Renyi-2 replica swap (csrc/qmc_renyi.h) -----------------------------
 // Tiles as for g2 (PD_TILE, PD_SCRATCH_ELEMS), on rows of 2 nlen per pair.
 static int renyi_check(const char *who, int64_t nconf, int32_t nlen,
-                       double origin)
+                       double origin, const char *what = "nlen")
 {
     if (nlen < 1 || nlen > RENYI_MAX_LEN)
-        return fail(std::string(who) + ": nlen outside [1, " +
+        return fail(std::string(who) + ": " + what + " outside [1, " +
                     std::to_string(RENYI_MAX_LEN) + "]");
     if (nconf <= 0 || (nconf & 1))
         return fail(std::string(who) +
@@ -2151,6 +2156,171 @@ extern "C" int qmc_vmc_renyi_swap(qmc_vmc *v, int32_t nlen,
     int rc = qmc_renyi_swap_reduce_dev(e, v->W, v->pos, nlen, dlen, origin,
                                        e->ry_vmc);
     return rc ? rc : read_doubles(e, out, e->ry_vmc, 3 * K);
+}
+
+// ---- Renyi-2 replica swap of two-segment regions (csrc/qmc_renyi_region.h) --
+// Tiles as for g2 (PD_TILE, PD_SCRATCH_ELEMS), on rows of 2 nreg per pair.
+static int region_check_host_regions(const char *who, const qmc_engine *e,
+                                     int32_t nreg, const double *regions)
+{
+    for (int32_t k = 0; k < nreg; ++k) {
+        const double l1 = regions[3 * k], g = regions[3 * k + 1];
+        const double l2 = regions[3 * k + 2];
+        const double m1 = l1 + g, m2 = m1 + l2;     // as the kernel forms them
+        if (!std::isfinite(l1) || !std::isfinite(g) || !std::isfinite(l2) ||
+            !(l1 > 0.0) || !(g >= 0.0) || !(l2 >= 0.0) || !(m2 < e->dm.L))
+            return fail(std::string(who) + ": region " + std::to_string(k) +
+                        " outside the limits (l1 > 0, g >= 0, l2 >= 0, "
+                        "l1 + g + l2 < L)");
+    }
+    return 0;
+}
+
+static int region_check_charges(const char *who, const qmc_engine *e,
+                                int32_t nreg, int32_t num_charges)
+{
+    if (num_charges < 0 || num_charges > e->dm.n + 1)
+        return fail(std::string(who) +
+                    ": num_charges outside [0, boson_number + 1]");
+    if ((long long)nreg * (3 + 2 * (long long)num_charges) > RG_MAX_SUMS)
+        return fail(std::string(who) +
+                    ": nreg (3 + 2 num_charges) exceeds 2^20");
+    return 0;
+}
+
+// npair device-resident replica pairs -> n_x, log_ratio and / or the rows of
+// a tile of `stride` pairs
+static int region_launch(qmc_engine *e, long long npair, const double *pos_dev,
+                         int32_t K, const double *regions_dev, double origin,
+                         int32_t *n_x, double *log_ratio, double *rows,
+                         long long stride)
+{
+    const size_t n2 = 2 * (size_t)e->dm.n;
+    const size_t lds = renyi_region_lds_bytes(e->dm.n, K);
+    if (e->dm.n > RG_MAX_N || lds > RENYI_LDS_LIMIT)
+        return fail("qmc_renyi_region_swap: boson_number too large for the "
+                    "LDS of a workgroup");
+    allow_lds(renyi_region_kernel, lds);    // 88 KB at N = 512, K = 4096
+    const long long xmax = 1ll << 30;
+    for (long long p0 = 0; p0 < npair; p0 += xmax) {
+        const long long np = std::min(xmax, npair - p0);
+        RegionArgs a{ pos_dev + (size_t)p0 * n2, regions_dev,
+                      n_x ? n_x + (size_t)p0 * 2 * K : nullptr,
+                      log_ratio ? log_ratio + (size_t)p0 * K : nullptr,
+                      rows ? rows + p0 : nullptr, np, stride, (int)K, origin };
+        hipLaunchKernelGGL(renyi_region_kernel, dim3((unsigned)np), dim3(64),
+                           lds, e->stream, e->dm_dev, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int qmc_renyi_region_swap_dev(qmc_engine *e, int64_t nconf,
+                                         const double *pos, int32_t nreg,
+                                         const double *regions, double origin,
+                                         int32_t *n_x, double *log_ratio)
+{
+    if (!e || !pos || !regions || (!n_x && !log_ratio))
+        return fail("qmc_renyi_region_swap_dev: null argument");
+    if (renyi_check("qmc_renyi_region_swap_dev", nconf, nreg, origin, "nreg"))
+        return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    return region_launch(e, nconf / 2, pos, nreg, regions, origin, n_x,
+                         log_ratio, nullptr, 0);
+}
+
+extern "C" int qmc_renyi_region_swap_reduce_dev(
+    qmc_engine *e, int64_t nconf, const double *pos, int32_t nreg,
+    const double *regions, double origin, int32_t num_charges, double *sums)
+{
+    const char *who = "qmc_renyi_region_swap_reduce_dev";
+    if (!e || !pos || !regions || !sums)
+        return fail(std::string(who) + ": null argument");
+    if (renyi_check(who, nconf, nreg, origin, "nreg") ||
+        region_check_charges(who, e, nreg, num_charges))
+        return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n2 = 2 * (size_t)e->dm.n;
+    const int C = 2 * nreg;                     // columns of a pair's row
+    const long long npair = nconf / 2;
+    const long long tile = std::min<long long>(
+        npair, std::min(PD_TILE, PD_SCRATCH_ELEMS / C));
+    if (e->rg_rows.reserve((size_t)tile * C)) return 1;
+    for (long long p0 = 0; p0 < npair; p0 += tile) {
+        const long long np = std::min(tile, npair - p0);
+        if (region_launch(e, np, pos + (size_t)p0 * n2, nreg, regions, origin,
+                          nullptr, nullptr, e->rg_rows.get(), tile))
+            return 1;
+        hipLaunchKernelGGL(renyi_region_reduce_kernel,
+                           dim3(nreg, 1 + num_charges), dim3(256), 0,
+                           e->stream, e->rg_rows.get(), np, tile, (int)nreg,
+                           (int)num_charges, p0 > 0 ? 1 : 0, sums);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int qmc_renyi_region_swap(qmc_engine *e, int64_t nconf,
+                                     const double *pos, int32_t nreg,
+                                     const double *regions, double origin,
+                                     int32_t *n_x, double *log_ratio)
+{
+    if (!e || !pos || !regions || (!n_x && !log_ratio))
+        return fail("qmc_renyi_region_swap: null argument");
+    if (renyi_check("qmc_renyi_region_swap", nconf, nreg, origin, "nreg") ||
+        region_check_host_regions("qmc_renyi_region_swap", e, nreg, regions))
+        return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n = (size_t)e->dm.n, K = (size_t)nreg;
+    // an even number of configurations to a tile: whole pairs
+    const long long tile = std::max<long long>(
+        2, std::min<long long>(
+               nconf, PD_SCRATCH_ELEMS / (long long)std::max(n, K)) & ~1ll);
+    DevBuf<double> dreg, dpos, dlr;
+    DevBuf<int32_t> dnx;
+    if (dreg.alloc(3 * K) || dpos.alloc((size_t)tile * n) ||
+        (n_x && dnx.alloc((size_t)tile * K)) ||
+        (log_ratio && dlr.alloc((size_t)(tile / 2) * K)))
+        return 1;
+    HIP_TRY(hipMemcpyAsync(dreg, regions, 3 * K * sizeof(double),
+                           hipMemcpyHostToDevice, e->stream));
+    // log_ratio has a row per pair: half a row per configuration
+    return run_host_tiles(e, nconf, tile, pos, dpos,
+                          { { n_x, dnx.get(), K * sizeof(int32_t) },
+                            { log_ratio, dlr.get(), K * sizeof(double) / 2 } },
+                          [&](long long nc) {
+        return region_launch(e, nc / 2, dpos, nreg, dreg, origin, dnx.get(),
+                             dlr.get(), nullptr, 0);
+    });
+}
+
+// Region sums of the CURRENT configurations of the chains, chains 2p and
+// 2p + 1 the replicas of pair p, on the resident rows (symmetric in the
+// particles of a row, as qmc_vmc_renyi_swap); the chain state is only read.
+extern "C" int qmc_vmc_renyi_region_swap(qmc_vmc *v, int32_t nreg,
+                                         const double *regions, double origin,
+                                         int32_t num_charges, double *out)
+{
+    const char *who = "qmc_vmc_renyi_region_swap";
+    if (!v || !regions || !out)
+        return fail(std::string(who) + ": null argument");
+    qmc_engine *e = v->eng;
+    if (v->W & 1)
+        return fail(std::string(who) + ": an odd number of chains has no "
+                    "replica pairs");
+    if (renyi_check(who, v->W, nreg, origin, "nreg") ||
+        region_check_host_regions(who, e, nreg, regions) ||
+        region_check_charges(who, e, nreg, num_charges))
+        return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t K = (size_t)nreg, cols = 3 + 2 * (size_t)num_charges;
+    if (e->rg_vmc.reserve((cols + 3) * K)) return 1;
+    double *dreg = e->rg_vmc + cols * K;
+    HIP_TRY(hipMemcpyAsync(dreg, regions, 3 * K * sizeof(double),
+                           hipMemcpyHostToDevice, e->stream));
+    int rc = qmc_renyi_region_swap_reduce_dev(e, v->W, v->pos, nreg, dreg,
+                                              origin, num_charges, e->rg_vmc);
+    return rc ? rc : read_doubles(e, out, e->rg_vmc, cols * K);
 }
 
 

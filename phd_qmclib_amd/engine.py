@@ -162,6 +162,87 @@ def renyi_entropy(sums, num_pairs):
         return -np.log(mean), stderr / mean, sums[:, 2] / p
 
 
+def renyi_regions(supercell_size, regions):
+    """Regions of the two-segment replica-swap estimator as a contiguous fp64
+    array [K, 3] of (l1, g, l2): 1 to 4096 rows, all finite, l1 > 0, g >= 0,
+    l2 >= 0 and (l1 + g) + l2 < L; anything else a ValueError."""
+    rg = np.ascontiguousarray(regions, dtype=np.float64)
+    if (rg.ndim != 2 or rg.shape[1] != 3
+            or not 1 <= rg.shape[0] <= MAX_RENYI_LENGTHS):
+        raise ValueError('regions[K, 3] of 1 to %d rows (l1, g, l2) expected'
+                         % MAX_RENYI_LENGTHS)
+    end = (rg[:, 0] + rg[:, 1]) + rg[:, 2]
+    if not (np.all(np.isfinite(rg)) and np.all(rg[:, 0] > 0.0)
+            and np.all(rg[:, 1:] >= 0.0)
+            and np.all(end < float(supercell_size))):
+        raise ValueError('every region needs l1 > 0, g >= 0, l2 >= 0 and '
+                         'l1 + g + l2 < supercell_size')
+    return rg
+
+
+MAX_RENYI_REGION_SUMS = 1 << 20    # RG_MAX_SUMS of csrc/qmc_renyi_region.h
+
+
+def _num_charges(num_charges, boson_number, nreg):
+    if num_charges is None:
+        num_charges = int(boson_number) + 1
+    q = int(num_charges)
+    if q != num_charges or not 0 <= q <= int(boson_number) + 1:
+        raise ValueError('num_charges must be an integer in '
+                         '[0, boson_number + 1]')
+    if nreg * (3 + 2 * q) > MAX_RENYI_REGION_SUMS:
+        raise ValueError('nreg (3 + 2 num_charges) exceeds 2^20')
+    return q
+
+
+class ResolvedRenyi(t.NamedTuple):
+    """`renyi_resolved`: the Renyi-2 entropy of K regions, its error and the
+    matched fraction as `renyi_entropy` gives them, and the resolution by the
+    particle number n = 0 ... Q - 1 of the region."""
+    entropy: np.ndarray           # [K]
+    entropy_err: np.ndarray       # [K]
+    p_match: np.ndarray           # [K]
+    charge_prob: np.ndarray       # [K, Q] p(n), the counting statistics
+    charge_swap: np.ndarray       # [K, Q] <swap delta(n_X = n)>
+    charge_entropy: np.ndarray    # [K, Q] S2(n)
+
+
+def renyi_resolved(sums, num_pairs, num_charges):
+    """Charge-resolved Renyi-2 entropies from the region sums[K, 3 + 2Q] of
+    `ModelEngine.renyi_region_swap_reduce_dev` over P = `num_pairs` replica
+    pairs -> ResolvedRenyi.  entropy, entropy_err and p_match are
+    `renyi_entropy` of the columns 0-2.  charge_prob[K, Q] = column(4 + 2n) /
+    (2P) is the probability p(n) that the region holds n particles,
+    charge_swap[K, Q] = column(3 + 2n) / P = <swap delta(n_X = n)> =
+    p(n)^2 Tr rho_n^2, and charge_entropy = -ln(charge_swap / charge_prob^2)
+    the entropy S2(n) of the block of rho_X with n particles, nan where
+    charge_swap is 0 (no matched pair held n particles).  With Q = N + 1 every
+    charge is collected and sum_n charge_swap = <swap>, sum_n charge_prob =
+    1."""
+    sums = np.asarray(sums, dtype=np.float64)
+    p, q = int(num_pairs), int(num_charges)
+    if q != num_charges or q < 0:
+        raise ValueError('num_charges must be a non-negative integer')
+    if sums.ndim != 2 or sums.shape[1] != 3 + 2 * q:
+        raise ValueError('sums[K, 3 + 2 num_charges] expected')
+    s2, s2_err, p_match = renyi_entropy(sums[:, :3], num_pairs)
+    prob = sums[:, 4::2] / (2.0 * p)
+    swap = sums[:, 3::2] / p
+    with np.errstate(divide='ignore', invalid='ignore'):
+        s2n = np.where(swap > 0.0, -np.log(swap / prob ** 2), np.nan)
+    return ResolvedRenyi(s2, s2_err, p_match, prob, swap, s2n)
+
+
+def renyi_mutual_information(s_a, s_c, s_ac, err_a, err_c, err_ac):
+    """Renyi-2 mutual information I2(A:C) = S2(A) + S2(C) - S2(A u C) of two
+    disjoint segments -> (I2, I2_err).  I2_err is the quadrature sum of the
+    three errors and only indicative: estimates taken from the same replica
+    pairs are correlated, as `contact_extrapolate` says of its own."""
+    s = [np.asarray(x, dtype=np.float64) for x in (s_a, s_c, s_ac)]
+    e = [np.asarray(x, dtype=np.float64) for x in (err_a, err_c, err_ac)]
+    return (s[0] + s[1] - s[2], np.sqrt(e[0] ** 2 + e[1] ** 2 + e[2] ** 2))
+
+
 def particle_entropy(sums, num_pairs):
     """One-particle Renyi-2 entropy from the one-particle swap
     sums[3] = sum m, sum m^2, P over `num_pairs` = P replica pairs
@@ -1036,6 +1117,51 @@ class ModelEngine:
             self._h, self._num_replicas(nconf), pos_ptr, int(nlen),
             lengths_ptr, _renyi_origin(origin), sums_ptr))
 
+    def _regions(self, regions):
+        return renyi_regions(self.cfc_spec.model_params.supercell_size,
+                             regions)
+
+    def renyi_region_swap(self, pos, regions, origin=0.0):
+        """Replica swap of the regions X_k = regions[k] = (l1, g, l2) -- the
+        segments [origin, origin + l1) and [origin + l1 + g,
+        origin + l1 + g + l2) of the ring; l2 = 0 is a single segment --
+        between the rows (2p, 2p + 1) of pos[W, N], W even
+        -> (n_x[W, K] (int32), log_ratio[W / 2, K]): the particles of every
+        row inside X_k, and ln|psi(R1') psi(R2') / (psi(R1) psi(R2))| of the
+        pair with its particles inside X_k exchanged, -inf where the two rows
+        hold different totals there.  S2(X) = -ln(mean exp(log_ratio)) over
+        independent pairs drawn from |psi|^2; I2 = S2(A) + S2(C) - S2(A u C)
+        (`renyi_mutual_information`)."""
+        pos = _pos2d(pos, self.num_particles)
+        rg, a0 = self._regions(regions), _renyi_origin(origin)
+        W = self._num_replicas(pos.shape[0])
+        n_x = np.zeros((W, rg.shape[0]), dtype=np.int32)
+        log_ratio = np.zeros((W // 2, rg.shape[0]))
+        check(self._lib.qmc_renyi_region_swap(
+            self._h, W, ptr(pos), rg.shape[0], ptr(rg), a0,
+            ptr(n_x, _lib._i32p), ptr(log_ratio)))
+        return n_x, log_ratio
+
+    def renyi_region_swap_dev(self, nconf, pos_ptr, nreg, regions_ptr, origin,
+                              n_x_ptr, log_ratio_ptr):
+        """Asynchronous region swap on device-resident buffers (raw
+        pointers): pos[nconf, N], regions[nreg, 3] (fp64) -> n_x[nconf, nreg]
+        (int32) and log_ratio[nconf / 2, nreg]; either output may be 0."""
+        check(self._lib.qmc_renyi_region_swap_dev(
+            self._h, self._num_replicas(nconf), pos_ptr, int(nreg),
+            regions_ptr, _renyi_origin(origin), n_x_ptr, log_ratio_ptr))
+
+    def renyi_region_swap_reduce_dev(self, nconf, pos_ptr, nreg, regions_ptr,
+                                     origin, num_charges, sums_ptr):
+        """Asynchronous sums over the nconf / 2 replica pairs, device buffers:
+        sums[nreg, 3 + 2 Q] = sum swap, sum swap^2, matched pairs, then per
+        charge n < Q = num_charges sum swap [n_X(R1) = n] and the number of
+        configurations with n particles in the region, in a fixed summation
+        order (`renyi_resolved` turns them into entropies)."""
+        check(self._lib.qmc_renyi_region_swap_reduce_dev(
+            self._h, self._num_replicas(nconf), pos_ptr, int(nreg),
+            regions_ptr, _renyi_origin(origin), int(num_charges), sums_ptr))
+
     def particle_swap(self, pos, matrix=False):
         """One-particle replica swap between the rows (2p, 2p + 1) of
         pos[W, N], W even, N <= 512 -> mean[W / 2], or with `matrix`
@@ -1217,6 +1343,21 @@ class VmcEnsemble:
         out = np.zeros((ln.size, 3))
         check(self._lib.qmc_vmc_renyi_swap(self._h, ln.size, ptr(ln), a0,
                                            ptr(out)))
+        return out
+
+    def renyi_region_parts(self, regions, origin=0.0,
+                           num_charges=0) -> np.ndarray:
+        """Region swap sums of the current configurations, the chains 2p and
+        2p + 1 being the replicas of pair p -> [K, 3 + 2 num_charges]
+        (`ModelEngine.renyi_region_swap_reduce_dev`; None collects every
+        charge, N + 1 of them); computed on the resident rows, which are only
+        read.  An odd number of chains is a ValueError."""
+        rg, a0 = self.engine._regions(regions), _renyi_origin(origin)
+        q = _num_charges(num_charges, self.num_particles, rg.shape[0])
+        ModelEngine._num_replicas(self.num_chains)
+        out = np.zeros((rg.shape[0], 3 + 2 * q))
+        check(self._lib.qmc_vmc_renyi_region_swap(
+            self._h, rg.shape[0], ptr(rg), a0, q, ptr(out)))
         return out
 
     def particle_swap_parts(self) -> np.ndarray:

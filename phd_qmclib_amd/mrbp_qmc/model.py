@@ -374,6 +374,7 @@ class PhysicalFuncs:
         triple_distribution(num_bins, sys_conf)  (ns,nop)->(B)
         energy_parts(sys_conf, contact_ranges)   (ns,nop)->(4+K)
         renyi_swap(lengths, sys_conf)     (2,ns,nop)->(K)
+        renyi_region_swap(regions, sys_conf)  (2,ns,nop)->(K)
         particle_swap(sys_conf)           (2,ns,nop)->()
         one_body_matrix(num_points, sys_conf)  (ns,nop)->(M,M)
         fourier_density(kz_set, sys_conf) (nkz),(ns,nop)->(nkz)   complex
@@ -484,6 +485,27 @@ class PhysicalFuncs:
             raise ValueError('sys_conf must have the core shape (2, ns, nop)')
         loop, pos = self._conf_batch(sys_conf)
         _, log_ratio = self._engine().renyi_swap(pos, lengths, origin)
+        swap = np.exp(np.clip(log_ratio, -700.0, 700.0))
+        swap[np.isneginf(log_ratio)] = 0.0
+        return swap.reshape(loop[:-1] + swap.shape[-1:])
+
+    def renyi_region_swap(self, regions, sys_conf, origin=0.0):
+        """Replica-swap ratio of regions made of up to two segments: as
+        `renyi_swap`, for every region X_k = regions[k] = (l1, g, l2), the
+        segments [origin, origin + l1) and [origin + l1 + g,
+        origin + l1 + g + l2) of the ring (l2 = 0: the first alone), with the
+        particles inside X_k exchanged between the replicas, 0 where the two
+        hold different totals there.  The mean over independent pairs drawn
+        from |psi|^2 is exp(-S2(X_k)), and S2(A) + S2(C) - S2(A u C) the
+        Renyi-2 mutual information of the two segments (variational, of the
+        Bijl-Jastrow state).  `regions` (l1 > 0, g >= 0, l2 >= 0,
+        l1 + g + l2 < L) and `origin` are shared by the batch; the loop
+        dimensions of sys_conf in front of the replica axis broadcast."""
+        sys_conf = np.asarray(sys_conf, dtype=np.float64)
+        if sys_conf.ndim < 3 or sys_conf.shape[-3] != 2:
+            raise ValueError('sys_conf must have the core shape (2, ns, nop)')
+        loop, pos = self._conf_batch(sys_conf)
+        _, log_ratio = self._engine().renyi_region_swap(pos, regions, origin)
         swap = np.exp(np.clip(log_ratio, -700.0, 700.0))
         swap[np.isneginf(log_ratio)] = 0.0
         return swap.reshape(loop[:-1] + swap.shape[-1:])

@@ -21,7 +21,7 @@ from ..engine import (ModelEngine, VmcEnsemble, energy_components,
                       natural_orbitals,
                       one_body_matrix_points, pair_distribution_bins,
                       pair_distribution_norm, particle_entropy, renyi_entropy,
-                      renyi_lengths,
+                      renyi_lengths, renyi_mutual_information, renyi_resolved,
                       triple_distribution_bins, triple_distribution_norm)
 from ..qmc_base import vmc as vmc_base
 from . import model
@@ -390,6 +390,59 @@ class EnsembleSampling:
         ln = renyi_lengths(self.model_spec.supercell_size, lengths)
         parts = self.ensemble.renyi_parts(ln, origin)
         return (ln,) + renyi_entropy(parts, self.num_chains // 2)
+
+    def renyi_entropy_resolved(self, lengths, origin=0.0, num_charges=None):
+        """Charge-resolved Renyi-2 entropies of the segments
+        A_k = [origin, origin + lengths[k]) by replica swap over the chains'
+        current configurations, as `renyi_entropy` -> `engine.ResolvedRenyi`:
+        S2, its error and the matched fraction, and for every particle number
+        n < num_charges (None: all N + 1) of the segment the counting
+        statistics p(n), <swap delta(n_A = n)> and the entropy S2(n) of that
+        block of rho_A.  The resolution is done in the device reduction; the
+        chains are not touched and an even `num_chains` is needed."""
+        ln = renyi_lengths(self.model_spec.supercell_size, lengths)
+        q = (self.model_spec.boson_number + 1 if num_charges is None
+             else num_charges)
+        regions = np.stack([ln, np.zeros_like(ln), np.zeros_like(ln)], axis=1)
+        parts = self.ensemble.renyi_region_parts(regions, origin, q)
+        return renyi_resolved(parts, self.num_chains // 2, q)
+
+    def renyi_mutual_information(self, length, separations, origin=0.0,
+                                 second_length=None):
+        """Renyi-2 mutual information I2(A:C) = S2(A) + S2(C) - S2(A u C)
+        between the segment A = [origin, origin + length) and the segments
+        C_k = [origin + length + separations[k], ... + second_length) (None:
+        `length`) by replica swap over the chains' current configurations
+        -> (separations, I2, I2_err, S2_A, S2_C, S2_AC), S2_A a number and the
+        others arrays over the separations.  One region call at `origin` gives
+        A and every A u C_k; S2(C_k) takes a call at the origin of C_k (in a
+        lattice with defects C is not a translate of A), one per distinct
+        separation.  I2_err is the quadrature sum of the three errors and only
+        indicative (`engine.renyi_mutual_information`).  The chains are not
+        touched and an even `num_chains` is needed; S2 is variational, of the
+        Bijl-Jastrow state."""
+        l1 = float(length)
+        l2 = l1 if second_length is None else float(second_length)
+        sep = np.ascontiguousarray(separations, dtype=np.float64)
+        if sep.ndim != 1 or sep.size < 1:
+            raise ValueError('separations must be a 1-d array')
+        regions = np.concatenate(
+            [[[l1, 0.0, 0.0]],
+             np.stack([np.full_like(sep, l1), sep, np.full_like(sep, l2)],
+                      axis=1)])
+        pairs = self.num_chains // 2
+        s2, err, _ = renyi_entropy(
+            self.ensemble.renyi_region_parts(regions, origin, 0), pairs)
+        s_c, err_c = np.empty_like(sep), np.empty_like(sep)
+        distinct, inverse = np.unique(sep, return_inverse=True)
+        for j, g in enumerate(distinct):
+            s, e, _ = renyi_entropy(
+                self.ensemble.renyi_region_parts(
+                    [[l2, 0.0, 0.0]], float(origin) + l1 + g, 0), pairs)
+            s_c[inverse == j], err_c[inverse == j] = s[0], e[0]
+        i2, i2_err = renyi_mutual_information(s2[0], s_c, s2[1:], err[0],
+                                              err_c, err[1:])
+        return sep, i2, i2_err, float(s2[0]), s_c, s2[1:]
 
     def particle_entropy(self):
         """Purity of the one-body density matrix and the one-particle
