@@ -370,6 +370,15 @@ __device__ __forceinline__ double wrap_box(double z, double L)
     return zw;
 }
 
+// The same wrap for a position known to lie in [-L, 2L): the two adds and
+// selects of wrap_box without the wide-excursion test and its division.  The
+// fused VMC launch takes it while every stored position of its chain is inside
+// [0, L) and no move is longer than L (vmc_step_kernel: `near`).
+__device__ __forceinline__ double wrap_box_near(double z, double L)
+{
+    return (z < 0.0) ? z + L : (z >= L) ? z - L : z;
+}
+
 // Slot (index into the walker's row of positions) held by (lane gl, register p)
 // of a lane group; >= n = none.
 // One walker per wavefront with several particles per lane (N > 64): a lane

@@ -91,25 +91,37 @@ __device__ __forceinline__ double qmc_lane_f64(double v, int k)
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
-// The fused VMC yields (vmc_step_kernel, VmcFused): the accept thresholds of 64
-// yields at once, one yield per lane.  The accept draw of a step is made of the
+// The fused VMC yields (vmc_step_kernel, VmcFused): the accept thresholds of
+// VMC_THR_YIELDS yields at once.  The accept draw of a step is made of the
 // second words of the move blocks of particles 0 and 1, and a block's counter
-// is (chain, step, particle index): it needs neither the labels nor the row,
-// so lane l draws both blocks of step `step0 + l` itself and takes the
-// logarithm there -- 64 logarithms for the price of one, and the yield reads
-// its threshold h = log(u) / 2 with two readlanes.  u = 0 (accept whatever the
-// ratio is) is kept as a NaN.  The Metropolis test adds h to log|psi|; the
-// per-yield kernels form 0.5 log(u) + log|psi| in one fused multiply-add: the
-// product by 0.5 is exact, so both round the same sum once.  (n = 1: particle
-// 0 gives both words, as in vmc_step_kernel.)
+// is (chain, step, particle index): it needs neither the labels nor the row.
+// Lanes 0-31 draw particle 0's block of step `step0 + lane`, lanes 32-63
+// particle 1's block of step `step0 + lane - 32`, the half-waves exchange their
+// words and every lane takes the logarithm of the draw of step `step0 + (lane
+// & 31)` -- 32 logarithms for the price of one, and the yield reads its
+// threshold h = log(u) / 2 with two readlanes.  (Round 13: one Philox sequence
+// per refill where lane l drew both blocks of step `step0 + l`; a block of at
+// most 32 yields, the benchmark's 16 among them, used less than half of those.
+// The words, and so every threshold, are the same numbers.)  u = 0 (accept
+// whatever the ratio is) is kept as a NaN.  The Metropolis test adds h to
+// log|psi|; the per-yield kernels form 0.5 log(u) + log|psi| in one fused
+// multiply-add: the product by 0.5 is exact, so both round the same sum once.
+// (n = 1: particle 0 gives both words, as in vmc_step_kernel.)
+static constexpr unsigned int VMC_THR_YIELDS = 32u;
 __device__ __forceinline__ double vmc_accept_thresholds(uint64_t seed,
                                                         uint32_t slot,
                                                         uint32_t step0, int lane,
                                                         int n)
 {
-    uint32_t m0, m1, hi, lo;
-    vmc_move_block(seed, slot, step0 + (uint32_t)lane, 0u, m0, hi);
-    vmc_move_block(seed, slot, step0 + (uint32_t)lane, n == 1 ? 0u : 1u, m1, lo);
+    const bool upper = lane >= 32;
+    uint32_t mv, own;
+    vmc_move_block(seed, slot, step0 + (uint32_t)(lane & 31),
+                   (upper && n != 1) ? 1u : 0u, mv, own);
+    // (v_permlane32_swap: lanes 32-63 of the first operand trade places with
+    // lanes 0-31 of the second.  Both are `own`: the first comes back as
+    // particle 0's words in both half-waves, the second as particle 1's.)
+    const auto sw = __builtin_amdgcn_permlane32_swap(own, own, false, false);
+    const uint32_t hi = sw[0], lo = sw[1];
     const double ua = u53(hi, lo);
     const double h = 0.5 * log_pos(ua);
     return ua <= 0.0 ? __builtin_nan("") : h;
@@ -340,7 +352,10 @@ struct VmcArgs {
 // shape 115 (4 waves, as its per-yield kernel).  Measured against the per-yield
 // launches, profiles/r06_ab_variants.txt: -9.5 % per step at N = 64, -8.8 % at
 // N = 48, -8.5 % at N = 128.  (Round 12: the unpadded N = 64 kernel hoists them
-// after all, at 72 registers -- the comment at the yield loop.)
+// after all, at 72 registers -- the comment at the yield loop.  Round 13: the
+// launch runs the first yield of a block as well and restarts the block sums
+// at its record load -- `reset_sums` -- so a block is one launch; until then
+// the per-yield kernel ran that yield in a launch of its own.)
 template <int G, int P, bool ZC>
 struct VmcFused {
     static constexpr bool ON = G == 64 && !ZC && (P == 1 || P == 2);
@@ -348,10 +363,13 @@ struct VmcFused {
 
 // LEAN = the production path (Philox uniform proposal, per-chain block sums
 // only); the full variant adds the test-only tape replay, the Gaussian
-// proposal and the per-step series.  STEADY (LEAN only): a yield after the
-// first of a block -- `forced` and `reset_sums` are zero, and the forced-move
-// and initial-state paths are not compiled (qmc_vmc_run_block launches it for
-// every yield y >= 1; on VmcFused shapes once, for all of them).
+// proposal and the per-step series.  STEADY (LEAN only): a yield that is not
+// the forced initial one -- `forced` is zero, and the forced-move and
+// initial-state paths are not compiled.  On VmcFused shapes qmc_vmc_run_block
+// launches it ONCE per block, for every yield of it, and the sums restart at
+// the record load when `reset_sums` is set (round 13; only the forced initial
+// yield of a generator still takes the per-yield kernel first).  On the other
+// shapes it runs every yield y >= 1 of a block, `reset_sums` zero.
 template <int G, int P, bool PAD, bool ZC, bool LEAN, typename R = double,
           bool STEADY = false>
 __global__ void __launch_bounds__(WalkBlock<G>::N, lb_waves(G, P, ZC, LB_VMC_P2))
@@ -376,7 +394,10 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
     // The very first yield of a generator is the initial state itself,
     // flagged ACCEPTED (qmc_base/vmc.py:616-618): a forced zero move.
     const bool forced = !STEADY && a.forced != 0;
-    const bool reset_sums = !STEADY && a.reset_sums != 0;
+    // (a fused STEADY launch may be the whole block -- a.reset_sums -- or what
+    // follows the forced yield of a generator's first block)
+    const bool reset_sums =
+        (!STEADY || VmcFused<G, P, ZC>::ON) && a.reset_sums != 0;
 
     // The chain's scalars are needed only after the pair sum; their load is
     // issued here so that the memory latency runs under it.  One chain per
@@ -406,7 +427,8 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
     constexpr bool FUSED = STEADY && VmcFused<G, P, ZC>::ON;
     double zc[P];
     int labc[P];
-    // FUSED: lane l holds log(u) / 2 of the accept draw of yield (s & ~63) + l
+    // FUSED: lane l holds log(u) / 2 of the accept draw of yield
+    // (s & ~31) + (l & 31)
     [[maybe_unused]] double thr = 0.0;
     if constexpr (FUSED) {
 #pragma unroll
@@ -415,6 +437,22 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
             zc[p] = (i < n) ? a.pos[wr * n + i] : 0.0;
             labc[p] = (i < n) ? (int)a.label[wr * n + i] : i;
         }
+    }
+    // FUSED: every stored position of the chain is inside [0, L) and no move is
+    // longer than L -- a proposal then lies inside (-L, 2L) and the wrap needs
+    // neither the wide-excursion test nor its division (wrap_box_near: the same
+    // adds and selects).  Wave-uniform, decided once per launch: an accepted
+    // move leaves the row inside the box.  (The row of a chain is as the caller
+    // gave it until its first accepted move, anywhere at all: the full wrap_box
+    // then, for the launch.)
+    [[maybe_unused]] bool near = false;
+    if constexpr (FUSED) {
+        bool inside = true;
+#pragma unroll
+        for (int p = 0; p < P; ++p)
+            inside = inside && zc[p] >= 0.0 && zc[p] < m.L;
+        near = __builtin_amdgcn_ballot_w64(!inside) == 0ull &&
+               a.move_spread >= 0.0 && a.move_spread <= 2.0 * m.L;
     }
     bool any_acc = false;     // FUSED: some yield of the launch accepted
     const unsigned int nst = FUSED ? a.nsteps : 1u;
@@ -437,8 +475,8 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
     constexpr bool REDERIVE = FUSED && (P != 1 || PAD);
     const int gl = REDERIVE ? qmc_opaque(gl_top) : gl_top;
     if constexpr (FUSED) {
-        // (a block longer than 64 yields refills every 64 trips)
-        if ((s & 63u) == 0u)
+        // (a block longer than that refills every VMC_THR_YIELDS trips)
+        if ((s & (VMC_THR_YIELDS - 1u)) == 0u)
             thr = vmc_accept_thresholds(a.seed, slot, step, gl, n);
     }
     QMC_SECTION("load+philox+wrap");
@@ -498,7 +536,7 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
 #pragma clang fp contract(off)
             zs = zp + d;
         }
-        zn[p] = wrap_box(zs, m.L);
+        zn[p] = (FUSED && near) ? wrap_box_near(zs, m.L) : wrap_box(zs, m.L);
         if (forced) outside = outside || zn[p] != zp;
     }
     QMC_SECTION("resort");
@@ -619,7 +657,7 @@ vmc_step_kernel(const DevModel *__restrict__ mp, VmcArgs a)
         // lane 0's log|psi| -- the lane whose decision the per-yield kernel
         // takes -- as a scalar: the test and its branch are scalar
         const double w0 = qmc_uniform_f64(wf_new);
-        const double h = qmc_lane_f64(thr, (int)(s & 63u));
+        const double h = qmc_lane_f64(thr, (int)(s & (VMC_THR_YIELDS - 1u)));
         acc = h != h || w0 > wf_cur;
         if (!acc) acc = w0 > h + wf_cur;
         acc = __builtin_amdgcn_readfirstlane((int)acc) != 0;

@@ -343,9 +343,12 @@ struct LaunchVmc {
         const size_t lds = step_lds_bytes<G, P, PAD, ZC>();
         const bool lean = !a.tape && !a.gaussian && !a.ser_wf && !a.ser_e &&
                           !a.ser_stat && !a.ser_pos;
-        // (the steady variant: every yield of a block after its first)
-        const bool steady = lean && !a.forced && !a.reset_sums;
-        *ran = (steady && VmcFused<G, P, ZC>::ON) ? (long long)a.nsteps : 1;
+        // (the steady variant: every yield of a block after its first; on a
+        // VmcFused shape the first as well, unless it is the forced initial
+        // yield -- the fused kernel restarts the sums itself)
+        constexpr bool FUSED = VmcFused<G, P, ZC>::ON;
+        const bool steady = lean && !a.forced && (FUSED || !a.reset_sums);
+        *ran = (steady && FUSED) ? (long long)a.nsteps : 1;
         ProfScope prof(e);
         return with_pair_type<G, ZC>(e, [&](auto r) {
             using R = decltype(r);

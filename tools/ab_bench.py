@@ -18,6 +18,12 @@ ap.add_argument('--bosons', type=int, default=64)
 ap.add_argument('--walkers', type=int, default=1 << 20)
 ap.add_argument('--dmc-walkers', type=int, default=1 << 18)
 ap.add_argument('--steps', type=int, default=48)
+ap.add_argument('--blocks', type=int, default=0,
+                help='time BLOCKS consecutive blocks of --steps yields in one '
+                     'HIP-event bracket on the stream (everything a block costs: '
+                     'its launches, the gaps between them, the record unpack), '
+                     'VMC only; the per-launch events of one block otherwise')
+ap.add_argument('--reps', type=int, default=1, help='with --blocks: brackets timed')
 ap.add_argument('--equil', type=int, default=200)
 ap.add_argument('--tag', default='')
 ap.add_argument('--fast', action='store_true', help='float pair loop')
@@ -46,6 +52,18 @@ done = 0
 while done < a.equil:
     v.run_block(50, sums=False)
     done += 50
+if a.blocks:
+    v.run_block(a.steps, sums=False)
+    for _ in range(a.reps):
+        eng.sync()
+        eng.timer_start()
+        for _ in range(a.blocks):
+            v.run_block(a.steps, sums=False)
+        ms = eng.timer_stop()
+        print(f'{a.tag:24s} VMC N={n} W={a.walkers}: '
+              f'{ms / (a.blocks * a.steps):.4f} ms/step over {a.blocks} blocks '
+              f'of {a.steps}', flush=True)
+    sys.exit(0)
 eng.profile_begin(a.steps)
 v.run_block(a.steps, sums=False)
 nl, tot, mn, mx = eng.profile_end()
